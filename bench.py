@@ -1,7 +1,16 @@
 """SAC gradient steps/s + replay-sample GB/s on MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c4w|c1]
-                    [--precision bf16|fp32] [--no-cpu-baseline]
+                    [--precision bf16|fp32] [--dump-outputs DIR] [--full [--no-cpu-baseline] ...]
+
+A plain run does what the headline figure needs and no more: it builds the
+engine and the replay, warms up, times the K steps and prints the result line
+(metric, value, unit, ms_per_step, dtype, losses of the last step).
+--dump-outputs DIR also writes what the timed path left behind in its last
+step (dump_outputs).  Everything else the benchmark measures -- the per-phase
+event timings and rooflines, the replay gather sweep and its ceilings, the
+bf16 and C3 legs, the bf16-vs-fp32 loss deviation and the CPU baseline -- runs
+only with --full; the --no-* options drop single legs of a --full run.
 
 A "step" is one full SAC gradient step (device sample + gather, target, both
 critic updates, actor update, alpha update, Polyak) on a full synthetic 1e6-row
@@ -341,6 +350,42 @@ class _StubEngine:
         return self.stats[:4].double().tolist()
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(eng, out_dir):
+    """--dump-outputs: what a caller of the timed path (eng.train_graph) holds
+    after its last step, one ``out_dir/<name>.npy`` each: the step's losses,
+    targets y and log pi (the engine's stats buffer) and every state tensor
+    the step updates in place (parameters of the five networks, Adam moments,
+    alpha state, optimiser step counts, RNG step).  float32 tensors stay
+    float32, everything else is written as float64.  The arrays are whole as
+    long as they fit DUMP_MAX_BYTES together (every CONFIGS entry does: 3-6 MB);
+    past that each array keeps a fixed, seeded sample of its elements, in index
+    order.  Weights, replay rows and the device sampler are all seeded by the
+    arguments, so two builds run with the same arguments dump comparable
+    arrays."""
+    B = eng.batch
+    arrays = {"losses": eng.stats[:4], "targets": eng.stats[4:4 + B], "log_pi": eng.stats[4 + B:4 + 2 * B],
+              "alpha_state": eng.alpha_state, "rng_step": eng.rng_step}
+    if hasattr(eng, "state_tensors"):
+        arrays.update({k.replace("/", "_"): v for k, v in eng.state_tensors().items()})
+    host = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy().reshape(-1)
+        host[name] = a if a.dtype == np.float32 else a.astype(np.float64)
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_MAX_BYTES:
+        keep = DUMP_MAX_BYTES / total
+        rng = np.random.default_rng(0)
+        for name, a in host.items():
+            n = max(1, int(a.size * keep))
+            host[name] = a[np.sort(rng.choice(a.size, size=n, replace=False))]
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def launch_ranks(n: int, argv) -> int:
     """``--gpus N`` (N > 1) without torchrun: start one rank process per GPU
     (RANK = LOCAL_RANK = r, WORLD_SIZE = N, MASTER_ADDR 127.0.0.1, a free
@@ -389,6 +434,12 @@ def main():
                     help="replicas (N > 1): gradient steps between the RCCL metric all-reduces (SURVEY §8e)")
     ap.add_argument("--prewarm", type=float, default=0.3,
                     help="seconds of replay gathers before the warm-up steps (device clocks; no SAC step)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the arrays the timed path left in its last step as "
+                         "DIR/<name>.npy (see dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary measurement: phase timings and rooflines, gather sweep, bf16 "
+                         "and C3 legs, bf16 loss deviation, CPU baseline (each --no-* below drops one of them)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-sweep", action="store_true")
     ap.add_argument("--no-bf16", action="store_true")
@@ -417,7 +468,7 @@ def run_rank(args, world, rank, local):
     if stub:
         device = torch.device("cpu")
         sync = lambda: None  # noqa: E731
-        args.no_sweep = args.no_bf16 = args.no_cpu_baseline = args.no_c3 = True
+        args.full = False
     else:
         device = torch.device("cuda", local)
         torch.cuda.set_device(device)
@@ -468,6 +519,8 @@ def run_rank(args, world, rank, local):
         return eng, rb, c, el, ls, aggs
 
     eng, rb, c, elapsed, losses, aggs = timed(args.precision, args.config)
+    if args.dump_outputs:  # before anything else steps the headline engine
+        dump_outputs(eng, args.dump_outputs if rank == 0 else os.path.join(args.dump_outputs, f"rank{rank}"))
     total_steps = args.steps * world
     replica = summarise_aggregates(aggs, world, every) if dist else None
     sps = total_steps / elapsed
@@ -495,11 +548,14 @@ def run_rank(args, world, rank, local):
     if stub:
         line["stub"] = "SAC_BENCH_STUB=1: rank/launcher logic only, no engine"
     else:
-        line.update(measure_phases(args, eng, rb, c, elapsed, sps / world))
+        W = 2 * c["obs"] + c["act"] + 2
+        line["replay_sample_GBps_in_step"] = round(sps / world * c["batch"] * W * 4 / 1e9, 4)
+        if args.full:
+            line.update(measure_phases(args, eng, rb, c, elapsed, sps / world))
         line["losses_last"] = [round(x, 6) for x in losses]
     if replica is not None:
         line["replica_metrics"] = replica
-    if rank == 0 and not stub:
+    if rank == 0 and args.full:
         if not args.no_sweep:
             line.update(sweep_fields(rb, c, device))
         if not args.no_bf16 and args.precision == "fp32" and world == 1:  # single-process leg: no barriers
@@ -572,9 +628,7 @@ def measure_phases(args, eng, rb, c, elapsed, sps_one):
         phases[ph] = {"kernel": kn, "flops_per_launch": flops[i], "avg_launch_ms": round(kern_ms[i], 5),
                       "achieved": round(a, 3), "frac": round(a / peak, 5), "counter_mfma_busy_frac": busy,
                       "counter_source": busy_src}
-    W = 2 * c["obs"] + c["act"] + 2
     return {
-        "replay_sample_GBps_in_step": round(sps_one * c["batch"] * W * 4 / 1e9, 4),
         "phase_ms": [round(x, 5) for x in kern_ms],
         "phase_event_interval_ms": [round(x, 5) for x in phase_ms],
         "event_cost_ms": round(ev_cost, 5),

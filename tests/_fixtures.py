@@ -11,8 +11,50 @@ CONFIGS = ["c1_fixed", "c1_auto", "elu3_clamp", "mix_act", "gelu_tanh", "const_r
 FULL_INIT = ["c1_fixed", "c1_auto", "elu3_clamp", "mix_act", "gelu_tanh", "const_reward"]
 
 
+class NpzParts:
+    """Read-only view of a fixture stored as several archives (<stem>.part0.npz,
+    <stem>.part1.npz, ...: make_golden.save_npz keeps every committed file under
+    1 MiB), with the ``.files`` / ``fx[key]`` / ``key in fx`` interface of
+    numpy's NpzFile.  Every key lives in exactly one part."""
+
+    def __init__(self, paths):
+        self._where = {}
+        for p in paths:
+            z = np.load(p)
+            for k in z.files:
+                assert k not in self._where, (k, p)
+                self._where[k] = z
+        self.files = list(self._where)
+
+    def __getitem__(self, key):
+        return self._where[key][key]
+
+    def __contains__(self, key):
+        return key in self._where
+
+    def __iter__(self):
+        return iter(self.files)
+
+    def __len__(self):
+        return len(self.files)
+
+
+def load_npz(stem):
+    """tests/golden/<stem>.npz, or its parts <stem>.part<k>.npz as one archive."""
+    whole = os.path.join(GOLDEN, f"{stem}.npz")
+    if os.path.exists(whole):
+        return np.load(whole)
+    parts, k = [], 0
+    while os.path.exists(os.path.join(GOLDEN, f"{stem}.part{k}.npz")):
+        parts.append(os.path.join(GOLDEN, f"{stem}.part{k}.npz"))
+        k += 1
+    if not parts:
+        raise FileNotFoundError(whole)
+    return NpzParts(parts)
+
+
 def load(name):
-    fx = np.load(os.path.join(GOLDEN, f"{name}.npz"))
+    fx = load_npz(name)
     meta = json.loads(str(fx["config"]))
     return fx, meta
 

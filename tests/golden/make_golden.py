@@ -498,6 +498,45 @@ def capture_logger(tmp: str) -> dict:
     return out
 
 
+PART_BYTES = 900_000  # committed files stay under 1 MiB
+
+
+def save_npz(stem: str, arrays: dict) -> list:
+    """``savez_compressed`` of ``arrays`` as OUT/<stem>.npz when that file stays
+    under PART_BYTES, else as OUT/<stem>.part0.npz, .part1.npz, ... (keys in
+    their given order, every key in one part, every part under PART_BYTES;
+    tests/_fixtures.load_npz reads either form).  Returns the paths written."""
+    import glob
+    import io
+
+    for old in glob.glob(os.path.join(OUT, f"{stem}.npz")) + glob.glob(os.path.join(OUT, f"{stem}.part*.npz")):
+        os.remove(old)
+
+    def packed(d):
+        buf = io.BytesIO()
+        np.savez_compressed(buf, **d)
+        return buf.getvalue()
+
+    blob = packed(arrays)
+    if len(blob) <= PART_BYTES:
+        parts = [blob]
+    else:
+        parts, cur = [], {}
+        for k, v in arrays.items():
+            if cur and len(packed({**cur, k: v})) > PART_BYTES:
+                parts.append(packed(cur))
+                cur = {}
+            cur[k] = v
+        parts.append(packed(cur))
+        assert all(len(p) <= PART_BYTES for p in parts), "one array alone exceeds PART_BYTES"
+    paths = [os.path.join(OUT, f"{stem}.npz" if len(parts) == 1 else f"{stem}.part{i}.npz")
+             for i in range(len(parts))]
+    for p, b in zip(paths, parts):
+        with open(p, "wb") as f:
+            f.write(b)
+    return paths
+
+
 def main() -> None:
     _install_stubs()
     sys.path.insert(0, REF)
@@ -507,16 +546,16 @@ def main() -> None:
         if only and name not in only:
             continue
         out = capture(name, c)
-        np.savez_compressed(os.path.join(OUT, f"{name}.npz"), **out)
+        save_npz(name, out)
         print(name, "losses:", [out[f"step{k}/out/losses"].tolist() for k in range(1, c["steps"] + 1)])
     if not only or "replay" in only:
-        np.savez_compressed(os.path.join(OUT, "replay_sample.npz"), **capture_replay_sample())
+        save_npz("replay_sample", capture_replay_sample())
         print("replay_sample written")
     if not only or "ckpt" in only:
-        np.savez_compressed(os.path.join(OUT, "ref_ckpt_c1_auto.npz"), **capture_checkpoint())
+        save_npz("ref_ckpt_c1_auto", capture_checkpoint())
         print("ref_ckpt_c1_auto written (+ ref_ckpt_c1_auto.pth from the reference's save_agent)")
     if not only or "loop" in only:
-        np.savez_compressed(os.path.join(OUT, "ref_loop.npz"), **capture_loop())
+        save_npz("ref_loop", capture_loop())
         print("ref_loop written")
     if not only or "logger" in only:
         import tempfile

@@ -59,6 +59,28 @@ def test_bench_single_gpu_runs_in_process():
     assert "replica_metrics" not in line
 
 
+def test_bench_plain_line_full_option_and_dump_outputs(tmp_path):
+    """The plain line holds the headline fields; --steps sets the timed steps
+    (the stub's step counter ends at warm-up + steps: rng_step in the dump);
+    --dump-outputs writes float32 / float64 .npy files; --full is accepted."""
+    import numpy as np
+
+    p = _run(["--gpus", "1", "--steps", "12", "--warmup", "3", "--dump-outputs", str(tmp_path / "d")], _env())
+    assert p.returncode == 0, p.stderr[-3000:]
+    line = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][0])
+    assert line["unit"] == "gradient steps/s" and line["higher_is_better"] is True and line["dtype"] == "fp32"
+    assert line["steps"] == 12 and line["ms_per_step"] >= 0.020  # 12 stub steps of 20 us
+    assert line["value"] == pytest.approx(1e3 / line["ms_per_step"], rel=1e-3)
+    for k in ("phase_ms", "roofline", "value_bf16", "value_c3", "cpu_baseline", "replay_gather_GBps_sweep"):
+        assert k not in line, k
+    d = {f[:-4]: np.load(tmp_path / "d" / f) for f in os.listdir(tmp_path / "d")}
+    assert {"losses", "targets", "log_pi", "alpha_state", "rng_step"} <= set(d)
+    assert all(a.dtype in (np.float32, np.float64) for a in d.values())
+    assert d["rng_step"].tolist() == [15.0] and d["losses"].tolist() == [1.0, 2.0, -0.5, pytest.approx(0.1)]
+    p = _run(["--gpus", "1", "--steps", "4", "--warmup", "1", "--full"], _env())
+    assert p.returncode == 0, p.stderr[-3000:]
+
+
 def test_bench_rejects_gpus_world_size_mismatch():
     p = _run(["--gpus", "3", "--steps", "4"], _env(WORLD_SIZE="2", RANK="0", LOCAL_RANK="0"))
     assert p.returncode != 0

@@ -148,6 +148,36 @@ def test_graph_replay_equals_direct_launches(precision):
     assert eng.opt_steps.cpu().tolist()[:3] == [40.0, 40.0, 40.0]
 
 
+def test_bench_dump_outputs_is_the_engine_state_after_the_last_step(tmp_path):
+    """bench.py --dump-outputs: the arrays written after the timed graph
+    replay are the engine's stats and state tensors of that moment, bit for
+    bit, as float32 / float64 .npy files; a second engine built from the same
+    arguments dumps identical arrays (same seeds -> same inputs)."""
+    import bench
+
+    dumps = []
+    for run in ("a", "b"):
+        eng, rb, _ = _engine("c1", "fp32")
+        eng.train_graph(rb, 0, 4)
+        eng.train_graph(rb, 3, 4)
+        eng.train_graph(rb, 10, 4)  # 2 full chunks + a remainder, as bench.py's timed region
+        bench.dump_outputs(eng, str(tmp_path / run))
+        dumps.append({f[:-4]: np.load(tmp_path / run / f) for f in sorted(os.listdir(tmp_path / run))})
+    d = dumps[0]
+    want = {k.replace("/", "_"): v for k, v in eng.state_tensors().items()}
+    B = eng.batch
+    want.update(losses=eng.stats[:4], targets=eng.stats[4:4 + B], log_pi=eng.stats[4 + B:4 + 2 * B])
+    assert set(d) == set(want)
+    for k, t in want.items():
+        a = d[k]
+        assert a.dtype == (np.float32 if t.dtype == torch.float32 else np.float64), k
+        assert a.shape == (t.numel(),) and np.isfinite(a).all(), k
+        assert np.array_equal(a, t.cpu().numpy().reshape(-1).astype(a.dtype)), k
+        assert np.array_equal(a, dumps[1][k]), k
+    assert d["rng_step"][0] == 13 and np.allclose(d["losses"], eng.losses())
+    assert sum(a.nbytes for a in d.values()) <= bench.DUMP_MAX_BYTES
+
+
 def test_c2_full_size_many_steps_properties():
     """C2 at full size (1e6-row buffer, B=256, bf16): 300 steps stay finite,
     alpha moves the right way, and Polyak keeps targets between their start

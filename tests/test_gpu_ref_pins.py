@@ -20,7 +20,7 @@ import numpy as np
 import pytest
 import torch
 
-from _fixtures import GOLDEN
+from _fixtures import GOLDEN, load_npz
 from oracle import sac_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -32,7 +32,7 @@ NETS = ("policy", "q1", "q2", "q1t", "q2t")
 def _fx():
     import json
 
-    fx = np.load(os.path.join(GOLDEN, "ref_ckpt_c1_auto.npz"))
+    fx = load_npz("ref_ckpt_c1_auto")
     return fx, json.loads(str(fx["config"]))
 
 

@@ -6,7 +6,8 @@ committed:
                         injected steps (agent.py:521-536);
   ref_ckpt_c1_auto.npz  the reference continuing from there (cont/) and a fresh
                         reference agent after load_agent of that file (load/),
-                        steps 3 and 4 with full post-step state;
+                        steps 3 and 4 with full post-step state (stored as
+                        .part0.npz, .part1.npz: _fixtures.load_npz);
   ref_loop.npz          run_training_loop (agent.py:329-418) on the
                         deterministic DetEnv: every training_step call as
                         (transitions pushed so far, len(replay_buffer)), and
@@ -20,7 +21,7 @@ import numpy as np
 import pytest
 import torch
 
-from _fixtures import GOLDEN
+from _fixtures import GOLDEN, load_npz
 from oracle import sac_oracle as O
 
 CKPT = os.path.join(GOLDEN, "ref_ckpt_c1_auto.pth")
@@ -33,7 +34,7 @@ REF_KEYS = {"policy_net_state_dict", "q_net1_state_dict", "q_net2_state_dict", "
 def _fx():
     import json
 
-    fx = np.load(os.path.join(GOLDEN, "ref_ckpt_c1_auto.npz"))
+    fx = load_npz("ref_ckpt_c1_auto")
     return fx, json.loads(str(fx["config"]))
 
 
