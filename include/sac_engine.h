@@ -237,6 +237,90 @@ int sac_engine_clear_status(sac_engine *e, void *stream);
 /* Phase kernel names as they appear in rocprofv3 kernel traces. */
 const char *sac_phase_kernel_name(int32_t phase);
 
+/* ---- device-resident probe environments (sac/envs.py on the device) -------
+ * N copies of one probe environment stepped in lockstep with SAME-STEP
+ * autoreset, exactly as sac.vector_env.SyncVectorEnv drives the host classes:
+ * an environment whose episode ended is reset inside the step, and the
+ * transition of a step is (obs, action, reward, final_obs, terminated |
+ * truncated).  Every probe takes ONE action component (act_dim = 1).  Values
+ * sac/envs.py keeps as Python floats are doubles here, so the fp32-rounded
+ * observations and rewards are the host's.
+ *
+ * RNG (Philox4x32-10, key = seed, counter (t, env row, which << 16 | block)):
+ * which = 2 the action noise of sac_rollout_step (key = the engine's seed,
+ * block = action pair, Box-Muller as the training draws, which use 0 / 1);
+ * which = 3 the observation a SAC_ENV_RANDOM_OBS environment steps to at t,
+ * which = 4 its reset observation at t (key = the environment seed; four
+ * draws per block, u = (word >> 8) * 2^-24, obs = 2u - 1).  The initial reset
+ * is t = 0; the k-th step (k = 0, 1, ...) is t = k + 1. */
+enum sac_env_kind {
+  SAC_ENV_CONSTANT_REWARD = 0,  /* envs.py ConstantRewardEnv: r = reward, terminated at max_steps */
+  SAC_ENV_QUADRATIC_ACTION = 1, /* QuadraticActionRewardEnv: r = -(clip(a) - target)^2 in fp32 */
+  SAC_ENV_RANDOM_OBS = 2,       /* RandomObsBinaryRewardEnv: uniform obs, r = +1 iff |a| <= threshold */
+  SAC_ENV_POINT_MASS = 3        /* OneDPointMassReachEnv: pos += clip(a) * dt, reach goal_pos */
+};
+
+/* The constructor arguments of the sac/envs.py class of `kind` (the others are
+ * ignored); action bounds are rounded to fp32 as its Box stores them. */
+typedef struct sac_env_config {
+  int32_t kind;                 /* enum sac_env_kind */
+  int32_t num_envs;
+  int32_t obs_dim;              /* 1, except SAC_ENV_RANDOM_OBS (its obs_dim argument) */
+  int32_t max_steps;
+  double reward;                              /* SAC_ENV_CONSTANT_REWARD */
+  double target;                              /* SAC_ENV_QUADRATIC_ACTION */
+  double action_low, action_high;             /* SAC_ENV_QUADRATIC_ACTION, SAC_ENV_POINT_MASS */
+  double threshold;                           /* SAC_ENV_RANDOM_OBS */
+  double start_pos, goal_pos, dt, step_penalty, goal_reward, goal_tolerance;  /* SAC_ENV_POINT_MASS */
+  uint64_t seed;                /* observation draws of SAC_ENV_RANDOM_OBS */
+} sac_env_config;
+
+/* One cell of the episode record: written by every environment on every step. */
+typedef struct sac_env_episode {
+  double ret;                   /* return of the episode so far (sum of the double rewards) */
+  int32_t length;               /* steps of the episode so far */
+  int32_t ended;                /* 1 if the episode ended on this step (then ret / length are final) */
+} sac_env_episode;
+
+/* Caller-owned device state of num_envs environments. */
+typedef struct sac_envs {
+  sac_env_config cfg;
+  float *obs;                   /* [num_envs][obs_dim] current observations */
+  int32_t *step;                /* [num_envs] step in the episode (envs.py current_step) */
+  int32_t *ep_length;           /* [num_envs] length of the running episode */
+  double *pos;                  /* [num_envs] SAC_ENV_POINT_MASS position */
+  double *ep_return;            /* [num_envs] return of the running episode */
+  sac_env_episode *episodes;    /* [ring_steps][num_envs] dense ring indexed by t % ring_steps and env row;
+                                   NULL: no record (sac_envs_step only) */
+  int64_t ring_steps;
+} sac_envs;
+
+/* Reset every environment: step and episode counters to 0, the initial
+ * observation (draws of SAC_ENV_RANDOM_OBS: which = 4, t = 0, key `seed`).
+ * Replaces: SyncVectorEnv.reset (sac/vector_env.py:39-46). */
+int sac_envs_reset(const sac_envs *envs, uint64_t seed, void *stream);
+
+/* Vector step t (>= 1) with the caller's actions [num_envs][1]: obs
+ * [num_envs][obs_dim] (after autoreset), final_obs [num_envs][obs_dim] (the
+ * true next state of every environment), reward [num_envs] fp32, terminated /
+ * truncated [num_envs] bytes (0 / 1).
+ * Replaces: SyncVectorEnv.step (sac/vector_env.py:55-71) over sac/envs.py. */
+int sac_envs_step(const sac_envs *envs, const float *actions, uint64_t t, float *obs, float *final_obs,
+                  float *reward, uint8_t *terminated, uint8_t *truncated, void *stream);
+
+/* Act -> step -> store in ONE kernel: the policy forward on the environments'
+ * current observations, the squashed-Gaussian sample (tanh(mu) * scale when
+ * deterministic), the environment step, and the num_envs transitions written
+ * into the replay ring at slots (pos_host + i) % capacity, with the new (size,
+ * pos) and the push generation written to rb->state as sac_replay_push does.
+ * store = 0 leaves the replay untouched (evaluation).  Needs envs->episodes
+ * and num_envs <= capacity.
+ * Replaces: one iteration of SAC.run_vectorized_training_loop up to the
+ * updates (select_actions, env.step, store_transitions; sac/agent.py:343-356
+ * of the reference per environment). */
+int sac_rollout_step(sac_engine *e, const sac_envs *envs, const sac_replay *rb, int64_t size_host,
+                     int64_t pos_host, uint64_t t, int32_t deterministic, int32_t store, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

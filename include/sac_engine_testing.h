@@ -52,6 +52,17 @@ int sac_debug_eps_device(uint64_t seed, uint64_t step, int32_t batch, int32_t ac
  * (default 1 << 22, about 0.3 s); synchronises the stream.  A bound of 0
  * forces the timeout path (tests/test_gpu_engine.py): the API must raise. */
 int sac_engine_debug_set_spin_limit(sac_engine *e, int32_t polls, void *stream);
+/* Host evaluation of the action noise sac_rollout_step draws at vector step t
+ * (the same inline philox_normal2, which = 2): out[i][j], env rows i < n,
+ * action dims j < act_dim.  Counter (t, i, 2 << 16 | j / 2), key seed (the
+ * engine's); Box-Muller gives dims 2p and 2p + 1. */
+int sac_debug_rollout_eps_host(uint64_t seed, uint64_t t, int32_t n, int32_t act_dim, float *out);
+/* Host evaluation of the observation draws of SAC_ENV_RANDOM_OBS (the same
+ * inline code as the device's): out[i][k], env rows i < n, k < obs_dim, for
+ * which = 3 (the observation stepped to at t) or 4 (the reset observation at
+ * t).  Counter (t, i, which << 16 | k / 4), key seed (the environments');
+ * output word k % 4: u = (word >> 8) * 2^-24, obs = 2u - 1 in [-1, 1). */
+int sac_debug_env_obs_host(uint64_t seed, uint64_t t, int32_t which, int32_t n, int32_t obs_dim, float *out);
 #ifdef __cplusplus
 }
 #endif

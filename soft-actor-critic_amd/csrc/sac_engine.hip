@@ -36,6 +36,7 @@
 #include "sac_split.h"
 #include "sac_wide.h"
 #include "sac_pairs.h"
+#include "sac_envs.h"
 
 // ============================================================================ params / replay
 template <typename T>
@@ -1174,6 +1175,7 @@ static void set_lds_attrs(size_t bytes) {
   (void)hipFuncSetAttribute((const void*)sac_actor<T, false>, hipFuncAttributeMaxDynamicSharedMemorySize, b);
   (void)hipFuncSetAttribute((const void*)sac_actor<T, true>, hipFuncAttributeMaxDynamicSharedMemorySize, b);
   (void)hipFuncSetAttribute((const void*)sac_policy_act_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, b);
+  (void)hipFuncSetAttribute((const void*)sac_rollout_step_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, b);
   (void)hipFuncSetAttribute((const void*)sac_target_critic_split<T>, hipFuncAttributeMaxDynamicSharedMemorySize, b);
   (void)hipFuncSetAttribute((const void*)sac_target_critic_pairs<T>, hipFuncAttributeMaxDynamicSharedMemorySize, b);
   (void)hipFuncSetAttribute((const void*)sac_actor_pairs<T>, hipFuncAttributeMaxDynamicSharedMemorySize, b);
@@ -1336,6 +1338,24 @@ static int check_replay(sac_engine* e, const sac_replay* rb) {
   if (rb->obs_dim != e->cfg.obs_dim || rb->act_dim != e->cfg.act_dim)
     return fail(SAC_E_INVALID, "replay dims do not match the engine");
   if (rb->capacity < e->cfg.batch) return fail(SAC_E_NOT_ENOUGH, "replay capacity smaller than the batch");
+  return SAC_OK;
+}
+
+// Configuration first, then pointers: the messages of a bad configuration do not
+// depend on the state being allocated.
+static int check_envs(const sac_envs* ev, bool need_ring) {
+  if (!ev) return fail(SAC_E_INVALID, "null environments");
+  const sac_env_config& c = ev->cfg;
+  if (c.kind < SAC_ENV_CONSTANT_REWARD || c.kind > SAC_ENV_POINT_MASS)
+    return fail(SAC_E_INVALID, "unknown environment kind " + std::to_string(c.kind));
+  if (c.num_envs < 1) return fail(SAC_E_INVALID, "num_envs >= 1");
+  if (c.max_steps < 1) return fail(SAC_E_INVALID, "max_steps >= 1");
+  if (c.kind == SAC_ENV_RANDOM_OBS ? (c.obs_dim < 1 || c.obs_dim > 4 * 65536) : c.obs_dim != 1)
+    return fail(SAC_E_INVALID, "obs_dim must be 1 (SAC_ENV_RANDOM_OBS: 1..262144)");
+  if (!ev->obs || !ev->step || !ev->ep_length || !ev->pos || !ev->ep_return)
+    return fail(SAC_E_INVALID, "null environment state");
+  if (need_ring ? (!ev->episodes || ev->ring_steps < 1) : (ev->episodes && ev->ring_steps < 1))
+    return fail(SAC_E_INVALID, "episode ring needs episodes != NULL and ring_steps >= 1");
   return SAC_OK;
 }
 
@@ -1544,6 +1564,83 @@ int sac_policy_act(sac_engine* e, const float* obs, int32_t n, const float* eps,
   else
     sac_policy_act_kernel<float><<<blocks, SAC_THREADS, e->lds_bytes, s>>>(e->d, obs, n, eps, action, log_pi);
   HIPCHK(hipGetLastError());
+  return SAC_OK;
+}
+
+int sac_envs_reset(const sac_envs* envs, uint64_t seed, void* stream) {
+  int rc = check_envs(envs, false);
+  if (rc) return rc;
+  const int n = envs->cfg.num_envs;
+  sac_envs_reset_kernel<<<(n + 255) / 256, 256, 0, (hipStream_t)stream>>>(*envs, seed);
+  HIPCHK(hipGetLastError());
+  return SAC_OK;
+}
+
+int sac_envs_step(const sac_envs* envs, const float* actions, uint64_t t, float* obs, float* final_obs, float* reward,
+                  uint8_t* terminated, uint8_t* truncated, void* stream) {
+  int rc = check_envs(envs, false);
+  if (rc) return rc;
+  if (!actions || !obs || !final_obs || !reward || !terminated || !truncated)
+    return fail(SAC_E_INVALID, "bad envs_step arguments: null actions or outputs");
+  const int n = envs->cfg.num_envs;
+  sac_envs_step_kernel<<<(n + 255) / 256, 256, 0, (hipStream_t)stream>>>(*envs, actions, t, obs, final_obs, reward,
+                                                                        terminated, truncated);
+  HIPCHK(hipGetLastError());
+  return SAC_OK;
+}
+
+int sac_rollout_step(sac_engine* e, const sac_envs* envs, const sac_replay* rb, int64_t size_host, int64_t pos_host,
+                     uint64_t t, int32_t deterministic, int32_t store, void* stream) {
+  int rc = check_envs(envs, true);
+  if (rc) return rc;
+  if (!rb || !rb->obs || !rb->act || !rb->rew || !rb->next_obs || !rb->done || !rb->state)
+    return fail(SAC_E_INVALID, "null replay buffer");
+  const int64_t n = envs->cfg.num_envs, cap = rb->capacity;
+  if (cap < 1 || n > cap)
+    return fail(SAC_E_INVALID, "num_envs (" + std::to_string(n) + ") exceeds the replay capacity (" +
+                                   std::to_string(cap) + ")");
+  if (size_host < 0 || size_host > cap || pos_host < 0 || pos_host >= cap)
+    return fail(SAC_E_INVALID, "replay (size, pos) out of range");
+  if (rb->obs_dim != envs->cfg.obs_dim || rb->act_dim != SAC_ENV_ACT_DIM)
+    return fail(SAC_E_INVALID, "replay dims do not match the environments (act_dim 1)");
+  if (!e) return fail(SAC_E_INVALID, "null engine");
+  if (e->cfg.obs_dim != envs->cfg.obs_dim || e->cfg.act_dim != SAC_ENV_ACT_DIM)
+    return fail(SAC_E_INVALID, "engine dims do not match the environments (act_dim 1)");
+  const int64_t new_size = std::min(cap, size_host + n);
+  const int64_t new_pos = (pos_host + n) % cap;
+  const int blocks = (int)((n + SAC_ROWS - 1) / SAC_ROWS);
+  hipStream_t s = (hipStream_t)stream;
+  if (e->cfg.precision == SAC_PREC_BF16)
+    sac_rollout_step_kernel<bf16><<<blocks, SAC_THREADS, e->lds_bytes, s>>>(e->d, *envs, *rb, pos_host, new_size, new_pos,
+                                                                           t, deterministic ? 1 : 0, store ? 1 : 0);
+  else
+    sac_rollout_step_kernel<float><<<blocks, SAC_THREADS, e->lds_bytes, s>>>(e->d, *envs, *rb, pos_host, new_size, new_pos,
+                                                                            t, deterministic ? 1 : 0, store ? 1 : 0);
+  HIPCHK(hipGetLastError());
+  return SAC_OK;
+}
+
+int sac_debug_rollout_eps_host(uint64_t seed, uint64_t t, int32_t n, int32_t act_dim, float* out) {
+  if (!out || n < 1 || act_dim < 1) return fail(SAC_E_INVALID, "need n >= 1, act_dim >= 1, out != NULL");
+  for (int i = 0; i < n; ++i)
+    for (int p = 0; 2 * p < act_dim; ++p) {
+      float n0, n1;
+      philox_normal2(seed, t, (uint32_t)i, ENV_WHICH_NOISE, (uint32_t)p, n0, n1);
+      out[(size_t)i * act_dim + 2 * p] = n0;
+      if (2 * p + 1 < act_dim) out[(size_t)i * act_dim + 2 * p + 1] = n1;
+    }
+  return SAC_OK;
+}
+
+int sac_debug_env_obs_host(uint64_t seed, uint64_t t, int32_t which, int32_t n, int32_t obs_dim, float* out) {
+  if (!out || n < 1 || obs_dim < 1 || obs_dim > 4 * 65536 || which < 0 || which > 0xFFFF)
+    return fail(SAC_E_INVALID, "need n >= 1, 1 <= obs_dim <= 262144, 0 <= which < 65536, out != NULL");
+  for (int i = 0; i < n; ++i)
+    for (int b = 0; 4 * b < obs_dim; ++b) {
+      float u[4];
+      philox_uniform4(seed, t, (uint32_t)i, (uint32_t)which, (uint32_t)b, u);
+      for (int k = 0; k < 4 && 4 * b + k < obs_dim; ++k) out[(size_t)i * obs_dim + 4 * b + k] = env_uniform_obs(u[k]);
+    }
   return SAC_OK;
 }
 

@@ -1,0 +1,248 @@
+// sac_envs.h — the probe environments of sac/envs.py on the device, and the
+// fused rollout step (act -> step -> store in one launch).
+//
+//   * env_step: ONE statement of the four probes' dynamics, with the semantics
+//     sac.vector_env.SyncVectorEnv gives the host classes (same-step autoreset;
+//     the transition is (obs, action, reward, final_obs, terminated | truncated)).
+//     Whatever sac/envs.py keeps as a Python float is a double here, so the
+//     fp32-rounded observations and rewards are the host's bit for bit;
+//   * sac_envs_step_kernel: N environments stepped with the caller's actions;
+//   * sac_rollout_step_kernel<T>: sibling of sac_policy_act_kernel<T> (same
+//     workgroup shape, LDS layout and mlp_forward call); the thread that owns
+//     environment row i samples its action, steps the environment and writes
+//     the transition into the replay ring.
+//
+// State is caller-owned global memory (include/sac_engine.h sac_envs).  Every
+// environment row is read and written by exactly one thread of one launch, and
+// every episode-ring cell by its own row: no atomics, no hand-offs, nothing
+// depends on the order workgroups run in.
+#pragma once
+#include "../../include/sac_engine.h"
+#include "sac_phases.h"
+
+// Action components the probes take (envs.py: every action_space has shape (1,)).
+#define SAC_ENV_ACT_DIM 1
+// Philox `which` values of the rollout (0 / 1 are the training draws)
+#define ENV_WHICH_NOISE 2u  // action noise of a rollout step, key = engine seed
+#define ENV_WHICH_STEP 3u   // observation an environment steps to at t, key = env seed
+#define ENV_WHICH_RESET 4u  // its reset observation at t
+
+// Four uniforms in [0, 1) for (t, row, which, block): counter (t, row,
+// which << 16 | block), key = seed; the top 24 bits of each output word.
+// Host-callable so the C ABI exports the same inline code (sac_debug_env_obs_host).
+__host__ __device__ inline void philox_uniform4(uint64_t seed, uint64_t t, uint32_t row, uint32_t which,
+                                                uint32_t block, float u[4]) {
+  uint32_t c[4] = {(uint32_t)t, (uint32_t)(t >> 32), row, (which << 16) | block};
+  philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+#pragma unroll
+  for (int k = 0; k < 4; ++k) u[k] = (float)(c[k] >> 8) * 5.9604644775390625e-8f;
+}
+// 2u - 1 is exact in fp32 (u is a multiple of 2^-24 below 1): obs in [-1, 1)
+__host__ __device__ inline float env_uniform_obs(float u) { return 2.0f * u - 1.0f; }
+
+// np.clip on float32: min(max(x, lo), hi) with NaN passed through
+__host__ __device__ inline float clip_f32(float x, float lo, float hi) { return x < lo ? lo : (x > hi ? hi : x); }
+
+struct EnvOut {
+  double reward;  // as the host class returns it (probe 1's fp32 reward widened, as float(r) does)
+  bool terminated, truncated;
+};
+
+// One step of environment row i at vector step t with the action's first
+// component.  Writes the observation stepped to into final_obs[obs_dim] (unless
+// NULL), the environment's new current observation (the reset observation where
+// the episode ended) into ev.obs, and its step counter / position.
+__device__ __forceinline__ EnvOut env_step(const sac_envs& ev, int i, uint64_t t, float action, float* final_obs) {
+  const sac_env_config& c = ev.cfg;
+  const int O = c.obs_dim;
+  const int step = ev.step[i] + 1;
+  float* cur = ev.obs + (size_t)i * O;
+  EnvOut o;
+  o.terminated = o.truncated = false;
+  float fo = 0.f, ro = 0.f;  // observation stepped to / after a reset (the probes with one observation)
+  double pos = 0.0;
+  switch (c.kind) {
+    case SAC_ENV_CONSTANT_REWARD:
+      o.reward = c.reward;
+      o.terminated = step >= c.max_steps;
+      break;
+    case SAC_ENV_QUADRATIC_ACTION: {
+      // np.float32 - Python float stays fp32 (the float is a weak scalar).  d * d is the correctly
+      // rounded square; numpy's scalar ** 2 is powf and misses it by an ulp for ~0.07 % of arguments.
+      const float a = clip_f32(action, (float)c.action_low, (float)c.action_high);
+      const float d = a - (float)c.target;
+      o.reward = (double)(-(d * d));
+      o.terminated = step >= c.max_steps;
+      break;
+    }
+    case SAC_ENV_RANDOM_OBS:
+      o.reward = fabs((double)action) <= c.threshold ? 1.0 : -1.0;
+      o.terminated = step >= c.max_steps;
+      break;
+    default: {  // SAC_ENV_POINT_MASS
+      const double a = (double)clip_f32(action, (float)c.action_low, (float)c.action_high);
+      pos = ev.pos[i] + a * c.dt;
+      const bool reached = fabs(pos - c.goal_pos) <= c.goal_tolerance;
+      o.reward = reached ? c.step_penalty + c.goal_reward : c.step_penalty;
+      o.terminated = reached;
+      o.truncated = step >= c.max_steps;
+      fo = (float)pos;
+      ro = (float)c.start_pos;
+      break;
+    }
+  }
+  const bool done = o.terminated || o.truncated;
+  if (c.kind == SAC_ENV_RANDOM_OBS) {
+    for (int b = 0; 4 * b < O; ++b) {
+      float u[4], v[4] = {0.f, 0.f, 0.f, 0.f};
+      philox_uniform4(c.seed, t, (uint32_t)i, ENV_WHICH_STEP, (uint32_t)b, u);
+      if (done) philox_uniform4(c.seed, t, (uint32_t)i, ENV_WHICH_RESET, (uint32_t)b, v);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int j = 4 * b + k;
+        if (j >= O) break;
+        const float f = env_uniform_obs(u[k]);
+        if (final_obs) final_obs[j] = f;
+        cur[j] = done ? env_uniform_obs(v[k]) : f;
+      }
+    }
+  } else {
+    if (final_obs) final_obs[0] = fo;
+    cur[0] = done ? ro : fo;
+  }
+  ev.step[i] = done ? 0 : step;
+  if (c.kind == SAC_ENV_POINT_MASS) ev.pos[i] = done ? c.start_pos : pos;
+  return o;
+}
+
+// The loop's episode bookkeeping (agent.py run_vectorized_training_loop:
+// ep_ret += rewards in float64, ep_len += 1, both zeroed where the episode
+// ended) and this step's cell of the episode ring.
+__device__ __forceinline__ void env_account(const sac_envs& ev, int i, uint64_t t, const EnvOut& o) {
+  const bool done = o.terminated || o.truncated;
+  const double ret = ev.ep_return[i] + o.reward;
+  const int len = ev.ep_length[i] + 1;
+  if (ev.episodes) {
+    sac_env_episode* cell = ev.episodes + (size_t)(t % (uint64_t)ev.ring_steps) * ev.cfg.num_envs + i;
+    cell->ret = ret;
+    cell->length = len;
+    cell->ended = done ? 1 : 0;
+  }
+  ev.ep_return[i] = done ? 0.0 : ret;
+  ev.ep_length[i] = done ? 0 : len;
+}
+
+__global__ void sac_envs_reset_kernel(sac_envs ev, uint64_t seed) {
+  const sac_env_config& c = ev.cfg;
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= c.num_envs) return;
+  const int O = c.obs_dim;
+  float* cur = ev.obs + (size_t)i * O;
+  if (c.kind == SAC_ENV_RANDOM_OBS) {
+    for (int b = 0; 4 * b < O; ++b) {
+      float u[4];
+      philox_uniform4(seed, 0, (uint32_t)i, ENV_WHICH_RESET, (uint32_t)b, u);
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (4 * b + k < O) cur[4 * b + k] = env_uniform_obs(u[k]);
+    }
+  } else {
+    cur[0] = c.kind == SAC_ENV_POINT_MASS ? (float)c.start_pos : 0.f;
+  }
+  ev.step[i] = 0;
+  ev.ep_length[i] = 0;
+  ev.pos[i] = c.kind == SAC_ENV_POINT_MASS ? c.start_pos : 0.0;
+  ev.ep_return[i] = 0.0;
+}
+
+__global__ void sac_envs_step_kernel(sac_envs ev, const float* __restrict__ actions, uint64_t t,
+                                     float* __restrict__ obs, float* __restrict__ final_obs,
+                                     float* __restrict__ reward, uint8_t* __restrict__ terminated,
+                                     uint8_t* __restrict__ truncated) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= ev.cfg.num_envs) return;
+  const int O = ev.cfg.obs_dim;
+  const EnvOut o = env_step(ev, i, t, actions[(size_t)i * SAC_ENV_ACT_DIM], final_obs + (size_t)i * O);
+  env_account(ev, i, t, o);
+  for (int k = 0; k < O; ++k) obs[(size_t)i * O + k] = ev.obs[(size_t)i * O + k];
+  reward[i] = (float)o.reward;
+  terminated[i] = o.terminated ? 1 : 0;
+  truncated[i] = o.truncated ? 1 : 0;
+}
+
+// One workgroup per SAC_ROWS environments.  new_size / new_pos: the replay's
+// (size, write slot) after this step, computed by the host as sac_replay_push
+// does.
+template <typename T>
+__global__ void __launch_bounds__(SAC_THREADS) sac_rollout_step_kernel(const EngineDev* __restrict__ Ep, sac_envs ev,
+                                                                      sac_replay rb, int64_t pos, int64_t new_size,
+                                                                      int64_t new_pos, uint64_t t, int deterministic,
+                                                                      int store) {
+  PREFETCH_ARG(Ep);
+  const AS_C EngineDev& E = *(const AS_C EngineDev*)Ep;
+  extern __shared__ float lds_raw[];
+  lf* lds = (lf*)lds_raw;
+  constexpr int R = SAC_ROWS;
+  const int tid = threadIdx.x, O = E.O, A = E.A, ld = E.ld, ldo = E.ldo;
+  const int n = ev.cfg.num_envs;
+  const int r0 = blockIdx.x * R;
+  const int nvalid = min(R, n - r0);
+  const AS_G float* obs = GPC(float, ev.obs);
+  lf* Xb = lds + E.o_X;
+  lf* Yb = lds + E.o_Y;
+  lf* outB = lds + E.o_out;
+  lf* outP = lds + E.o_outp;
+  const AS_C NetDev& pi = E.net[NET_PI];
+  const int Kp0 = pi.l[0].Kp;
+  for (int i = tid; i < R * Kp0; i += SAC_THREADS) {
+    const int r = i / Kp0, k = i % Kp0;
+    Xb[r * ld + k] = (k < O && r < nvalid) ? obs[(size_t)(r0 + r) * O + k] : 0.f;
+  }
+  __syncthreads();
+  Pf<T> pf;
+  pf.tag = nullptr;
+  mlp_forward<T, R>(pi, Xb, Yb, ld, outP, outB, ldo, E.o_P1, E.ldp1, lds, false, false, 0, 0, 0, pf, gw_none());
+  // every read of ev.obs above is behind mlp_forward's barriers: row owners may now overwrite their rows
+  if (tid < nvalid) {
+    const int i = r0 + tid;
+    const lf* o = outB + tid * ldo;
+    const float lo = E.ls_min, hi = E.ls_max, scale = E.scale;
+    const RowStrides rs = row_strides(rb.row_stride, O, A);
+    const int64_t slot = (pos + i) % rb.capacity;
+    if (store)
+      for (int k = 0; k < O; ++k) rb.obs[slot * rs.obs + k] = ev.obs[(size_t)i * O + k];
+    float a0 = 0.f;
+    for (int p = 0; 2 * p < A; ++p) {
+      float e2[2] = {0.f, 0.f};
+      if (!deterministic) philox_normal2(E.seed, t, (uint32_t)i, ENV_WHICH_NOISE, (uint32_t)p, e2[0], e2[1]);
+#pragma unroll
+      for (int q = 0; q < 2; ++q) {
+        const int j = 2 * p + q;
+        if (j >= A) break;
+        float a;
+        if (deterministic) {
+          a = tanhf(o[j]) * scale;
+        } else {  // the head arithmetic of sac_policy_act_kernel
+          const float mu = o[j], lsr = o[A + j], e = e2[q];
+          const float ls = lsr < lo ? lo : (lsr > hi ? hi : lsr);
+          const float sd = expf(ls);
+          const float z = mu + e * sd;
+          a = tanhf(z) * scale;
+        }
+        if (j == 0) a0 = a;
+        if (store) rb.act[slot * rs.act + j] = a;
+      }
+    }
+    const EnvOut eo = env_step(ev, i, t, a0, store ? rb.next_obs + slot * rs.obs : nullptr);
+    env_account(ev, i, t, eo);
+    if (store) {
+      rb.rew[slot * rs.one] = (float)eo.reward;
+      rb.done[slot * rs.one] = (eo.terminated || eo.truncated) ? 1.f : 0.f;
+    }
+  }
+  if (store && blockIdx.x == 0 && tid == 0) {  // as replay_push_kernel
+    rb.state[0] = new_size;
+    rb.state[1] = new_pos;
+    rb.state[2] += 1;  // push generation: a batch phase C staged before this step is stale
+  }
+}

@@ -15,10 +15,18 @@
 //   train_step           SAC.training_step            (sac/agent.py:302-327)
 //   train_graph          a loop of training_step      (sac/agent.py:361-364), hipGraph-replayed
 //   policy_act           SAC.select_action            (sac/agent.py:149-156; models.py:79-92)
+//   envs_reset           SyncVectorEnv.reset          (sac/vector_env.py:39-46 over sac/envs.py)
+//   envs_step            SyncVectorEnv.step           (sac/vector_env.py:55-71 over sac/envs.py)
+//   rollout_step         select_actions + env.step + store_transitions of one vector step, ONE kernel
 //
 // Replay storage is ONE fp32 tensor per buffer; `layout` = [capacity, obs_dim,
 // act_dim, row_stride, off_obs, off_act, off_rew, off_next_obs, off_done]
 // (offsets in floats from storage.data_ptr(); row_stride 0 = struct-of-arrays).
+// Environment state (envs_*, rollout_step): `obs` [N][O] fp32, `counters`
+// int32 [2][N] (step in episode, episode length), `dstate` float64 [2][N]
+// (position, episode return), `ring` float64 [S][N][2] (the sac_env_episode
+// cells: return, then length and ended as two int32); `icfg` = [kind, num_envs,
+// obs_dim, max_steps], `params` = the 11 doubles of sac_env_config in order.
 // Engine state: `engine` is the sac_engine* handle (int64) from
 // sac_engine_create; `state` lists the 16 caller-owned tensors the step reads
 // and writes (sac_engine_buffers order) so the op's mutation is declared.
@@ -51,6 +59,9 @@ struct EngineApi {
   decltype(&sac_engine_train) engine_train = nullptr;
   decltype(&sac_engine_train_graph) engine_train_graph = nullptr;
   decltype(&sac_policy_act) policy_act = nullptr;
+  decltype(&sac_envs_reset) envs_reset = nullptr;
+  decltype(&sac_envs_step) envs_step = nullptr;
+  decltype(&sac_rollout_step) rollout_step = nullptr;
 };
 EngineApi g_api;
 std::string g_bound_path;
@@ -75,6 +86,9 @@ void bind_engine_library(c10::string_view path_) {
   resolve(h, "sac_engine_train", a.engine_train);
   resolve(h, "sac_engine_train_graph", a.engine_train_graph);
   resolve(h, "sac_policy_act", a.policy_act);
+  resolve(h, "sac_envs_reset", a.envs_reset);
+  resolve(h, "sac_envs_step", a.envs_step);
+  resolve(h, "sac_rollout_step", a.rollout_step);
   g_api = a;
   g_bound_path = path;
 }
@@ -269,6 +283,99 @@ std::tuple<at::Tensor, at::Tensor> policy_act(int64_t engine, const at::Tensor& 
   return {act, lp};
 }
 
+// ---------------------------------------------------------------- environments
+sac_envs make_envs(const at::Tensor& obs, const at::Tensor& counters, const at::Tensor& dstate,
+                   const std::optional<at::Tensor>& ring, at::IntArrayRef icfg, at::ArrayRef<double> params,
+                   int64_t seed) {
+  TORCH_CHECK(icfg.size() == 4, "icfg must be [kind, num_envs, obs_dim, max_steps]");
+  TORCH_CHECK(params.size() == 11, "params must hold the 11 doubles of sac_env_config");
+  const int64_t N = icfg[1], O = icfg[2];
+  TORCH_CHECK(N >= 1 && N <= INT32_MAX && O >= 1 && O <= INT32_MAX, "num_envs and obs_dim must be >= 1");
+  check_f32(obs, "env obs");
+  TORCH_CHECK(obs.dim() == 2 && obs.size(0) == N && obs.size(1) == O, "env obs must be [num_envs][obs_dim]");
+  TORCH_CHECK(counters.is_cuda() && counters.scalar_type() == at::kInt && counters.is_contiguous() &&
+                  counters.dim() == 2 && counters.size(0) == 2 && counters.size(1) == N,
+              "env counters must be a contiguous int32 [2][num_envs] device tensor");
+  TORCH_CHECK(dstate.is_cuda() && dstate.scalar_type() == at::kDouble && dstate.is_contiguous() && dstate.dim() == 2 &&
+                  dstate.size(0) == 2 && dstate.size(1) == N,
+              "env dstate must be a contiguous float64 [2][num_envs] device tensor");
+  TORCH_CHECK(counters.device() == obs.device() && dstate.device() == obs.device(), "env state on different devices");
+  sac_envs ev{};
+  ev.cfg.kind = static_cast<int32_t>(icfg[0]);
+  ev.cfg.num_envs = static_cast<int32_t>(N);
+  ev.cfg.obs_dim = static_cast<int32_t>(O);
+  ev.cfg.max_steps = static_cast<int32_t>(std::min<int64_t>(std::max<int64_t>(icfg[3], INT32_MIN), INT32_MAX));
+  ev.cfg.reward = params[0];
+  ev.cfg.target = params[1];
+  ev.cfg.action_low = params[2];
+  ev.cfg.action_high = params[3];
+  ev.cfg.threshold = params[4];
+  ev.cfg.start_pos = params[5];
+  ev.cfg.goal_pos = params[6];
+  ev.cfg.dt = params[7];
+  ev.cfg.step_penalty = params[8];
+  ev.cfg.goal_reward = params[9];
+  ev.cfg.goal_tolerance = params[10];
+  ev.cfg.seed = static_cast<uint64_t>(seed);
+  ev.obs = obs.data_ptr<float>();
+  ev.step = counters.data_ptr<int32_t>();
+  ev.ep_length = ev.step + N;
+  ev.pos = dstate.data_ptr<double>();
+  ev.ep_return = ev.pos + N;
+  if (ring && ring->defined()) {
+    const auto& r = *ring;
+    TORCH_CHECK(r.is_cuda() && r.scalar_type() == at::kDouble && r.is_contiguous() && r.dim() == 3 && r.size(0) >= 1 &&
+                    r.size(1) == N && r.size(2) == 2 && r.device() == obs.device(),
+                "episode ring must be a contiguous float64 [ring_steps][num_envs][2] device tensor");
+    static_assert(sizeof(sac_env_episode) == 2 * sizeof(double), "ring cell layout");
+    ev.episodes = reinterpret_cast<sac_env_episode*>(r.data_ptr<double>());
+    ev.ring_steps = r.size(0);
+  }
+  return ev;
+}
+
+void envs_reset(at::Tensor& obs, at::Tensor& counters, at::Tensor& dstate, at::IntArrayRef icfg,
+                at::ArrayRef<double> params, int64_t seed) {
+  sac_envs ev = make_envs(obs, counters, dstate, std::nullopt, icfg, params, seed);
+  Guard g(obs.device());
+  check_rc(api().envs_reset(&ev, static_cast<uint64_t>(seed), stream_of(obs)));
+}
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor> envs_step(
+    at::Tensor& obs, at::Tensor& counters, at::Tensor& dstate, const std::optional<at::Tensor>& ring,
+    at::IntArrayRef icfg, at::ArrayRef<double> params, int64_t seed, const at::Tensor& actions, int64_t t) {
+  sac_envs ev = make_envs(obs, counters, dstate, ring, icfg, params, seed);
+  check_f32(actions, "actions");
+  TORCH_CHECK(actions.dim() == 2 && actions.size(0) == obs.size(0) && actions.size(1) == 1 &&
+                  actions.device() == obs.device(),
+              "actions must be [num_envs][1] on the environments' device");
+  TORCH_CHECK(t >= 1, "vector step t must be >= 1 (0 is the reset)");
+  const int64_t N = obs.size(0), O = obs.size(1);
+  auto o = obs.options();
+  at::Tensor obs_out = at::empty({N, O}, o), final_obs = at::empty({N, O}, o), reward = at::empty({N}, o);
+  at::Tensor term = at::empty({N}, o.dtype(at::kBool)), trunc = at::empty({N}, o.dtype(at::kBool));
+  Guard g(obs.device());
+  check_rc(api().envs_step(&ev, actions.data_ptr<float>(), static_cast<uint64_t>(t), obs_out.data_ptr<float>(),
+                           final_obs.data_ptr<float>(), reward.data_ptr<float>(),
+                           reinterpret_cast<uint8_t*>(term.data_ptr<bool>()),
+                           reinterpret_cast<uint8_t*>(trunc.data_ptr<bool>()), stream_of(obs)));
+  return {obs_out, final_obs, reward, term, trunc};
+}
+
+void rollout_step(int64_t engine, at::Tensor& obs, at::Tensor& counters, at::Tensor& dstate, at::Tensor& ring,
+                  at::IntArrayRef icfg, at::ArrayRef<double> params, int64_t seed, at::Tensor& storage,
+                  at::Tensor& rstate, at::IntArrayRef layout, int64_t size, int64_t pos, int64_t t, bool deterministic,
+                  bool store) {
+  TORCH_CHECK(engine != 0, "null engine handle");
+  sac_envs ev = make_envs(obs, counters, dstate, ring, icfg, params, seed);
+  Replay r = make_replay(storage, rstate, layout);
+  TORCH_CHECK(storage.device() == obs.device(), "replay and environments on different devices");
+  TORCH_CHECK(t >= 1, "vector step t must be >= 1 (0 is the reset)");
+  Guard g(obs.device());
+  check_rc(api().rollout_step(reinterpret_cast<sac_engine*>(engine), &ev, &r.d, size, pos, static_cast<uint64_t>(t),
+                              deterministic ? 1 : 0, store ? 1 : 0, stream_of(obs)));
+}
+
 // ---------------------------------------------------------------- meta (shapes only)
 void replay_push_meta(at::Tensor&, at::Tensor&, at::IntArrayRef, const at::Tensor&, int64_t, int64_t) {}
 
@@ -302,6 +409,21 @@ std::tuple<at::Tensor, at::Tensor> policy_act_meta(int64_t, const at::Tensor& ob
   return {at::empty({n, act_dim}, obs.options()), at::empty({lp ? n : 0}, obs.options())};
 }
 
+void envs_reset_meta(at::Tensor&, at::Tensor&, at::Tensor&, at::IntArrayRef, at::ArrayRef<double>, int64_t) {}
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor> envs_step_meta(
+    at::Tensor& obs, at::Tensor&, at::Tensor&, const std::optional<at::Tensor>&, at::IntArrayRef, at::ArrayRef<double>,
+    int64_t, const at::Tensor&, int64_t) {
+  const int64_t N = obs.size(0), O = obs.size(1);
+  auto o = obs.options();
+  return {at::empty({N, O}, o), at::empty({N, O}, o), at::empty({N}, o), at::empty({N}, o.dtype(at::kBool)),
+          at::empty({N}, o.dtype(at::kBool))};
+}
+
+void rollout_step_meta(int64_t, at::Tensor&, at::Tensor&, at::Tensor&, at::Tensor&, at::IntArrayRef,
+                       at::ArrayRef<double>, int64_t, at::Tensor&, at::Tensor&, at::IntArrayRef, int64_t, int64_t,
+                       int64_t, bool, bool) {}
+
 }  // namespace
 
 TORCH_LIBRARY(sac_hip, m) {
@@ -317,6 +439,13 @@ TORCH_LIBRARY(sac_hip, m) {
   m.def("train_graph(int engine, Tensor(a!)[] state, Tensor storage, Tensor replay_state, int[] layout, "
         "int n_steps, int chunk) -> ()");
   m.def("policy_act(int engine, Tensor obs, Tensor? eps, int act_dim, bool want_log_pi=False) -> (Tensor, Tensor)");
+  m.def("envs_reset(Tensor(a!) obs, Tensor(b!) counters, Tensor(c!) dstate, int[] icfg, float[] params, int seed) "
+        "-> ()");
+  m.def("envs_step(Tensor(a!) obs, Tensor(b!) counters, Tensor(c!) dstate, Tensor(d!)? ring, int[] icfg, "
+        "float[] params, int seed, Tensor actions, int t) -> (Tensor, Tensor, Tensor, Tensor, Tensor)");
+  m.def("rollout_step(int engine, Tensor(a!) obs, Tensor(b!) counters, Tensor(c!) dstate, Tensor(d!) ring, "
+        "int[] icfg, float[] params, int seed, Tensor(e!) storage, Tensor(f!) replay_state, int[] layout, "
+        "int size, int pos, int t, bool deterministic=False, bool store=True) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(sac_hip, CUDA, m) {
@@ -327,6 +456,9 @@ TORCH_LIBRARY_IMPL(sac_hip, CUDA, m) {
   m.impl("train_step", &train_step);
   m.impl("train_graph", &train_graph);
   m.impl("policy_act", &policy_act);
+  m.impl("envs_reset", &envs_reset);
+  m.impl("envs_step", &envs_step);
+  m.impl("rollout_step", &rollout_step);
 }
 
 TORCH_LIBRARY_IMPL(sac_hip, Meta, m) {
@@ -337,4 +469,7 @@ TORCH_LIBRARY_IMPL(sac_hip, Meta, m) {
   m.impl("train_step", &train_step_meta);
   m.impl("train_graph", &train_graph_meta);
   m.impl("policy_act", &policy_act_meta);
+  m.impl("envs_reset", &envs_reset_meta);
+  m.impl("envs_step", &envs_step_meta);
+  m.impl("rollout_step", &rollout_step_meta);
 }

@@ -75,6 +75,29 @@ class ReplayDesc(ctypes.Structure):
                 ("row_stride", ctypes.c_int64)]
 
 
+# sac_env_kind (include/sac_engine.h) by the names sac/train_replicas.py uses
+ENV_KINDS = {"constant_reward": 0, "quadratic_action": 1, "random_obs_binary": 2, "point_mass": 3}
+# the double parameters of sac_env_config, in struct order
+ENV_PARAMS = ("reward", "target", "action_low", "action_high", "threshold", "start_pos", "goal_pos", "dt",
+              "step_penalty", "goal_reward", "goal_tolerance")
+
+
+class EnvConfig(ctypes.Structure):
+    _fields_ = [("kind", ctypes.c_int32), ("num_envs", ctypes.c_int32), ("obs_dim", ctypes.c_int32),
+                ("max_steps", ctypes.c_int32)] + [(n, ctypes.c_double) for n in ENV_PARAMS] + [
+        ("seed", ctypes.c_uint64)]
+
+
+class EnvEpisode(ctypes.Structure):
+    _fields_ = [("ret", ctypes.c_double), ("length", ctypes.c_int32), ("ended", ctypes.c_int32)]
+
+
+class EnvsDesc(ctypes.Structure):
+    _fields_ = [("cfg", EnvConfig), ("obs", ctypes.c_void_p), ("step", ctypes.c_void_p),
+                ("ep_length", ctypes.c_void_p), ("pos", ctypes.c_void_p), ("ep_return", ctypes.c_void_p),
+                ("episodes", ctypes.c_void_p), ("ring_steps", ctypes.c_int64)]
+
+
 # name -> (restype, argtypes): every symbol include/sac_engine.h declares
 SIGNATURES = {
     "sac_last_error": (ctypes.c_char_p, []),
@@ -105,6 +128,12 @@ SIGNATURES = {
     "sac_phase_kernel_name": (ctypes.c_char_p, [ctypes.c_int32]),
     "sac_engine_check": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "sac_engine_set_alpha_update": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]),
+    "sac_envs_reset": (ctypes.c_int, [ctypes.POINTER(EnvsDesc), ctypes.c_uint64, ctypes.c_void_p]),
+    "sac_envs_step": (ctypes.c_int, [ctypes.POINTER(EnvsDesc), ctypes.c_void_p, ctypes.c_uint64]
+                      + [ctypes.c_void_p] * 6),
+    "sac_rollout_step": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(EnvsDesc), ctypes.POINTER(ReplayDesc),
+                                        ctypes.c_int64, ctypes.c_int64, ctypes.c_uint64, ctypes.c_int32,
+                                        ctypes.c_int32, ctypes.c_void_p]),
 }
 
 _lib: Optional[ctypes.CDLL] = None
@@ -143,7 +172,8 @@ def ops_library_path() -> str:
 def ops():
     """``torch.ops.sac_hip``: the PyTorch custom ops over the C ABI
     (csrc/sac_torch_ops.cpp: replay_push, replay_gather, replay_sample,
-    replay_sample_gather, train_step, train_graph, policy_act).  The op library
+    replay_sample_gather, train_step, train_graph, policy_act, envs_reset,
+    envs_step, rollout_step).  The op library
     dlopens the engine library ctypes loaded (bind_engine_library: the same file,
     so the same instance owns the engine handles).  Raises EngineUnavailable
     when it is not built."""

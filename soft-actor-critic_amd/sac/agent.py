@@ -688,6 +688,123 @@ class SAC:
             active_logger.log_hparams(self.config, metrics)
         return metrics
 
+    def _device_env(self, vec_env: Any, what: str):
+        from .device_envs import DeviceVectorEnv
+
+        env = vec_env if vec_env is not None else self.env
+        if not isinstance(env, DeviceVectorEnv):
+            raise TypeError(f"{what} needs a sac.device_envs.DeviceVectorEnv (a probe environment of sac.envs "
+                            "resident on the device); other environments run through run_vectorized_training_loop")
+        return env
+
+    def run_device_training_loop(self, total_env_steps: int, vec_env: Any = None, logger=None,
+                                 print_rewards: bool = False, seed: Optional[int] = None,
+                                 callback: Optional[Callable[[Dict[str, float]], None]] = None,
+                                 drain_every: int = 64) -> Dict[str, float]:
+        """``run_vectorized_training_loop`` over a ``DeviceVectorEnv``: the envs
+        live on the device and act -> step -> store is ONE launch
+        (``SacEngine.rollout_step``), so a vector step is that launch plus the
+        gradient steps that fell due -- gated and counted exactly as in the
+        vectorised loop (``due_updates_gated``, ``can_update``, ``_run_updates``,
+        the loss log, the callback) -- with no host<->device copy, no ``.cpu()``,
+        no ``.item()`` and no synchronisation per step.
+
+        Episode returns and lengths are accumulated on the device and written
+        to the envs' episode ring; every ``drain_every`` vector steps the new
+        cells are copied to pinned memory behind the launches and consumed once
+        the copy has landed (``sac.device_envs.EpisodeDrain``, the ``QValueLog``
+        pattern), and after the last step the rest is consumed blocking.  So
+        the returned metrics and the logged episodes are exact and in the
+        order the host loop sees them, (vector step, env row); but the
+        ``episodes`` and ``avg_return`` a ``callback`` sees inside the loop may
+        lag the device by up to ``drain_every`` vector steps (plus the copy in
+        flight).  ``drain_every`` is capped at the ring's length.
+
+        Actions are sampled with the engine's device RNG (Philox, ``which`` =
+        2), not torch's generator, so a seeded run differs from the vectorised
+        loop's in its noise draws, not in distribution.  ``logger.log_q_values``
+        is not supported here (it evaluates the critics per env step on host
+        inputs): ValueError."""
+        from .device_envs import EpisodeDrain
+
+        env = self._device_env(vec_env, "run_device_training_loop")
+        if self.config["logger"]["log_q_values"]:
+            raise ValueError("run_device_training_loop does not support logger.log_q_values (per-env-step Q values "
+                             "need the transitions on the host); use run_vectorized_training_loop or turn it off")
+        eng = self._engine()
+        active_logger = logger or self.logger
+        tr = self.config["train"]
+        update_every = tr.get("update_frequency", 1)
+        n_grad = tr.get("gradient_steps_per_update", 1)
+        N = env.num_envs
+        env.reset(seed=seed)
+        returns_window = deque(maxlen=100)
+        st = {"episodes": 0, "best": -float("inf"), "avg": float("nan")}
+        total_steps = grad_steps = 0
+        log_episodes = active_logger is not None and self.config["logger"]["log_episode_stats"]
+        loss_log = self._loss_log(active_logger)
+
+        def on_episode(ret: float, length: int) -> None:
+            returns_window.append(ret)
+            st["avg"] = float(np.mean(returns_window))
+            st["best"] = max(st["best"], st["avg"])
+            if log_episodes:
+                active_logger.log_episode_metrics(episode_idx=st["episodes"], reward=ret, length=length)
+            if print_rewards:
+                print(f"Episode {st['episodes']}, Return: {ret:.2f}, "
+                      f"Average Return(last 100 episodes): {st['avg']:.2f}")
+            st["episodes"] += 1
+
+        drain = EpisodeDrain(env, on_episode, drain_every)
+        for _ in range((int(total_env_steps) + N - 1) // N):
+            len_before = len(self.replay_buffer)
+            eng.rollout_step(env, self.replay_buffer)
+            old = total_steps
+            total_steps += N
+            due = due_updates_gated(old, total_steps, len_before, self.replay_buffer.capacity,
+                                    tr["warming_steps"], update_every, n_grad)
+            if self.can_update() and due:
+                self._run_updates(due)
+                grad_steps += due
+                if loss_log is not None:
+                    loss_log.after_updates(total_steps)
+            drain.after_step()
+            if callback is not None:
+                callback({"env_steps": total_steps, "gradient_steps": grad_steps, "episodes": st["episodes"],
+                          "avg_return": st["avg"]})
+        eng.check()  # a timed-out hand-off invalidates the run: raise, do not report it
+        drain.finish()
+        if loss_log is not None:
+            loss_log.finish()
+        metrics = {"total_episodes": st["episodes"], "best_avg_return": st["best"],
+                   "final_avg_return": st["avg"], "total_env_steps": total_steps, "gradient_steps": grad_steps}
+        if active_logger is not None:
+            active_logger.log_hparams(self.config, metrics)
+        return metrics
+
+    def evaluate_device(self, num_episodes: int, vec_env: Any = None) -> float:
+        """Mean return of the first ``num_episodes`` episodes the deterministic
+        policy (tanh(mu) * scale) finishes on a ``DeviceVectorEnv``, counted in
+        (vector step, env row) order.  Nothing is stored: the replay buffer and
+        its device state are untouched.  The envs are reset first; one blocking
+        read of the episode ring per ring length."""
+        from .device_envs import EpisodeDrain
+
+        env = self._device_env(vec_env, "evaluate_device")
+        if num_episodes < 1:
+            raise ValueError("num_episodes must be >= 1")
+        eng = self._engine()
+        env.reset()
+        returns: list = []
+        drain = EpisodeDrain(env, lambda ret, length: returns.append(ret), env.ring_steps)
+        # every env ends an episode at least once per max_steps vector steps
+        chunk = max(1, min(env.ring_steps, env.max_steps * ((num_episodes + env.num_envs - 1) // env.num_envs)))
+        while len(returns) < num_episodes:
+            for _ in range(chunk):
+                eng.rollout_step(env, self.replay_buffer, deterministic=True, store=False)
+            drain.finish()
+        return float(np.mean(returns[:num_episodes]))
+
     def eval_agent(self, num_episodes: int, render_mode: Optional[str] = None, tqdm_disable: bool = False,
                    print_returns: bool = False, writer=None) -> float:
         eval_env = self._get_render_environment(render_mode)

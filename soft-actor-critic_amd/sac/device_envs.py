@@ -1,0 +1,230 @@
+"""The probe environments of ``sac.envs`` resident on the device.
+
+``DeviceVectorEnv`` holds N copies of one probe environment as device state
+(``include/sac_engine.h`` ``sac_envs``) and steps them in HIP kernels with the
+semantics ``sac.vector_env.SyncVectorEnv`` gives the host classes: same-step
+autoreset, ``infos["final_obs"]`` holding the true next state of every env.
+Observations, rewards and flags are the host classes' (bit for bit; what
+``sac/envs.py`` keeps as Python floats is float64 on the device).
+
+Two ways to step:
+
+* ``step(actions)``: the gym-shaped path for a caller with its own policy.
+  Takes and returns device tensors, never copies to the host;
+* ``SacEngine.rollout_step(envs, replay)``: act -> step -> store fused into ONE
+  launch (the policy forward, the squashed-Gaussian sample, the env step and
+  the write into the replay ring), the step of ``SAC.run_device_training_loop``.
+
+The only randomness is ``RandomObsBinaryRewardEnv``'s observations: Philox
+draws keyed by the seed given to ``reset`` with counter (vector step, env row),
+so a run is reproducible whatever order the workgroups run in (the host class
+draws from numpy's generator instead: same distribution, other numbers).
+
+Episode statistics: every step writes each env's running (return, length,
+ended) into a dense ring ``[ring_steps][N]`` indexed by ``t % ring_steps``;
+``episode_cells`` queues an asynchronous copy of the cells of a range of steps
+and ``EpisodeDrain`` consumes them in ``(t, i)`` order, the order in which the
+host loop sees episodes end.
+
+There is no host fallback: without the engine ``DeviceVectorEnv(...)`` raises
+``EngineUnavailable``.
+"""
+from __future__ import annotations
+
+from typing import List, Optional, Tuple
+
+import numpy as np
+import torch
+
+from . import _engine as E
+from . import envs as host_envs
+
+# kind name -> (sac_env_kind, host class); the names of sac/train_replicas.py
+KINDS = {
+    "constant_reward": (0, host_envs.ConstantRewardEnv),
+    "quadratic_action": (1, host_envs.QuadraticActionRewardEnv),
+    "random_obs_binary": (2, host_envs.RandomObsBinaryRewardEnv),
+    "point_mass": (3, host_envs.OneDPointMassReachEnv),
+}
+_BY_CLASS = {cls.__name__: name for name, (_, cls) in KINDS.items()}
+_BY_CODE = {code: name for name, (code, _) in KINDS.items()}
+
+# sac_env_config double <- attribute of the host instance, per kind
+_PARAM_ATTRS = {
+    "constant_reward": {"reward": "constant_reward"},
+    "quadratic_action": {"target": "target"},
+    "random_obs_binary": {"threshold": "threshold"},
+    "point_mass": {"start_pos": "start_pos", "goal_pos": "goal_pos", "dt": "dt", "step_penalty": "step_penalty",
+                   "goal_reward": "goal_reward", "goal_tolerance": "goal_tolerance"},
+}
+
+
+def kind_name(kind_or_name) -> str:
+    """Canonical kind name of a name, a ``sac.envs`` class (or its name) or a sac_env_kind code."""
+    if isinstance(kind_or_name, str):
+        name = _BY_CLASS.get(kind_or_name, kind_or_name)
+    elif isinstance(kind_or_name, type):
+        name = _BY_CLASS.get(kind_or_name.__name__)
+    else:
+        name = _BY_CODE.get(int(kind_or_name))
+    if name not in KINDS:
+        raise ValueError(f"unknown probe environment {kind_or_name!r} (one of {sorted(KINDS)})")
+    return name
+
+
+class DeviceVectorEnv:
+    #: vector steps the episode ring holds; a loop must copy a step's cells out
+    #: before ``ring_steps`` further steps overwrite them
+    RING_STEPS = 256
+
+    def __init__(self, kind_or_name, num_envs: int, device=None, ring_steps: Optional[int] = None, **env_kwargs):
+        self._setup(KINDS[kind_name(kind_or_name)][1](**env_kwargs), num_envs, device, ring_steps)
+
+    @classmethod
+    def from_env(cls, host_env, num_envs: int, device=None, ring_steps: Optional[int] = None) -> "DeviceVectorEnv":
+        """N device copies of ``host_env`` (an instance of a ``sac.envs`` class), with its parameters."""
+        kind_name(type(host_env))
+        self = cls.__new__(cls)
+        self._setup(host_env, num_envs, device, ring_steps)
+        return self
+
+    def _setup(self, host, num_envs: int, device, ring_steps: Optional[int]) -> None:
+        self.kind = kind_name(type(host))
+        self.kind_code = KINDS[self.kind][0]
+        self.num_envs = int(num_envs)
+        if self.num_envs < 1:
+            raise ValueError("DeviceVectorEnv needs at least one environment")
+        # the host instance supplies the spaces (the same Box as sac/envs.py) and the parameters
+        self.single_observation_space = self.observation_space = host.observation_space
+        self.single_action_space = self.action_space = host.action_space
+        self.spec = getattr(host, "spec", None)
+        self.obs_dim = int(np.prod(host.observation_space.shape))
+        self.act_dim = int(np.prod(host.action_space.shape))
+        self.max_steps = int(host.max_steps)
+        params = dict.fromkeys(E.ENV_PARAMS, 0.0)
+        params["action_low"] = float(host.action_space.low[0])
+        params["action_high"] = float(host.action_space.high[0])
+        for field, attr in _PARAM_ATTRS[self.kind].items():
+            params[field] = float(getattr(host, attr))
+        self.params = params
+        self._params = [params[k] for k in E.ENV_PARAMS]
+        self._icfg = [self.kind_code, self.num_envs, self.obs_dim, self.max_steps]
+        self.device = torch.device(device) if device is not None else torch.device(
+            "cuda" if torch.cuda.is_available() else "cpu")
+        E.require_gpu(self.device)
+        self.ops = E.ops()
+        N, dev = self.num_envs, self.device
+        self.ring_steps = int(ring_steps or self.RING_STEPS)
+        if self.ring_steps < 1:
+            raise ValueError("ring_steps must be >= 1")
+        self.obs = torch.zeros(N, self.obs_dim, dtype=torch.float32, device=dev)
+        self.counters = torch.zeros(2, N, dtype=torch.int32, device=dev)   # step in episode, episode length
+        self.dstate = torch.zeros(2, N, dtype=torch.float64, device=dev)   # position, episode return
+        self.ring = torch.zeros(self.ring_steps, N, 2, dtype=torch.float64, device=dev)
+        self.seed = 0
+        self.t = 0  # vector steps taken since the last reset; step k (0-based) is RNG step t = k + 1
+        self._reset_done = False
+
+    # ------------------------------------------------------------------ gym-shaped API
+    def reset(self, seed: Optional[int] = None, options: Optional[dict] = None):
+        """Reset every env (``seed`` keys the observation draws from here on;
+        None keeps the current one).  Returns (obs device tensor, {})."""
+        if seed is not None:
+            self.seed = int(seed) & 0x7FFFFFFFFFFFFFFF
+        self.t = 0
+        with torch.cuda.device(self.device):
+            self.ops.envs_reset(self.obs, self.counters, self.dstate, self._icfg, self._params, self.seed)
+        self._reset_done = True
+        return self.obs.clone(), {}
+
+    def step(self, actions):
+        """Step with device actions [N][1] -> device tensors (obs, rewards,
+        terminated, truncated, {"final_obs": ...}); no host copy, no sync."""
+        if not self._reset_done:
+            self.reset()
+        if not (isinstance(actions, torch.Tensor) and actions.is_cuda):
+            raise TypeError("DeviceVectorEnv.step takes a device tensor of actions (it never copies from the host)")
+        actions = actions.to(torch.float32).reshape(self.num_envs, self.act_dim).contiguous()
+        with torch.cuda.device(self.device):
+            obs, final_obs, rew, term, trunc = self.ops.envs_step(
+                self.obs, self.counters, self.dstate, self.ring, self._icfg, self._params, self.seed, actions,
+                self.t + 1)
+        self.t += 1
+        return obs, rew, term, trunc, {"final_obs": final_obs}
+
+    def seed_action_spaces(self, seed: int) -> None:
+        self.action_space.seed(seed)
+
+    def close(self) -> None:
+        pass
+
+    # ------------------------------------------------------------------ episode records
+    def episode_cells(self, t_first: int, t_last: int):
+        """Queue an asynchronous copy of the ring cells of steps t_first..t_last
+        (RNG step numbers, inclusive; at most ring_steps of them) to pinned host
+        memory: (host tensor [n][N][2] float64, event).  No synchronisation."""
+        n = t_last - t_first + 1
+        if n < 1 or n > self.ring_steps:
+            raise ValueError(f"episode_cells: {n} steps do not fit the ring of {self.ring_steps}")
+        host = torch.empty(n, self.num_envs, 2, dtype=torch.float64, pin_memory=True)
+        a, b = t_first % self.ring_steps, t_last % self.ring_steps
+        with torch.cuda.device(self.device):
+            if a <= b:
+                host.copy_(self.ring[a:b + 1], non_blocking=True)
+            else:  # the range wraps the ring
+                k = self.ring_steps - a
+                host[:k].copy_(self.ring[a:], non_blocking=True)
+                host[k:].copy_(self.ring[:b + 1], non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+        return host, ev
+
+    @staticmethod
+    def decode_cells(host) -> Tuple[List[float], List[int]]:
+        """(returns, lengths) of the episodes that ended in copied cells [n][N][2], in (t, i) order."""
+        ints = host[..., 1].contiguous().view(torch.int32).reshape(host.shape[0], host.shape[1], 2)
+        ended = ints[..., 1] != 0  # boolean-mask indexing is row-major: (t, i) order
+        return host[..., 0][ended].tolist(), ints[..., 0][ended].tolist()
+
+
+class EpisodeDrain:
+    """Finished episodes of a ``DeviceVectorEnv`` in ``(t, i)`` order without
+    per-step host traffic (the ``QValueLog`` pattern of sac/agent.py): every
+    ``every`` vector steps ``after_step`` queues one pinned copy of the new ring
+    cells behind the launches and hands finished copies to ``on_episode(ret,
+    length)``; ``finish`` waits for the rest."""
+
+    def __init__(self, envs: DeviceVectorEnv, on_episode, every: int = 64):
+        self.envs, self.on_episode = envs, on_episode
+        self.every = max(1, min(int(every), envs.ring_steps))
+        self.copied_to = envs.t  # last RNG step whose cells were queued
+        self.pending: List[tuple] = []
+
+    def _queue(self) -> None:
+        t = self.envs.t
+        if t > self.copied_to:
+            self.pending.append(self.envs.episode_cells(self.copied_to + 1, t))
+            self.copied_to = t
+
+    def _consume(self, block: bool) -> None:
+        while self.pending:
+            host, ev = self.pending[0]
+            if not block and not ev.query():
+                return
+            ev.synchronize()
+            for ret, length in zip(*DeviceVectorEnv.decode_cells(host)):
+                self.on_episode(ret, length)
+            self.pending.pop(0)
+
+    def after_step(self) -> None:
+        if self.envs.t - self.copied_to >= self.every:
+            self._queue()
+        self._consume(block=False)
+
+    def finish(self) -> None:
+        """Blocking: every episode that ended up to now."""
+        self._queue()
+        self._consume(block=True)
+
+
+__all__ = ["DeviceVectorEnv", "EpisodeDrain", "KINDS", "kind_name"]

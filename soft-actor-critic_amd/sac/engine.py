@@ -297,6 +297,31 @@ class SacEngine:
                                           bool(want_log_pi and eps is not None))
         return (act, lp if lp.numel() else None) if want_log_pi else act
 
+    def rollout_step(self, envs, replay, deterministic: bool = False, store: bool = True) -> None:
+        """One vector step of a ``sac.device_envs.DeviceVectorEnv`` in ONE
+        launch: the policy's actions for the envs' current observations (the
+        squashed-Gaussian sample with device noise, or tanh(mu) * scale when
+        ``deterministic``), the env step, and -- unless ``store`` is False
+        (evaluation) -- the N transitions appended to ``replay`` at its
+        host-tracked (size, pos), which advance as in ``_push_device_rows``.
+        No host copy and no synchronisation."""
+        if not replay._alloc_done:
+            replay._alloc(envs.obs_dim, envs.act_dim)
+        replay.flush()
+        if not envs._reset_done:
+            envs.reset()
+        n = envs.num_envs
+        if n > replay.capacity:
+            raise ValueError(f"rollout_step: num_envs ({n}) exceeds the replay capacity ({replay.capacity})")
+        with torch.cuda.device(self.device):
+            self.ops.rollout_step(self.handle.value, envs.obs, envs.counters, envs.dstate, envs.ring, envs._icfg,
+                                  envs._params, envs.seed, replay.storage, replay.state, replay.layout_spec,
+                                  replay._size, replay._pos, envs.t + 1, bool(deterministic), bool(store))
+        envs.t += 1
+        if store:
+            replay._size = min(replay.capacity, replay._size + n)
+            replay._pos = (replay._pos + n) % replay.capacity
+
     def time_phases(self, replay, n_steps: int) -> List[float]:
         """[A, B, C, D, gap]: mean hipEvent interval per phase launch (ms) and
         that of an empty kernel launched the same way (see sac_engine.h)."""

@@ -19,6 +19,11 @@ aggregate as one JSON line.
 Without torchrun it runs one replica in-process.  ``--env`` names one of the
 probe envs of ``sac.envs`` or, when gymnasium is importable, any registered
 gymnasium id (the reference's own envs).
+
+``--device-envs`` (probe envs only) keeps the environments on the device
+(``sac.device_envs.DeviceVectorEnv``) and trains through
+``SAC.run_device_training_loop``: act -> step -> store is one launch per
+vector step, with no per-step host<->device traffic.
 """
 from __future__ import annotations
 
@@ -66,11 +71,14 @@ def rank_env() -> tuple:
 
 
 def train_replica(config: dict, make_env: Callable[[], object], num_envs: int, env_steps: int, every: int,
-                  rank: int, device: Optional[str] = None, agent_cls=None, vec_env_cls=None) -> dict:
+                  rank: int, device: Optional[str] = None, agent_cls=None, vec_env_cls=None,
+                  device_envs: bool = False) -> dict:
     """Train this rank's replica and return {"metrics": its loop metrics,
     "aggregate": the all-reduced METRICS summary}.  ``agent_cls`` /
     ``vec_env_cls`` default to sac.agent.SAC / sac.vector_env.SyncVectorEnv
-    (tests pass host stubs)."""
+    (tests pass host stubs).  ``device_envs``: ``make_env`` must build a probe
+    env of sac.envs; num_envs device copies of it (DeviceVectorEnv.from_env)
+    train through ``run_device_training_loop``."""
     if agent_cls is None:
         from sac.agent import SAC as agent_cls  # noqa: N813
     if vec_env_cls is None:
@@ -82,7 +90,12 @@ def train_replica(config: dict, make_env: Callable[[], object], num_envs: int, e
     lg = cfg.get("logger", {})
     if lg.get("agent_name"):
         lg["agent_name"] = f"{lg['agent_name']}_rank{rank}"  # per-replica run directories
-    vec = vec_env_cls([make_env] * num_envs)
+    if device_envs:
+        from sac.device_envs import DeviceVectorEnv
+
+        vec = DeviceVectorEnv.from_env(make_env(), num_envs, device=cfg["train"].get("device"))
+    else:
+        vec = vec_env_cls([make_env] * num_envs)
     agent = agent_cls(vec, cfg)
     if getattr(agent, "engine", None) is None:
         # no HIP engine (no MI355X visible, or train.engine_device: cpu): the
@@ -93,7 +106,8 @@ def train_replica(config: dict, make_env: Callable[[], object], num_envs: int, e
         raise E.EngineUnavailable(f"replica {rank}: replica training needs the HIP engine on an MI355X "
                                   f"(train.device={cfg['train'].get('device')!r}); there is no CPU fallback")
     agg = ReplicaAggregator(agent.engine, every)
-    metrics = agent.run_vectorized_training_loop(env_steps, callback=agg, seed=cfg["train"]["seed"])
+    loop = agent.run_device_training_loop if device_envs else agent.run_vectorized_training_loop
+    metrics = loop(env_steps, callback=agg, seed=cfg["train"]["seed"])
     return {"metrics": metrics, "aggregate": agg.finish()}
 
 
@@ -104,7 +118,11 @@ def main(argv=None) -> int:
     ap.add_argument("--num-envs", type=int, default=16)
     ap.add_argument("--env-steps", type=int, default=100_000)
     ap.add_argument("--aggregate-every", type=int, default=1000, help="gradient steps between all-reduces")
+    ap.add_argument("--device-envs", action="store_true",
+                    help="keep the (probe) environments on the device: one fused act/step/store launch per vector step")
     a = ap.parse_args(argv)
+    if a.device_envs and a.env not in PROBE_ENVS:
+        raise SystemExit(f"--device-envs: {a.env!r} is not a probe env ({sorted(PROBE_ENVS)})")
     import yaml
 
     with open(a.config) as f:
@@ -120,7 +138,8 @@ def main(argv=None) -> int:
         torch.cuda.set_device(local)
         dist.init_process_group("nccl")  # RCCL on ROCm: the metric all-reduce only
     try:
-        out = train_replica(config, env_factory(a.env), a.num_envs, a.env_steps, a.aggregate_every, rank, device)
+        out = train_replica(config, env_factory(a.env), a.num_envs, a.env_steps, a.aggregate_every, rank, device,
+                            device_envs=a.device_envs)
     finally:
         if world > 1:
             import torch.distributed as dist
