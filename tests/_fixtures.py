@@ -7,8 +7,9 @@ import numpy as np
 from oracle import sac_oracle as O
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-CONFIGS = ["c1_fixed", "c1_auto", "elu3_clamp", "mix_act", "gelu_tanh", "const_reward", "c2", "donkey_new"]
-FULL_INIT = ["c1_fixed", "c1_auto", "elu3_clamp", "mix_act", "gelu_tanh", "const_reward"]
+CONFIGS = ["c1_fixed", "c1_auto", "elu3_clamp", "mix_act", "gelu_tanh", "const_reward", "c2", "donkey_new",
+           "out_smooth", "out_kink"]
+FULL_INIT = ["c1_fixed", "c1_auto", "elu3_clamp", "mix_act", "gelu_tanh", "const_reward", "out_smooth", "out_kink"]
 
 
 class NpzParts:
@@ -104,10 +105,11 @@ def oracle_state(name):
     hp = O.SacHyper.from_config(cfg)
     sds = init_state_dicts(name)
     qa, pa = cfg["q_net"]["hidden_layers_act"], cfg["policy_net"]["hidden_layers_act"]
-    pi = O.MLP.from_state_dict(sds["policy"], pa)
-    q1 = O.MLP.from_state_dict(sds["q1"], qa)
-    q2 = O.MLP.from_state_dict(sds["q2"], qa)
+    qo, po = cfg["q_net"]["output_activation"], cfg["policy_net"]["output_activation"]
+    pi = O.MLP.from_state_dict(sds["policy"], pa, po)
+    q1 = O.MLP.from_state_dict(sds["q1"], qa, qo)
+    q2 = O.MLP.from_state_dict(sds["q2"], qa, qo)
     st = O.SacState.fresh(pi, q1, q2, hp, meta["act"])
-    st.q1t = O.MLP.from_state_dict(sds["q1t"], qa)
-    st.q2t = O.MLP.from_state_dict(sds["q2t"], qa)
+    st.q1t = O.MLP.from_state_dict(sds["q1t"], qa, qo)
+    st.q2t = O.MLP.from_state_dict(sds["q2t"], qa, qo)
     return st, hp, fx, meta

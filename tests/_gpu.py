@@ -54,6 +54,87 @@ def make_agent(name, precision="fp32", capacity=None):
     return agent, fx, meta, nets
 
 
+def _net_cfg(c):
+    """The activation and shape fields of an engine config dict, with the
+    defaults of bench.build_engine (ReLU nets, identity outputs, auto alpha,
+    log sigma clamped to [-20, 2])."""
+    return dict(q_hidden=c.get("q_hidden", c.get("hidden")), pi_hidden=c.get("pi_hidden", c.get("hidden")),
+                q_act=c.get("q_act", "relu"), pi_act=c.get("pi_act", "relu"),
+                q_out_act=c.get("q_out_act", "identity"), pi_out_act=c.get("pi_out_act", "identity"),
+                auto=bool(c.get("auto", True)), log_std_min=c.get("log_std_min", -20), log_std_max=c.get("log_std_max", 2))
+
+
+def build_engine(c, precision, seed=3, device=None, layout=None):
+    """Engine + synthetic replay of a config dict, as bench.build_engine builds
+    them (same seeding, hyper-parameters and replay rows), with the fields that
+    one leaves at its defaults:
+      obs, act, batch, capacity;
+      hidden, or q_hidden and pi_hidden (they may differ);
+      q_act, pi_act, q_out_act, pi_out_act (sac.models activation names);
+      auto (entropy tuning; False: alpha stays 0.1), log_std_min, log_std_max;
+      layout (kernel layout overrides of sac.engine.SacEngine; the `layout`
+      argument is merged over it).
+    The engine gains `.split` (sac_engine_uses_split, include/
+    sac_engine_testing.h) next to .roles / .pairs / .wide.  Returns (engine,
+    replay, c)."""
+    import ctypes
+
+    import bench
+    from sac.engine import SacEngine
+    from sac.models import PolicyNetwork, QNetwork
+    from sac.replay_buffer import ReplayBuffer
+
+    device = device or torch.device("cuda", 0)
+    n = _net_cfg(c)
+    pi = PolicyNetwork(c["obs"], c["act"], n["pi_hidden"], log_std_min=n["log_std_min"], log_std_max=n["log_std_max"],
+                       seed=seed, hidden_activations=n["pi_act"], output_activation=n["pi_out_act"]).to(device)
+    q1 = QNetwork(c["obs"], c["act"], n["q_hidden"], n["q_act"], n["q_out_act"], seed=seed).to(device)
+    q2 = QNetwork(c["obs"], c["act"], n["q_hidden"], n["q_act"], n["q_out_act"], seed=seed + 1).to(device)
+    q1t, q2t = copy.deepcopy(q1), copy.deepcopy(q2)
+    lay = dict(c.get("layout") or {}, **(layout or {}))
+    eng = SacEngine(pi, q1, q2, q1t, q2t, batch_size=c["batch"], gamma=0.99, tau=0.005, actor_lr=3e-4,
+                    critic_lr=3e-4, alpha_lr=3e-4, alpha=0.1, auto_entropy_tuning=n["auto"], device=device,
+                    precision=precision, seed=seed, layout=lay or None)
+    eng.lib.sac_engine_uses_split.argtypes = [ctypes.c_void_p]
+    eng.split = bool(eng.lib.sac_engine_uses_split(eng.handle))
+    rb = ReplayBuffer(c["capacity"], device=device, obs_dim=c["obs"], act_dim=c["act"])
+    bench.synthetic_replay(rb, c["capacity"], c["obs"], c["act"], seed)
+    return eng, rb, c
+
+
+def assert_layout(eng, want):
+    """The kernel family phases A and C run: "split" (hidden-split role
+    kernels), "roles" (per-network role kernels without the split), "rows"
+    (one workgroup per row tile), "pairs" (pair tiles) or "stage" (the
+    layer-synchronous stage path)."""
+    got = ("stage" if eng.wide else "split" if eng.split else "roles" if eng.roles else "pairs" if eng.pairs
+           else "rows")
+    flags = dict(split=eng.split, roles=eng.roles, pairs=eng.pairs, wide=eng.wide)
+    assert got == want, (want, flags)
+    # the flags exclude one another, except that the hidden split is a form of the role kernels
+    assert not (eng.wide and (eng.roles or eng.pairs)) and not (eng.pairs and eng.roles), flags
+    assert eng.roles or not eng.split, flags
+
+
+def oracle_hyper(c):
+    """oracle.sac_oracle.SacHyper of build_engine(c)."""
+    from oracle import sac_oracle as O
+
+    n = _net_cfg(c)
+    return O.SacHyper(alpha=0.1, auto_entropy_tuning=n["auto"],
+                      policy=O.PolicyCfg(n["log_std_min"], n["log_std_max"], 1.0))
+
+
+def engine_mlp(eng, key):
+    """Oracle MLP holding the engine's current parameters of one network, with
+    that network's hidden and output activations."""
+    from oracle import sac_oracle as O
+
+    net = eng.nets[key]
+    return O.MLP.from_state_dict({kk: v.detach().cpu().numpy().copy() for kk, v in net.state_dict().items()},
+                                 net.hidden_activations, net.output_activation)
+
+
 def run_step(agent, fx, meta, k):
     B, A = meta["batch"], meta["act"]
     idx = torch.arange((k - 1) * B, k * B, dtype=torch.int32).reshape(1, B)

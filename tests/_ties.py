@@ -4,7 +4,8 @@ fp32 parity checks (test infrastructure; the oracle is the checker).
 A "tie" is a decision of the step that fp32 summation order can flip between
 two correct implementations (the numpy oracle and the MFMA kernels):
 
-* a hidden ReLU pre-activation p with |p| <= rel * (|W| |x| + |b|) on a pass
+* a pre-activation p of a kinked activation (ReLU, leaky ReLU, SELU; hidden
+  layers and a kinked output activation) with |p| <= rel * (|W| |x| + |b|) on a pass
   whose backward runs (pi on s, the critics on (s, a) and, with the UPDATED
   critics, on (s, a~)): the unit's mask for that row, and so a rank-one term
   of every lower layer's dW, follows the sign the sum happened to take
@@ -15,7 +16,7 @@ two correct implementations (the numpy oracle and the MFMA kernels):
   min's backward routes the row's gradient to the other critic.
 
 Reference: /root/reference/sac/agent.py:195-260 (the passes), sac/models.py:
-115-149 (the ReLU stacks).  The parity tests draw each step's indices and eps
+104-149 (the activation stacks).  The parity tests draw each step's indices and eps
 until no tie is found, so the per-element parameter check (>= 99.5% within
 1e-6) runs on every network at every shape instead of being voided."""
 import copy
@@ -27,19 +28,55 @@ from oracle import sac_oracle as O
 REL = 1e-7
 
 
-def relu_ties(mlp, x, rel=REL):
-    """Rows of this forward with a hidden ReLU pre-activation within fp32
-    summation-order noise of 0 (float64 evaluation), as a boolean mask."""
+KINKED = ("relu", "leaky_relu", "selu")  # derivative jump at 0: 1 | 0, 1 | 0.01, 1.0507 | 1.7581
+
+
+def _act64(name, p):
+    """The activation in float64 (oracle.sac_oracle.act_fwd rounds to fp32)."""
+    if name == "identity":
+        return p
+    if name == "relu":
+        return np.maximum(p, 0.0)
+    if name == "tanh":
+        return np.tanh(p)
+    if name == "elu":
+        return np.where(p > 0, p, np.expm1(np.minimum(p, 0.0)))
+    if name == "leaky_relu":
+        return np.where(p > 0, p, 0.01 * p)
+    if name == "gelu":
+        from scipy.special import erf
+
+        return p * 0.5 * (1.0 + erf(p / np.sqrt(2.0)))
+    if name == "selu":
+        return float(O._SELU_SCALE) * np.where(p > 0, p, float(O._SELU_ALPHA) * np.expm1(np.minimum(p, 0.0)))
+    raise KeyError(name)
+
+
+def kink_ties(mlp, x, rel=REL):
+    """Rows of this forward with a pre-activation of a kinked activation (ReLU,
+    leaky ReLU, SELU: hidden layers, and the output layer when the net's output
+    activation is one of them) within fp32 summation-order noise of 0 (float64
+    evaluation, each layer propagated with its own activation), as a boolean
+    mask.  The smooth activations (ELU, tanh, GELU, identity) have no such
+    decision: a pre-activation at 0 moves their derivative by ~|p| only."""
     h = np.asarray(x, np.float64)
     rows = np.zeros(h.shape[0], bool)
-    if mlp.hidden_act != "relu":
+    n = len(mlp.W)
+    if mlp.hidden_act not in KINKED and mlp.out_act not in KINKED:
         return rows
-    for i in range(len(mlp.W) - 1):
+    for i in range(n):
+        act = mlp.hidden_act if i < n - 1 else mlp.out_act
+        if i == n - 1 and act not in KINKED:
+            break
         W, b = mlp.W[i].astype(np.float64), mlp.b[i].astype(np.float64)
         p = h @ W.T + b
-        rows |= np.any(np.abs(p) <= rel * (np.abs(h) @ np.abs(W).T + np.abs(b)), axis=1)
-        h = np.maximum(p, 0.0)
+        if act in KINKED:
+            rows |= np.any(np.abs(p) <= rel * (np.abs(h) @ np.abs(W).T + np.abs(b)), axis=1)
+        h = _act64(act, p)
     return rows
+
+
+relu_ties = kink_ties  # the name from when ReLU was the only kinked activation modelled
 
 
 def step_ties(st, hp, bt, et, ea, rel=REL):

@@ -160,6 +160,17 @@ CONFIGS = {
                        pi_hidden=[256, 256, 32], q_act="elu", pi_act="elu",
                        batch=128, auto=False, tau=0.02, actor_lr=4e-4,
                        critic_lr=4e-4, steps=2, full_steps=[], seed=23),
+    # Output activations.  out_smooth: tanh on the policy's output keeps log
+    # sigma in [-1, 1], so both edges of the +-0.5 clamp are active and the
+    # clamp's gradient mask meets the output activation's backward; ELU on Q.
+    "out_smooth": dict(obs=5, act=2, q_hidden=[32, 32], pi_hidden=[32, 32],
+                       q_act="tanh", pi_act="elu", q_out_act="elu", pi_out_act="tanh",
+                       log_std_min=-0.5, log_std_max=0.5, batch=32, auto=True,
+                       steps=3, full=True),
+    # out_kink: output activations with a derivative jump at 0, fixed alpha.
+    "out_kink": dict(obs=4, act=3, q_hidden=[40, 24], pi_hidden=[24, 40],
+                     q_out_act="leaky_relu", pi_out_act="selu", batch=48,
+                     auto=False, gamma=0.95, steps=3, full=True),
 }
 
 

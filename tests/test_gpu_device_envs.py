@@ -35,8 +35,9 @@ def lib():
     return lb
 
 
-def _cfg(precision="fp32", capacity=4096, warming=24, update_frequency=1, log_episodes=False, seed=3):
-    return {
+def _cfg(precision="fp32", capacity=4096, warming=24, update_frequency=1, log_episodes=False, seed=3, nets=None):
+    """nets: {"q_net": {...}, "policy_net": {...}} entries laid over the ReLU defaults."""
+    cfg = {
         "sac": {"gamma": 0.99, "tau": 0.005, "alpha": 0.2, "auto_entropy_tuning": True, "actor_lr": 3e-4,
                 "critic_lr": 3e-4, "alpha_lr": 3e-4},
         "q_net": {"hidden_sizes": [32, 32], "hidden_layers_act": "relu", "output_activation": "identity"},
@@ -49,6 +50,9 @@ def _cfg(precision="fp32", capacity=4096, warming=24, update_frequency=1, log_ep
         "logger": {"enabled": False, "env_name": "probe", "agent_name": "SAC", "log_episode_stats": log_episodes,
                    "log_q_values": False, "save_model": {"enabled": False, "path": None}},
     }
+    for k, v in (nets or {}).items():
+        cfg[k].update(v)
+    return cfg
 
 
 # name -> (sac.envs class name, constructor arguments)
@@ -62,7 +66,13 @@ CASES = {
     "point_reach": ("OneDPointMassReachEnv", dict(max_steps=7, dt=0.5, action_low=-1.0, action_high=1.0, goal_pos=0.5,
                                                   goal_tolerance=0.2)),
     "point_six": ("OneDPointMassReachEnv", dict(max_steps=6)),
+    # random_obs with the nets of NON_RELU_NETS (the fused step's action path off the ReLU branch)
+    "random_obs_out_smooth": ("RandomObsBinaryRewardEnv", dict(obs_dim=5, threshold=0.2, max_steps=4)),
 }
+# the out_smooth fixture's activations: ELU policy with a tanh output under a log sigma clamp at +-0.5
+NON_RELU_NETS = {"random_obs_out_smooth": {
+    "q_net": {"hidden_layers_act": "tanh", "output_activation": "elu"},
+    "policy_net": {"hidden_layers_act": "elu", "output_activation": "tanh", "log_std_min": -0.5, "log_std_max": 0.5}}}
 
 
 def host_vec(lib, case, N, seed):
@@ -264,10 +274,12 @@ def check_stored(lib, case, N, seed, rows, T, what=""):
 
 # ---------------------------------------------------------------- 2. the fused step's actions
 @pytest.mark.parametrize("precision", ["fp32", "bf16"])
-@pytest.mark.parametrize("case", ["random_obs", "point_reach"])
+@pytest.mark.parametrize("case", ["random_obs", "point_reach", "random_obs_out_smooth"])
 def test_fused_actions_match_policy_act(lib, case, precision):
     N, T = 17, 3
-    agent, dv = make_agent(case, N, precision)
+    agent, dv = make_agent(case, N, precision, nets=NON_RELU_NETS.get(case))
+    if case in NON_RELU_NETS:
+        assert agent.policy_net.hidden_activations == "elu" and agent.policy_net.output_activation == "tanh"
     eng, rb = agent.engine, agent.replay_buffer
     for _ in range(T):
         eng.rollout_step(dv, rb)

@@ -230,6 +230,47 @@ def test_policy_act_matches_torch(precision, tol):
         assert ((lp - lp_ref).abs() / lp_ref.abs().clamp_min(1.0)).max().item() <= tol
 
 
+# non-ReLU hidden layers, and the out_smooth fixture's activations: a tanh output
+# under a log sigma clamp at +-0.5 (both edges active), ELU on the critics' output
+ACT_POLICIES = {"gelu_tanh": dict(q_act="gelu", pi_act="tanh"),
+                "out_smooth": dict(q_act="tanh", pi_act="elu", q_out_act="elu", pi_out_act="tanh", log_std_min=-0.5,
+                                   log_std_max=0.5)}
+
+
+@pytest.mark.parametrize("precision,tol", [("fp32", 2e-5), ("bf16", 3e-2)])
+@pytest.mark.parametrize("kernels", ["roles", "stage"])
+@pytest.mark.parametrize("acts", sorted(ACT_POLICIES))
+def test_policy_act_matches_torch_with_activations(acts, kernels, precision, tol):
+    """test_policy_act_matches_torch on nets that are not ReLU and have output
+    activations, on a role-kernel engine and on a stage-path engine (which
+    keeps policy_act on the phase kernel), at widths that pad (40 -> 64,
+    72 -> 96).  The torch modules are the reference."""
+    from _gpu import assert_layout, build_engine
+
+    c = dict(obs=5, act=3, q_hidden=[72, 40], pi_hidden=[40, 72], batch=40, capacity=64, **ACT_POLICIES[acts])
+    eng, rb, c = build_engine(c, precision, device=DEV,
+                              layout={"layout": "roles"} if kernels == "roles" else {"stage_path": 1})
+    assert_layout(eng, kernels)
+    pi = eng.nets["pi"]
+    g = torch.Generator(device="cpu").manual_seed(0)
+    clamped = 0
+    for n in (1, 7, 300):
+        s = torch.randn(n, c["obs"], generator=g).to(DEV)
+        eps = torch.randn(n, c["act"], generator=g).to(DEV)
+        with torch.no_grad():
+            a_ref, _ = _torch_policy(pi, s, None)
+            a2_ref, lp_ref = _torch_policy(pi, s, eps)
+            raw = pi.net(s)[:, c["act"]:]
+            clamped += int(((raw < pi.log_std_min) | (raw > pi.log_std_max)).sum())
+        a = eng.policy_act(s)
+        a2, lp = eng.policy_act(s, eps, want_log_pi=True)
+        assert (a - a_ref).abs().max().item() <= tol
+        assert (a2 - a2_ref).abs().max().item() <= tol
+        assert ((lp - lp_ref).abs() / lp_ref.abs().clamp_min(1.0)).max().item() <= tol
+    if acts == "out_smooth":
+        assert clamped > 0  # the clamp is active on some rows
+
+
 # ---------------------------------------------------------------- checkpoints
 def test_save_load_roundtrip_continues_identically(tmp_path):
     from _gpu import make_agent

@@ -37,6 +37,16 @@ def _loss_ok(got, want, floor, rtol):
     return abs(got - want) <= rtol * max(abs(want), floor)
 
 
+# bf16 loss bounds of fixtures whose bf16 rounding alone exceeds 2e-3 rel, at
+# 2x the error of the same step on the CPU with every forward matmul's operands
+# rounded to bf16 (fp32 accumulate; tools/debug/bf16_loss_emulation.py) against
+# the fp32 oracle.  out_smooth (B = 32, tanh critics under an ELU output), step
+# 1: emulation L_Q1 2.36e-3, L_Q2 1.22e-3 rel; the engine 2.36e-3 on L_Q1 (the
+# same arithmetic); steps 2, 3 of the emulation <= 9.6e-4.  The seven older
+# fixtures in the same emulation: <= 1.4e-3 (mix_act step 2).
+BF16_LOSS_RTOL = {"out_smooth": 2 * 2.36e-3}
+
+
 @pytest.mark.parametrize("precision", ["fp32", "bf16"])
 @pytest.mark.parametrize("name", CONFIGS)
 def test_engine_matches_oracle(name, precision):
@@ -44,7 +54,7 @@ def test_engine_matches_oracle(name, precision):
 
     agent, fx, meta, nets = make_agent(name, precision)
     st, hp, _, _ = oracle_state(name)
-    rtol = 1e-4 if precision == "fp32" else 2e-3
+    rtol = 1e-4 if precision == "fp32" else BF16_LOSS_RTOL.get(name, 2e-3)
     lrs = {"policy": hp.actor_lr, "q1": hp.critic_lr, "q2": hp.critic_lr, "q1t": hp.critic_lr * hp.tau,
            "q2t": hp.critic_lr * hp.tau}  # per-step movement scale; targets accumulate tau * sum_i |dp_i|
     for k in range(1, meta["steps"] + 1):
@@ -136,9 +146,10 @@ def test_forced_layout_edges_match_oracle(shape, precision):
                                  layout={"layout": lay})
 
 
-@pytest.mark.parametrize("name", ["c1_auto", "c2"])
+@pytest.mark.parametrize("name", ["c1_auto", "c2", "out_smooth", "out_kink"])
 def test_engine_matches_reference_golden_directly(name):
-    """Step 1 against the reference's own captured outputs (no oracle in between)."""
+    """Step 1 against the reference's own captured outputs (no oracle in
+    between); out_smooth / out_kink: nets with output activations."""
     from _gpu import make_agent, run_step
 
     agent, fx, meta, nets = make_agent(name, "fp32")
@@ -244,12 +255,14 @@ def test_stage_path_is_used_where_the_phase_kernels_do_not_fit(shape):
 
 
 def _engine_mlp(eng, key):
-    """Oracle MLP holding the engine's current parameters of one network."""
-    return O.MLP.from_state_dict({kk: v.detach().cpu().numpy().copy() for kk, v in eng.nets[key].state_dict().items()},
-                                 "relu")
+    """Oracle MLP holding the engine's current parameters of one network (with
+    its hidden and output activations)."""
+    from _gpu import engine_mlp
+
+    return engine_mlp(eng, key)
 
 
-def _check_config_against_oracle(c, precision, steps, roles=None, traj_tol=1e-4, layout=None):
+def _check_config_against_oracle(c, precision, steps, roles=None, traj_tol=1e-4, layout=None, expect=None):
     """`steps` engine steps of config c against two oracles, with injected
     indices and eps:
       the trajectory oracle, started from the engine's initial state and run
@@ -263,24 +276,26 @@ def _check_config_against_oracle(c, precision, steps, roles=None, traj_tol=1e-4,
     any summation-order tie -- a ReLU pre-activation within fp32 noise of 0 on
     any pass, a min-Q near-tie of the actor pass -- get a fresh index and eps
     until none is left), so the element checks hold on all five networks at
-    every shape; the test prints how many rows it redrew and the ties seen."""
-    import bench
+    every shape; the test prints how many rows it redrew and the ties seen.
+    c is a config dict of tests/_gpu.py::build_engine: besides the shape it may
+    name activations, output activations, a fixed alpha (auto=False: L_alpha
+    NaN on both sides, the alpha state untouched) and the log sigma clamp; the
+    oracle's nets and hyper-parameters are built from the same dict.  expect:
+    the kernel layout the case must run (tests/_gpu.py::assert_layout)."""
+    from _gpu import assert_layout, build_engine, oracle_hyper
 
     ckey = "_parity_" + c.get("name", "cfg")
-    bench.CONFIGS[ckey] = c
-    try:
-        eng, rb, cc = bench.build_engine(ckey, precision, 3, torch.device("cuda", 0), layout=layout)
-    finally:
-        del bench.CONFIGS[ckey]
+    eng, rb, cc = build_engine(c, precision, 3, torch.device("cuda", 0), layout=layout)
     if roles is not None:
         assert eng.roles == roles
     if layout and layout.get("layout") == "pairs":
         assert eng.pairs and not eng.roles and not eng.wide
+    if expect is not None:
+        assert_layout(eng, expect)
     B, A = cc["batch"], cc["act"]
-    sds = {k: {kk: v.detach().cpu().numpy().copy() for kk, v in m.state_dict().items()} for k, m in eng.nets.items()}
-    hp = O.SacHyper(alpha=0.1, auto_entropy_tuning=True)  # bench.build_engine's hyper-parameters
-    st = O.SacState.fresh(O.MLP.from_state_dict(sds["pi"], "relu"), O.MLP.from_state_dict(sds["q1"], "relu"),
-                          O.MLP.from_state_dict(sds["q2"], "relu"), hp, A)
+    hp = oracle_hyper(cc)  # bench.build_engine's hyper-parameters where c names none
+    st = O.SacState.fresh(_engine_mlp(eng, "pi"), _engine_mlp(eng, "q1"), _engine_mlp(eng, "q2"), hp, A)
+    alpha0 = eng.alpha_state[:2].cpu().numpy().copy()
     rows = {k: getattr(rb, k).cpu().numpy() for k in ("obs", "act", "rew", "next_obs", "done")}
     g = np.random.default_rng(11)
     # bf16: 2e-3 at B >= 256; a loss over fewer rows averages fewer independent
@@ -291,7 +306,7 @@ def _check_config_against_oracle(c, precision, steps, roles=None, traj_tol=1e-4,
     fp32 = precision == "fp32"
     for k in range(1, steps + 1):
         # the engine's own pre-step state: the local oracle (fp32), y / log pi one step from it
-        loc = _oracle_state_from_engine(eng, A) if fp32 else None
+        loc = _oracle_state_from_engine(eng, A, hp.auto_entropy_tuning) if fp32 else None
         pre = {n: _engine_mlp(eng, n) for n in ("pi", "q1t", "q2t")}
         alpha_pre = np.float32(eng.alpha_state[1].item())
         idx, et, ea, bt, outs, redrawn, seen = _ties.tie_free_draw(g, rows, len(rb), B, A, hp,
@@ -320,7 +335,7 @@ def _check_config_against_oracle(c, precision, steps, roles=None, traj_tol=1e-4,
             np.testing.assert_allclose(lp, ref_loc["log_pi"], rtol=1e-4, atol=1e-4)
             fl_loc = float(np.mean(np.abs(loc.alpha * ref_loc["log_pi"])) + np.mean(np.abs(ref_loc["y"])))
             for i, (gv, w) in enumerate(zip(got, ref_loc["losses"])):
-                assert abs(gv - w) <= 1e-5 * max(abs(w), fl_loc if i == 2 else 1e-3), (ckey, "local", k, i, gv, w)
+                assert _loss_ok(gv, w, fl_loc if i == 2 else 1e-3, 1e-5), (ckey, "local", k, i, gv, w)
             for n, net in (("pi", post_loc.pi), ("q1", post_loc.q1), ("q2", post_loc.q2), ("q1t", post_loc.q1t),
                            ("q2t", post_loc.q2t)):
                 mine = {kk: v.detach().cpu().numpy() for kk, v in eng.nets[n].state_dict().items()}
@@ -352,12 +367,16 @@ def _check_config_against_oracle(c, precision, steps, roles=None, traj_tol=1e-4,
             if precision == "bf16":
                 d = np.concatenate(ds)
                 assert d.mean() <= 0.05 * lr + 1e-7, (c.get('name'), k, key, d.mean())
-        la = float(eng.alpha_state[0].item())
-        assert abs(la - st.log_alpha) <= (1e-7 if precision == "fp32" else 1e-5), (la, st.log_alpha)
+        if hp.auto_entropy_tuning:
+            la = float(eng.alpha_state[0].item())
+            assert abs(la - st.log_alpha) <= (1e-7 if precision == "fp32" else 1e-5), (la, st.log_alpha)
+        else:  # fixed alpha: no L_alpha on either side, [log alpha, alpha] as created
+            assert np.isnan(got[3]) and np.isnan(ref["losses"][3]), (ckey, k, got[3], ref["losses"][3])
+            assert np.array_equal(eng.alpha_state[:2].cpu().numpy(), alpha0), (ckey, k)
     eng.check()
 
 
-def _oracle_state_from_engine(eng, act):
+def _oracle_state_from_engine(eng, act, auto=True):
     """The engine's full training state as an oracle SacState: parameters of the
     five networks, Adam moments and step counts, and the alpha state."""
     to_np = lambda t: t.detach().cpu().numpy().copy()  # noqa: E731
@@ -369,7 +388,7 @@ def _oracle_state_from_engine(eng, act):
         opt[k] = O.AdamState([to_np(x) for x in m], [to_np(x) for x in v], float(steps[i]))
     al = eng.alpha_state.cpu().numpy()
     return O.SacState(mlp["pi"], mlp["q1"], mlp["q2"], mlp["q1t"], mlp["q2t"], opt["pi"], opt["q1"], opt["q2"], act,
-                      log_alpha=float(al[0]), alpha=float(al[1]), opt_alpha_m=float(al[2]),
+                      log_alpha=float(al[0]) if auto else None, alpha=float(al[1]), opt_alpha_m=float(al[2]),
                       opt_alpha_v=float(al[3]), opt_alpha_step=float(steps[3]))
 
 
@@ -454,8 +473,6 @@ def test_bf16_one_step_from_the_engine_state(shape):
     <= 3.1e-3 / 1.1e-2 at obs <= 24, 5.2e-3 for y at the 216-wide C4w input).
     This check found the row-tile kernels' bf16 fault (fixed in round 6): the
     actor rows' log pi wrong in ~30% of rows at hidden widths other than 256."""
-    import bench
-
     c = {"c2_split": dict(obs=24, act=4, hidden=[256, 256], batch=256, capacity=2048),
          "c3_pairs": dict(obs=24, act=4, hidden=[256, 256], batch=4096, capacity=8192),
          "roles_b384": dict(obs=24, act=4, hidden=[256, 256], batch=384, capacity=2048),
@@ -470,13 +487,20 @@ def test_bf16_one_step_from_the_engine_state(shape):
     lay = {"roles_b384": {"layout": "roles"}, "rowtile_b2000": {"layout": "rows"}, "pairs_b2000": {"layout": "pairs"},
            "c3_pairs": {"layout": "pairs"}, "stage_b2000": {"stage_path": 1}, "deep4_pairs": {"layout": "pairs"},
            "c3_rows": {"layout": "rows"}}.get(shape)
-    bench.CONFIGS["_local16"] = c
-    try:
-        eng, rb, cc = bench.build_engine("_local16", "bf16", 3, torch.device("cuda", 0), layout=lay)
-    finally:
-        del bench.CONFIGS["_local16"]
+    _bf16_one_step_from_the_engine_state(shape, c, lay)
+
+
+def _bf16_one_step_from_the_engine_state(shape, c, lay=None, expect=None):
+    """The body of test_bf16_one_step_from_the_engine_state (its docstring
+    states the bounds) for a config dict of tests/_gpu.py::build_engine; expect:
+    the kernel layout the case must run."""
+    from _gpu import assert_layout, build_engine, oracle_hyper
+
+    eng, rb, cc = build_engine(c, "bf16", 3, torch.device("cuda", 0), layout=lay)
+    if expect is not None:
+        assert_layout(eng, expect)
     B, A = cc["batch"], cc["act"]
-    hp = O.SacHyper(alpha=0.1, auto_entropy_tuning=True)
+    hp = oracle_hyper(cc)
     rows = {k: getattr(rb, k).cpu().numpy() for k in ("obs", "act", "rew", "next_obs", "done")}
     g = np.random.default_rng(13)
     lrs = {"pi": hp.actor_lr, "q1": hp.critic_lr, "q2": hp.critic_lr, "q1t": hp.critic_lr * hp.tau,
@@ -485,7 +509,7 @@ def test_bf16_one_step_from_the_engine_state(shape):
     f = max(1.0, (256 / B) ** 0.5)
     bad = []
     for k in range(1, 4):
-        st = _oracle_state_from_engine(eng, A)
+        st = _oracle_state_from_engine(eng, A, hp.auto_entropy_tuning)
         idx = g.choice(len(rb), size=B, replace=False).astype(np.int32)
         et = g.standard_normal((B, A)).astype(np.float32)
         ea = g.standard_normal((B, A)).astype(np.float32)

@@ -55,9 +55,11 @@ def test_models_init_matches_reference(name):
     seed = cfg["train"]["seed"]
     pc, qc = cfg["policy_net"], cfg["q_net"]
     pi = PolicyNetwork(meta["obs"], meta["act"], pc["hidden_sizes"], seed=seed,
-                       hidden_activations=pc["hidden_layers_act"])
-    q1 = QNetwork(meta["obs"], meta["act"], qc["hidden_sizes"], qc["hidden_layers_act"], seed=seed)
-    q2 = QNetwork(meta["obs"], meta["act"], qc["hidden_sizes"], qc["hidden_layers_act"], seed=seed + 1)
+                       hidden_activations=pc["hidden_layers_act"], output_activation=pc["output_activation"])
+    q1 = QNetwork(meta["obs"], meta["act"], qc["hidden_sizes"], qc["hidden_layers_act"], qc["output_activation"],
+                  seed=seed)
+    q2 = QNetwork(meta["obs"], meta["act"], qc["hidden_sizes"], qc["hidden_layers_act"], qc["output_activation"],
+                  seed=seed + 1)
     for net, m in (("policy", pi), ("q1", q1), ("q2", q2)):
         for k, v in m.state_dict().items():
             key = f"init/{net}/{k}"

@@ -25,23 +25,31 @@ SAC_E_INVALID, SAC_E_HIP = -1, -2
 
 
 def _cfg(name, precision):
-    c = bench.CONFIGS[name]
+    return _cfg_of(bench.CONFIGS[name], precision)
+
+
+def _cfg_of(c, precision):
+    """sac_engine_config of a config dict: hidden (or q_hidden / pi_hidden),
+    and optionally q_act, pi_act, q_out_act, pi_out_act (sac.models names),
+    auto, log_std_min / log_std_max: the fields of tests/_gpu.py::build_engine."""
+    from sac.models import ACT_CODES
+
     cfg = E.EngineConfig()
     cfg.obs_dim, cfg.act_dim, cfg.batch = c["obs"], c["act"], c["batch"]
-    qd = [c["obs"] + c["act"]] + c["hidden"] + [1]
-    pd = [c["obs"]] + c["hidden"] + [2 * c["act"]]
+    qd = [c["obs"] + c["act"]] + c.get("q_hidden", c.get("hidden")) + [1]
+    pd = [c["obs"]] + c.get("pi_hidden", c.get("hidden")) + [2 * c["act"]]
     cfg.q_layers, cfg.pi_layers = len(qd) - 1, len(pd) - 1
     for i, d in enumerate(qd):
         cfg.q_dims[i] = d
     for i, d in enumerate(pd):
         cfg.pi_dims[i] = d
-    cfg.q_hidden_act = cfg.pi_hidden_act = 1  # relu
-    cfg.q_out_act = cfg.pi_out_act = 0
+    cfg.q_hidden_act, cfg.pi_hidden_act = ACT_CODES[c.get("q_act", "relu")], ACT_CODES[c.get("pi_act", "relu")]
+    cfg.q_out_act, cfg.pi_out_act = ACT_CODES[c.get("q_out_act", "identity")], ACT_CODES[c.get("pi_out_act", "identity")]
     cfg.gamma, cfg.tau = 0.99, 0.005
-    cfg.log_std_min, cfg.log_std_max, cfg.action_scale = -20.0, 2.0, 1.0
+    cfg.log_std_min, cfg.log_std_max, cfg.action_scale = c.get("log_std_min", -20.0), c.get("log_std_max", 2.0), 1.0
     cfg.actor_lr = cfg.critic_lr = cfg.alpha_lr = 3e-4
     cfg.beta1, cfg.beta2, cfg.adam_eps = 0.9, 0.999, 1e-8
-    cfg.auto_entropy, cfg.target_entropy = 1, -float(c["act"])
+    cfg.auto_entropy, cfg.target_entropy = int(c.get("auto", True)), -float(c["act"])
     cfg.precision = E.PREC_FP32 if precision == "fp32" else E.PREC_BF16
     cfg.seed = 0
     return cfg
@@ -99,6 +107,69 @@ def test_unhonourable_layout_override_fails():
         lib.sac_engine_destroy(out)
         pytest.fail("layout=roles honoured at C3")
     assert rc == SAC_E_INVALID and "cannot be honoured: roles" in lib.sac_last_error().decode()
+
+
+def _activation_cases():
+    """The shapes, layout overrides and activations of tests/test_gpu_activations.py."""
+    import test_gpu_activations as GA
+
+    shapes = dict(GA.LAYOUTS, **{"stage_" + k: v for k, v in GA.STAGE_SHAPES.items()})
+    acts = {"elu_elu": dict(q_act="elu", pi_act="elu"), "relu_tanh": dict(q_act="relu", pi_act="tanh"),
+            "elu_relu": dict(q_act="elu", pi_act="relu"), "selu_leaky": dict(q_act="selu", pi_act="leaky_relu"),
+            "fixed_alpha": dict(q_act="elu", pi_act="elu", auto=False),
+            "relu_out_smooth": dict(GA.OUT_ACTS["smooth"]), "relu_out_kink": dict(GA.OUT_ACTS["kink"]),
+            "tanh_gelu_out_smooth": dict(GA.OUT_ACTS["smooth"], q_act="tanh", pi_act="gelu"),
+            "elu_elu_q_out_only": dict(GA.OUT_ACTS["smooth"], q_act="elu", pi_act="elu", pi_out_act="identity")}
+    return [(s, a, dict(shapes[s][0], **acts[a]), shapes[s][1]) for s in sorted(shapes) for a in sorted(acts)]
+
+
+@pytest.mark.parametrize("precision", ["fp32", "bf16"])
+@pytest.mark.parametrize("shape,acts,c,lay", _activation_cases(), ids=[f"{s}-{a}" for s, a, _, _ in _activation_cases()])
+def test_activation_matrix_plans(shape, acts, c, lay, precision):
+    """The shapes of the GPU activation matrix with non-ReLU and output
+    activation codes, their layout overrides, both precisions: the planner
+    accepts each one (no "internal", no refused override) and creation stops at
+    its first HIP call."""
+    lib = E.load_library()
+    cfg = _cfg_of(c, precision)
+    for k, v in (lay or {}).items():
+        setattr(cfg, k, E.LAYOUTS[v] if k == "layout" else int(v))
+    ws = lib.sac_engine_workspace_bytes(ctypes.byref(cfg))
+    assert ws > 0, lib.sac_last_error()
+    bufs = E.EngineBuffers(*([0x1000] * 15), 0x100000, ws)  # never dereferenced before the first HIP call
+    out = ctypes.c_void_p()
+    rc = lib.sac_engine_create(ctypes.byref(cfg), ctypes.byref(bufs), None, ctypes.byref(out))
+    msg = lib.sac_last_error().decode()
+    if rc == 0:  # a GPU is present: the engine exists; destroy it
+        lib.sac_engine_destroy(out)
+        pytest.skip("GPU present: the planner ran for real")
+    assert "internal" not in msg, msg
+    assert rc == SAC_E_HIP, (rc, msg)
+
+
+@pytest.mark.parametrize("shape,needs", [("w288", False), ("w384", True)])
+def test_stage_path_is_the_planners_choice_only_past_the_lds_layout(shape, needs):
+    """With the stage path refused (stage_path = -1) creation fails in the
+    planner exactly for the shape that needs it: [384, 384] critics do not fit
+    the phase kernels' LDS layout, [288, 40] at B = 40 does (it runs the role
+    kernels unless the stage path is forced)."""
+    import test_gpu_activations as GA
+
+    cfg = _cfg_of(dict(GA.STAGE_SHAPES[shape][0], q_act="elu", pi_act="elu"), "fp32")
+    cfg.stage_path = -1
+    lib = E.load_library()
+    ws = lib.sac_engine_workspace_bytes(ctypes.byref(cfg))
+    bufs = E.EngineBuffers(*([0x1000] * 15), 0x100000, max(ws, 1))
+    out = ctypes.c_void_p()
+    rc = lib.sac_engine_create(ctypes.byref(cfg), ctypes.byref(bufs), None, ctypes.byref(out))
+    msg = lib.sac_last_error().decode()
+    if rc == 0:
+        lib.sac_engine_destroy(out)
+        pytest.skip("GPU present: the planner ran for real")
+    if needs:
+        assert rc == SAC_E_INVALID and "B of LDS per workgroup (max 163840)" in msg, (rc, msg)
+    else:
+        assert rc == SAC_E_HIP and "internal" not in msg, (rc, msg)
 
 
 def _create_rc(obs, act, hidden, batch=64):

@@ -1,7 +1,10 @@
-"""tests/_ties.py on the CPU: a constructed ReLU tie is found on the row that
-holds it, and a tie-free draw leaves no tie on any pass (the GPU parity tests
-rely on both to keep the per-element parameter check on every network)."""
+"""tests/_ties.py on the CPU: a constructed tie of a kinked activation (ReLU,
+leaky ReLU, SELU; hidden or output layer) is found on the row that holds it,
+a smooth activation at 0 is not one, and a tie-free draw leaves no tie on any
+pass (the GPU parity tests rely on these to keep the per-element parameter
+check on every network)."""
 import numpy as np
+import pytest
 
 import _ties
 from oracle import sac_oracle as O
@@ -29,6 +32,77 @@ def test_relu_tie_is_found_on_its_row():
     x[3] -= (x[3].astype(np.float64) @ w) / (w @ w) * w
     m = _ties.relu_ties(st.pi, x, rel=1e-6)
     assert m[3] and m.sum() == 1
+
+
+def _row3_on_the_kink(mlp, x, layer):
+    """x with row 3 moved so that unit 0's pre-activation of `layer` (0: first
+    hidden layer, -1: the output layer of a net whose layers below it are the
+    identity) is 0 up to float64 rounding."""
+    w = mlp.W[0][0].astype(np.float64)
+    if layer == -1:  # the composite linear map of the whole stack, biases 0
+        M = np.eye(x.shape[1])
+        for W in mlp.W:
+            M = W.astype(np.float64) @ M
+        w = M[0]
+    x = x.copy()
+    x[3] -= (x[3].astype(np.float64) @ w) / (w @ w) * w
+    return x
+
+
+@pytest.mark.parametrize("act", ["leaky_relu", "selu"])
+def test_kinked_hidden_activation_tie_is_found_on_its_row(act):
+    st, _ = _state(5, 2, [16, 16], 0)
+    st.pi.hidden_act = act
+    x = np.random.default_rng(1).standard_normal((8, 5)).astype(np.float32)
+    assert not _ties.kink_ties(st.pi, x).any()
+    m = _ties.kink_ties(st.pi, _row3_on_the_kink(st.pi, x, 0), rel=1e-6)
+    assert m[3] and m.sum() == 1
+
+
+@pytest.mark.parametrize("act", ["elu", "tanh", "gelu", "identity"])
+def test_smooth_activation_at_zero_is_no_tie(act):
+    """A pre-activation at 0 decides nothing for a smooth activation: not
+    flagged, as a hidden or as an output activation."""
+    st, _ = _state(5, 2, [16, 16], 0)
+    x = np.random.default_rng(1).standard_normal((8, 5)).astype(np.float32)
+    st.pi.hidden_act = act
+    assert not _ties.kink_ties(st.pi, _row3_on_the_kink(st.pi, x, 0), rel=1e-6).any()
+    st.pi.hidden_act, st.pi.out_act = "identity", act
+    assert not _ties.kink_ties(st.pi, _row3_on_the_kink(st.pi, x, -1), rel=1e-6).any()
+
+
+@pytest.mark.parametrize("act", ["relu", "leaky_relu", "selu"])
+def test_kinked_output_activation_tie_is_found_on_its_row(act):
+    st, _ = _state(5, 2, [16, 16], 0)
+    st.pi.hidden_act, st.pi.out_act = "identity", act
+    x = np.random.default_rng(1).standard_normal((8, 5)).astype(np.float32)
+    assert not _ties.kink_ties(st.pi, x).any()
+    m = _ties.kink_ties(st.pi, _row3_on_the_kink(st.pi, x, -1), rel=1e-6)
+    assert m[3] and m.sum() == 1
+    # behind a smooth hidden activation the output layer is still checked
+    st.pi.hidden_act = "tanh"
+    assert not _ties.kink_ties(st.pi, x).any()
+    st.pi.b[-1][0] = -(st.pi.forward(x)[1][-1][1][3, 0])  # row 3's output pre-activation of unit 0 to ~0 (fp32)
+    m = _ties.kink_ties(st.pi, x, rel=1e-6)
+    assert m[3] and m.sum() == 1
+
+
+def test_step_ties_names_the_pass_of_an_output_kink():
+    """step_ties flags a kinked critic output activation on the critic pass."""
+    st, hp = _state(5, 2, [16, 16], 0)
+    for q in (st.q1, st.q2, st.q1t, st.q2t):
+        q.out_act = "leaky_relu"
+    g = np.random.default_rng(4)
+    B = 8
+    bt = O.Batch(g.standard_normal((B, 5)).astype(np.float32), g.uniform(-1, 1, (B, 2)).astype(np.float32),
+                 g.standard_normal(B).astype(np.float32), g.standard_normal((B, 5)).astype(np.float32),
+                 np.zeros(B, np.float32))
+    et, ea = g.standard_normal((2, B, 2)).astype(np.float32)
+    assert not _ties.step_ties(st, hp, bt, et, ea)[0]
+    p = st.q1.forward(np.concatenate([bt.s, bt.a], 1))[1][-1][1]
+    st.q1.b[-1][0] = -p[5, 0]
+    ties = _ties.step_ties(st, hp, bt, et, ea, rel=1e-6)[0]
+    assert set(ties) == {"q1(s,a)"} and ties["q1(s,a)"][5] and ties["q1(s,a)"].sum() == 1
 
 
 def test_tie_free_draw_leaves_no_tie():
