@@ -248,6 +248,13 @@ class AdamState:
         return AdamState([np.zeros_like(p) for p in params], [np.zeros_like(p) for p in params], 0.0)
 
 
+def _fma(a, b, c):
+    """a * b + c of float32 operands rounded once: the product of two float32
+    is exact in float64, and so, but for a double rounding in ~2^-29 of the
+    cases, is the sum."""
+    return (np.asarray(a, np.float64) * np.asarray(b, np.float64) + np.asarray(c, np.float64)).astype(F32)
+
+
 def adam_update(params, grads, st: AdamState, lr: float, beta1=0.9, beta2=0.999, eps=1e-8):
     """torch.optim.Adam single-tensor path (adam.py _single_tensor_adam)."""
     st.step += 1.0
@@ -259,10 +266,28 @@ def adam_update(params, grads, st: AdamState, lr: float, beta1=0.9, beta2=0.999,
     w = dt.type(1.0 - beta1)
     for i, (p, g) in enumerate(zip(params, grads)):
         m, v = st.m[i], st.v[i]
-        m[...] = m + w * (g - m)  # lerp, weight < 0.5
-        v[...] = v * dt.type(beta2) + dt.type(1.0 - beta2) * g * g
+        # torch's CPU lerp and addcmul end in a fused multiply-add (Lerp.h lerp_vec,
+        # PointwiseOpsKernel.cpp): lerp is fma(w, g - m, m) for a weight below 0.5 and
+        # fma(w - 1, g - m, g) from there on, addcmul fma((1 - beta2) g, g, beta2 v)
+        if w < 0.5:
+            m[...] = _fma(w, (g - m).astype(dt), m)
+        else:
+            m[...] = _fma(w - dt.type(1), (g - m).astype(dt), g)
+        v[...] = _fma((dt.type(1.0 - beta2) * g).astype(dt), g, (v * dt.type(beta2)).astype(dt))
         denom = np.sqrt(v) / dt.type(bc2_sqrt) + dt.type(eps)
         p[...] = p + dt.type(-step_size) * m / denom
+
+
+def adam_update_scalar(p: float, g: float, m: float, v: float, step: float, lr: float, beta1=0.9, beta2=0.999,
+                       eps=1e-8):
+    """adam_update on one float64 scalar (the reference's log_alpha); returns (p, m, v, step)."""
+    step += 1.0
+    m = m + (1 - beta1) * (g - m)
+    v = v * beta2 + (1 - beta2) * g * g
+    bc1 = 1 - beta1 ** step
+    bc2 = 1 - beta2 ** step
+    denom = math.sqrt(v) / math.sqrt(bc2) + eps
+    return p + (-lr / bc1) * m / denom, m, v, step
 
 
 # ----------------------------------------------------------------------------- agent state
@@ -276,6 +301,12 @@ class SacHyper:
     critic_lr: float = 3e-4
     alpha_lr: float = 3e-4
     policy: PolicyCfg = field(default_factory=PolicyCfg)
+    # torch.optim.Adam's defaults and the reference's target entropy (-act_dim,
+    # agent.py:43-53), which the reference cannot set; None: -act_dim
+    beta1: float = 0.9
+    beta2: float = 0.999
+    adam_eps: float = 1e-8
+    target_entropy: Optional[float] = None
 
     @staticmethod
     def from_config(cfg: dict) -> "SacHyper":
@@ -352,7 +383,7 @@ def training_step(st: SacState, hp: SacHyper, batch: Batch, eps_t: np.ndarray, e
         grads = []
         for w_, b_ in zip(gW, gb):
             grads += [w_, b_]
-        adam_update(q.params(), grads, opt, hp.critic_lr)
+        adam_update(q.params(), grads, opt, hp.critic_lr, hp.beta1, hp.beta2, hp.adam_eps)
 
     # ---- actor (agent.py:238-260), post-update critics
     at, lp, ctx = policy_sample(st.pi, s, eps_a, pc)
@@ -375,24 +406,19 @@ def training_step(st: SacState, hp: SacHyper, batch: Batch, eps_t: np.ndarray, e
     grads = []
     for w_, b_ in zip(gW, gb):
         grads += [w_, b_]
-    adam_update(st.pi.params(), grads, st.opt_pi, hp.actor_lr)
+    adam_update(st.pi.params(), grads, st.opt_pi, hp.actor_lr, hp.beta1, hp.beta2, hp.adam_eps)
 
     # ---- alpha (agent.py:263-280), fp64 log_alpha, fp32 loss
     if hp.auto_entropy_tuning:
-        H = F32(-float(st.act_dim))
+        H = F32(-float(st.act_dim) if hp.target_entropy is None else hp.target_entropy)
         la32 = F32(st.log_alpha)
         term = (lp + H).astype(F32)
         losses.append(float(-np.mean(la32 * term, dtype=F32)))
     if hp.auto_entropy_tuning and not st.alpha_orphaned:
         g = float(np.sum(F32(-1.0 / B) * term, dtype=F32))
-        st.opt_alpha_step += 1.0
-        b1, b2, e = 0.9, 0.999, 1e-8
-        st.opt_alpha_m = st.opt_alpha_m + (1 - b1) * (g - st.opt_alpha_m)
-        st.opt_alpha_v = st.opt_alpha_v * b2 + (1 - b2) * g * g
-        bc1 = 1 - b1 ** st.opt_alpha_step
-        bc2 = 1 - b2 ** st.opt_alpha_step
-        denom = math.sqrt(st.opt_alpha_v) / math.sqrt(bc2) + e
-        st.log_alpha = st.log_alpha + (-hp.alpha_lr / bc1) * st.opt_alpha_m / denom
+        st.log_alpha, st.opt_alpha_m, st.opt_alpha_v, st.opt_alpha_step = adam_update_scalar(
+            st.log_alpha, g, st.opt_alpha_m, st.opt_alpha_v, st.opt_alpha_step, hp.alpha_lr, hp.beta1, hp.beta2,
+            hp.adam_eps)
         st.alpha = math.exp(st.log_alpha)
     elif not hp.auto_entropy_tuning:
         losses.append(float("nan"))

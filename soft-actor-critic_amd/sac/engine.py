@@ -59,8 +59,12 @@ class SacEngine:
     def __init__(self, policy_net, q_net1, q_net2, q_net1_target, q_net2_target, *, batch_size: int,
                  gamma: float, tau: float, actor_lr: float, critic_lr: float, alpha_lr: float,
                  alpha: float, auto_entropy_tuning: bool, device, precision: str = "fp32",
-                 seed: int = 0, betas=(0.9, 0.999), eps: float = 1e-8, layout: Optional[dict] = None):
-        """``layout`` (tests and A/B runs only; None = the engine's choice, which
+                 seed: int = 0, betas=(0.9, 0.999), eps: float = 1e-8, layout: Optional[dict] = None,
+                 target_entropy: Optional[float] = None):
+        """``target_entropy``: the entropy target of the alpha loss; None = the
+        reference's -action_size.
+
+        ``layout`` (tests and A/B runs only; None = the engine's choice, which
         every measured number uses): kernel layout overrides, the fields of
         sac_engine_config named in sac._engine.LAYOUT_KEYS -- layout ("auto" |
         "roles" | "rows" | "pairs"; an override the shape cannot take fails in
@@ -115,7 +119,7 @@ class SacEngine:
         cfg.actor_lr, cfg.critic_lr, cfg.alpha_lr = actor_lr, critic_lr, alpha_lr
         cfg.beta1, cfg.beta2, cfg.adam_eps = betas[0], betas[1], eps
         cfg.auto_entropy = int(self.auto)
-        cfg.target_entropy = -float(pi.action_size)
+        cfg.target_entropy = -float(pi.action_size) if target_entropy is None else float(target_entropy)
         cfg.precision = PRECISIONS[precision]
         cfg.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
         for k, v in (layout or {}).items():

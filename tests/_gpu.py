@@ -64,6 +64,58 @@ def _net_cfg(c):
                 auto=bool(c.get("auto", True)), log_std_min=c.get("log_std_min", -20), log_std_max=c.get("log_std_max", 2))
 
 
+# build_engine's hyper-parameters where the config dict names none: those of bench.build_engine
+HYPER_DEFAULTS = dict(gamma=0.99, tau=0.005, alpha=0.1, actor_lr=3e-4, critic_lr=3e-4, alpha_lr=3e-4,
+                      action_scale=1.0, betas=(0.9, 0.999), adam_eps=1e-8, target_entropy=None)
+
+
+def _hyper(c):
+    return {k: c.get(k, d) for k, d in HYPER_DEFAULTS.items()}
+
+
+def synthetic_rows(cap, obs, act, seed, done_p):
+    """bench.synthetic_replay's rows (s ~ N(0, 1), a ~ U(-1, 1), r ~ N(0, 1),
+    s' = the next row's s, the same draws in the same order) with terminal
+    probability done_p instead of its 1 %, as a dict of the replay's columns
+    (no GPU needed)."""
+    rng = np.random.default_rng(seed)
+    s_all = rng.standard_normal((cap + 1, obs), dtype=np.float32)
+    a = rng.uniform(-1, 1, (cap, act)).astype(np.float32)
+    r = rng.standard_normal(cap, dtype=np.float32)
+    d = (rng.random(cap) < done_p).astype(np.float32)
+    return dict(obs=s_all[:cap], act=a, rew=r, next_obs=s_all[1:cap + 1], done=d)
+
+
+def config_rows(c, seed=3):
+    """The replay rows build_engine fills for a config dict that names done_p."""
+    return synthetic_rows(c["capacity"], c["obs"], c["act"], c.get("replay_seed", seed), c["done_p"])
+
+
+def torch_nets(c, seed=3):
+    """(pi, q1, q2) torch modules of a config dict on the CPU, as build_engine creates them."""
+    from sac.models import PolicyNetwork, QNetwork
+
+    n, h = _net_cfg(c), _hyper(c)
+    pi = PolicyNetwork(c["obs"], c["act"], n["pi_hidden"], log_std_min=n["log_std_min"], log_std_max=n["log_std_max"],
+                       seed=seed, action_scale=h["action_scale"], hidden_activations=n["pi_act"],
+                       output_activation=n["pi_out_act"])
+    q1 = QNetwork(c["obs"], c["act"], n["q_hidden"], n["q_act"], n["q_out_act"], seed=seed)
+    q2 = QNetwork(c["obs"], c["act"], n["q_hidden"], n["q_act"], n["q_out_act"], seed=seed + 1)
+    return pi, q1, q2
+
+
+def oracle_fresh_state(c, seed=3):
+    """The oracle's state of a config dict before its first step, from the same
+    initial parameters build_engine gives the engine, and its hyper-parameters
+    (no GPU needed).  Returns (SacState, SacHyper)."""
+    from oracle import sac_oracle as O
+
+    hp = oracle_hyper(c)
+    mlps = [O.MLP.from_state_dict({k: v.detach().numpy().copy() for k, v in net.state_dict().items()},
+                                  net.hidden_activations, net.output_activation) for net in torch_nets(c, seed)]
+    return O.SacState.fresh(*mlps, hp, c["act"]), hp
+
+
 def build_engine(c, precision, seed=3, device=None, layout=None):
     """Engine + synthetic replay of a config dict, as bench.build_engine builds
     them (same seeding, hyper-parameters and replay rows), with the fields that
@@ -71,7 +123,12 @@ def build_engine(c, precision, seed=3, device=None, layout=None):
       obs, act, batch, capacity;
       hidden, or q_hidden and pi_hidden (they may differ);
       q_act, pi_act, q_out_act, pi_out_act (sac.models activation names);
-      auto (entropy tuning; False: alpha stays 0.1), log_std_min, log_std_max;
+      auto (entropy tuning; False: alpha stays at its initial value), log_std_min, log_std_max;
+      gamma, tau, alpha (the initial one), actor_lr, critic_lr, alpha_lr, action_scale;
+      betas, adam_eps (Adam, of all four optimizers), target_entropy (None: -act);
+      done_p (terminal probability of the replay rows; given, the rows come
+      from synthetic_rows instead of bench.synthetic_replay, which has 1 %;
+      replay_seed: their seed, default the engine's);
       layout (kernel layout overrides of sac.engine.SacEngine; the `layout`
       argument is merged over it).
     The engine gains `.split` (sac_engine_uses_split, include/
@@ -81,24 +138,26 @@ def build_engine(c, precision, seed=3, device=None, layout=None):
 
     import bench
     from sac.engine import SacEngine
-    from sac.models import PolicyNetwork, QNetwork
     from sac.replay_buffer import ReplayBuffer
 
     device = device or torch.device("cuda", 0)
-    n = _net_cfg(c)
-    pi = PolicyNetwork(c["obs"], c["act"], n["pi_hidden"], log_std_min=n["log_std_min"], log_std_max=n["log_std_max"],
-                       seed=seed, hidden_activations=n["pi_act"], output_activation=n["pi_out_act"]).to(device)
-    q1 = QNetwork(c["obs"], c["act"], n["q_hidden"], n["q_act"], n["q_out_act"], seed=seed).to(device)
-    q2 = QNetwork(c["obs"], c["act"], n["q_hidden"], n["q_act"], n["q_out_act"], seed=seed + 1).to(device)
+    n, h = _net_cfg(c), _hyper(c)
+    pi, q1, q2 = (net.to(device) for net in torch_nets(c, seed))
     q1t, q2t = copy.deepcopy(q1), copy.deepcopy(q2)
     lay = dict(c.get("layout") or {}, **(layout or {}))
-    eng = SacEngine(pi, q1, q2, q1t, q2t, batch_size=c["batch"], gamma=0.99, tau=0.005, actor_lr=3e-4,
-                    critic_lr=3e-4, alpha_lr=3e-4, alpha=0.1, auto_entropy_tuning=n["auto"], device=device,
-                    precision=precision, seed=seed, layout=lay or None)
+    eng = SacEngine(pi, q1, q2, q1t, q2t, batch_size=c["batch"], gamma=h["gamma"], tau=h["tau"],
+                    actor_lr=h["actor_lr"], critic_lr=h["critic_lr"], alpha_lr=h["alpha_lr"], alpha=h["alpha"],
+                    auto_entropy_tuning=n["auto"], device=device, precision=precision, seed=seed,
+                    betas=tuple(h["betas"]), eps=h["adam_eps"], target_entropy=h["target_entropy"], layout=lay or None)
     eng.lib.sac_engine_uses_split.argtypes = [ctypes.c_void_p]
     eng.split = bool(eng.lib.sac_engine_uses_split(eng.handle))
     rb = ReplayBuffer(c["capacity"], device=device, obs_dim=c["obs"], act_dim=c["act"])
-    bench.synthetic_replay(rb, c["capacity"], c["obs"], c["act"], seed)
+    if c.get("done_p") is None:
+        bench.synthetic_replay(rb, c["capacity"], c["obs"], c["act"], seed)
+    else:
+        r = config_rows(c, seed)
+        rb.push_batch(r["obs"], r["act"], r["rew"], r["next_obs"], r["done"])
+        torch.cuda.synchronize()
     return eng, rb, c
 
 
@@ -120,9 +179,12 @@ def oracle_hyper(c):
     """oracle.sac_oracle.SacHyper of build_engine(c)."""
     from oracle import sac_oracle as O
 
-    n = _net_cfg(c)
-    return O.SacHyper(alpha=0.1, auto_entropy_tuning=n["auto"],
-                      policy=O.PolicyCfg(n["log_std_min"], n["log_std_max"], 1.0))
+    n, h = _net_cfg(c), _hyper(c)
+    return O.SacHyper(gamma=h["gamma"], tau=h["tau"], alpha=h["alpha"], auto_entropy_tuning=n["auto"],
+                      actor_lr=h["actor_lr"], critic_lr=h["critic_lr"], alpha_lr=h["alpha_lr"],
+                      policy=O.PolicyCfg(n["log_std_min"], n["log_std_max"], h["action_scale"]),
+                      beta1=h["betas"][0], beta2=h["betas"][1], adam_eps=h["adam_eps"],
+                      target_entropy=h["target_entropy"])
 
 
 def engine_mlp(eng, key):

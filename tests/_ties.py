@@ -13,7 +13,11 @@ two correct implementations (the numpy oracle and the MFMA kernels):
 * the same on the forward-only passes (pi on s', the targets on (s', a')),
   where the flipped unit moves y by ~|p| only, checked all the same;
 * a min-Q near-tie of the actor pass, |q1 - q2| <= rel * (|q1| + |q2|): the
-  min's backward routes the row's gradient to the other critic.
+  min's backward routes the row's gradient to the other critic;
+* a raw log sigma of pi(s), the pass whose backward runs, within
+  rel * (|W| |x| + |b|) of an edge of the clamp: the clamp's backward keeps or
+  zeroes that entry's gradient (a narrow clamp puts many entries near an edge;
+  at the default [-20, 2] none is).
 
 Reference: /root/reference/sac/agent.py:195-260 (the passes), sac/models.py:
 104-149 (the activation stacks).  The parity tests draw each step's indices and eps
@@ -76,6 +80,30 @@ def kink_ties(mlp, x, rel=REL):
     return rows
 
 
+def clamp_ties(mlp, x, lo, hi, rel=REL):
+    """Rows of the policy's forward with a raw log sigma output (the second
+    half of the net's output, before the clamp) within fp32 summation-order
+    noise of a clamp edge, as a boolean mask: the clamp's backward passes the
+    entry's gradient inside [lo, hi] and zeroes it outside, so the side the sum
+    happened to take decides a whole row of the last layer's dW.  float64
+    evaluation; the noise of the last layer's sum is rel * (|W| |x| + |b|), and
+    an output activation passes it on with a slope of at most 1.76 (SELU),
+    taken as 2."""
+    h = np.asarray(x, np.float64)
+    n = len(mlp.W)
+    for i in range(n):
+        W, b = mlp.W[i].astype(np.float64), mlp.b[i].astype(np.float64)
+        p = h @ W.T + b
+        if i == n - 1:
+            noise = rel * (np.abs(h) @ np.abs(W).T + np.abs(b))
+            if mlp.out_act != "identity":
+                noise = 2.0 * noise
+            A = p.shape[1] // 2
+            ls, noise = _act64(mlp.out_act, p)[:, A:], noise[:, A:]
+            return np.any((np.abs(ls - float(lo)) <= noise) | (np.abs(ls - float(hi)) <= noise), axis=1)
+        h = _act64(mlp.hidden_act, p)
+
+
 relu_ties = kink_ties  # the name from when ReLU was the only kinked activation modelled
 
 
@@ -92,6 +120,7 @@ def step_ties(st, hp, bt, et, ea, rel=REL):
     pc = hp.policy
     ties["pi(s')"] = relu_ties(st.pi, s2, rel)
     ties["pi(s)"] = relu_ties(st.pi, s, rel)
+    ties["clamp(s)"] = clamp_ties(st.pi, s, pc.log_std_min, pc.log_std_max, rel)
     a2, _, _ = O.policy_sample(st.pi, s2, et, pc)
     at, _, _ = O.policy_sample(st.pi, s, ea, pc)
     sa2 = np.concatenate([s2, a2], 1)

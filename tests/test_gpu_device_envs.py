@@ -68,11 +68,14 @@ CASES = {
     "point_six": ("OneDPointMassReachEnv", dict(max_steps=6)),
     # random_obs with the nets of NON_RELU_NETS (the fused step's action path off the ReLU branch)
     "random_obs_out_smooth": ("RandomObsBinaryRewardEnv", dict(obs_dim=5, threshold=0.2, max_steps=4)),
+    # random_obs with SCALED_NETS' action_scale (the fused step's own tanh(z) * scale)
+    "random_obs_scale": ("RandomObsBinaryRewardEnv", dict(obs_dim=5, threshold=0.2, max_steps=4)),
 }
 # the out_smooth fixture's activations: ELU policy with a tanh output under a log sigma clamp at +-0.5
 NON_RELU_NETS = {"random_obs_out_smooth": {
     "q_net": {"hidden_layers_act": "tanh", "output_activation": "elu"},
     "policy_net": {"hidden_layers_act": "elu", "output_activation": "tanh", "log_std_min": -0.5, "log_std_max": 0.5}}}
+SCALED_NETS = {"random_obs_scale": {"policy_net": {"action_scale": 2.5}}}
 
 
 def host_vec(lib, case, N, seed):
@@ -274,12 +277,13 @@ def check_stored(lib, case, N, seed, rows, T, what=""):
 
 # ---------------------------------------------------------------- 2. the fused step's actions
 @pytest.mark.parametrize("precision", ["fp32", "bf16"])
-@pytest.mark.parametrize("case", ["random_obs", "point_reach", "random_obs_out_smooth"])
+@pytest.mark.parametrize("case", ["random_obs", "point_reach", "random_obs_out_smooth", "random_obs_scale"])
 def test_fused_actions_match_policy_act(lib, case, precision):
     N, T = 17, 3
-    agent, dv = make_agent(case, N, precision, nets=NON_RELU_NETS.get(case))
+    agent, dv = make_agent(case, N, precision, nets=NON_RELU_NETS.get(case) or SCALED_NETS.get(case))
     if case in NON_RELU_NETS:
         assert agent.policy_net.hidden_activations == "elu" and agent.policy_net.output_activation == "tanh"
+    assert float(agent.engine.cfg.action_scale) == (2.5 if case in SCALED_NETS else 1.0)
     eng, rb = agent.engine, agent.replay_buffer
     for _ in range(T):
         eng.rollout_step(dv, rb)
@@ -294,6 +298,8 @@ def test_fused_actions_match_policy_act(lib, case, precision):
         err = np.abs(rows["act"][sl] - want).max()
         assert err <= 1e-6, (t, err)
     assert len(np.unique(rows["act"])) > N  # not one constant action
+    if case in SCALED_NETS:  # the scale shows: |tanh| alone stays below 1
+        assert np.abs(rows["act"]).max() > 1.0
     # deterministic: tanh(mu) * scale of the observation the step saw
     before = dv.obs.clone()
     n0 = len(rb)

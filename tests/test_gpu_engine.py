@@ -230,11 +230,13 @@ def test_policy_act_matches_torch(precision, tol):
         assert ((lp - lp_ref).abs() / lp_ref.abs().clamp_min(1.0)).max().item() <= tol
 
 
-# non-ReLU hidden layers, and the out_smooth fixture's activations: a tanh output
-# under a log sigma clamp at +-0.5 (both edges active), ELU on the critics' output
+# non-ReLU hidden layers, the out_smooth fixture's activations: a tanh output
+# under a log sigma clamp at +-0.5 (both edges active), ELU on the critics' output,
+# and an action_scale other than 1 (tanh(z) * scale in the policy kernel's own copy)
 ACT_POLICIES = {"gelu_tanh": dict(q_act="gelu", pi_act="tanh"),
                 "out_smooth": dict(q_act="tanh", pi_act="elu", q_out_act="elu", pi_out_act="tanh", log_std_min=-0.5,
-                                   log_std_max=0.5)}
+                                   log_std_max=0.5),
+                "scale2_5": dict(q_act="gelu", pi_act="tanh", action_scale=2.5)}
 
 
 @pytest.mark.parametrize("precision,tol", [("fp32", 2e-5), ("bf16", 3e-2)])
@@ -269,6 +271,8 @@ def test_policy_act_matches_torch_with_activations(acts, kernels, precision, tol
         assert ((lp - lp_ref).abs() / lp_ref.abs().clamp_min(1.0)).max().item() <= tol
     if acts == "out_smooth":
         assert clamped > 0  # the clamp is active on some rows
+    if acts == "scale2_5":
+        assert float(eng.cfg.action_scale) == 2.5 and a2_ref.abs().max().item() > 1.0  # |tanh| alone stays below 1
 
 
 # ---------------------------------------------------------------- checkpoints

@@ -262,7 +262,8 @@ def _engine_mlp(eng, key):
     return engine_mlp(eng, key)
 
 
-def _check_config_against_oracle(c, precision, steps, roles=None, traj_tol=1e-4, layout=None, expect=None):
+def _check_config_against_oracle(c, precision, steps, roles=None, traj_tol=1e-4, layout=None, expect=None,
+                                 on_step=None):
     """`steps` engine steps of config c against two oracles, with injected
     indices and eps:
       the trajectory oracle, started from the engine's initial state and run
@@ -274,14 +275,19 @@ def _check_config_against_oracle(c, precision, steps, roles=None, traj_tol=1e-4,
         within 1e-6, free of trajectory drift.
     fp32 steps are drawn tie-free from both states (tests/_ties.py: the rows of
     any summation-order tie -- a ReLU pre-activation within fp32 noise of 0 on
-    any pass, a min-Q near-tie of the actor pass -- get a fresh index and eps
+    any pass, a min-Q near-tie of the actor pass, a log sigma of pi(s) on an
+    edge of the clamp -- get a fresh index and eps
     until none is left), so the element checks hold on all five networks at
     every shape; the test prints how many rows it redrew and the ties seen.
     c is a config dict of tests/_gpu.py::build_engine: besides the shape it may
     name activations, output activations, a fixed alpha (auto=False: L_alpha
-    NaN on both sides, the alpha state untouched) and the log sigma clamp; the
+    NaN on both sides, the alpha state untouched), the log sigma clamp, the
+    hyper-parameters, Adam settings and the replay's terminal share; the
     oracle's nets and hyper-parameters are built from the same dict.  expect:
-    the kernel layout the case must run (tests/_gpu.py::assert_layout)."""
+    the kernel layout the case must run (tests/_gpu.py::assert_layout).
+    on_step: called after every step's checks with (k, hp, batch, the
+    trajectory oracle's policy before the step, the local oracle's post-step
+    state or None in bf16, the engine), for checks of the caller's own."""
     from _gpu import assert_layout, build_engine, oracle_hyper
 
     ckey = "_parity_" + c.get("name", "cfg")
@@ -309,6 +315,7 @@ def _check_config_against_oracle(c, precision, steps, roles=None, traj_tol=1e-4,
         loc = _oracle_state_from_engine(eng, A, hp.auto_entropy_tuning) if fp32 else None
         pre = {n: _engine_mlp(eng, n) for n in ("pi", "q1t", "q2t")}
         alpha_pre = np.float32(eng.alpha_state[1].item())
+        pi_pre = st.pi.copy() if on_step else None
         idx, et, ea, bt, outs, redrawn, seen = _ties.tie_free_draw(g, rows, len(rb), B, A, hp,
                                                                     [st, loc] if fp32 else [])
         if fp32:
@@ -373,6 +380,8 @@ def _check_config_against_oracle(c, precision, steps, roles=None, traj_tol=1e-4,
         else:  # fixed alpha: no L_alpha on either side, [log alpha, alpha] as created
             assert np.isnan(got[3]) and np.isnan(ref["losses"][3]), (ckey, k, got[3], ref["losses"][3])
             assert np.array_equal(eng.alpha_state[:2].cpu().numpy(), alpha0), (ckey, k)
+        if on_step:
+            on_step(k, hp, bt, pi_pre, post_loc if fp32 else None, eng)
     eng.check()
 
 

@@ -105,6 +105,54 @@ def test_step_ties_names_the_pass_of_an_output_kink():
     assert set(ties) == {"q1(s,a)"} and ties["q1(s,a)"][5] and ties["q1(s,a)"].sum() == 1
 
 
+@pytest.mark.parametrize("edge", ["lo", "hi"])
+def test_log_sigma_on_a_clamp_edge_is_found_on_its_row(edge):
+    """A raw log sigma moved onto an edge of a narrow clamp is flagged on its
+    row, by clamp_ties and as step_ties' "clamp(s)"; at a distance of 1e-3
+    from the edge it is not."""
+    st, hp = _state(5, 2, [16, 16], 0)
+    lo, hi = -0.1, 0.1
+    hp.policy = O.PolicyCfg(lo, hi, 1.0)
+    g = np.random.default_rng(4)
+    B = 8
+    bt = O.Batch(g.standard_normal((B, 5)).astype(np.float32), g.uniform(-1, 1, (B, 2)).astype(np.float32),
+                 g.standard_normal(B).astype(np.float32), g.standard_normal((B, 5)).astype(np.float32),
+                 np.zeros(B, np.float32))
+    et, ea = g.standard_normal((2, B, 2)).astype(np.float32)
+    assert not _ties.clamp_ties(st.pi, bt.s, lo, hi).any()
+    assert "clamp(s)" not in _ties.step_ties(st, hp, bt, et, ea)[0]
+    e = lo if edge == "lo" else hi
+    raw = st.pi.forward(bt.s)[0][:, 2:]  # log sigma of unit 0 is output 2 (act = 2)
+    b0 = st.pi.b[-1][2]
+    st.pi.b[-1][2] = b0 + np.float32(e) - raw[5, 0]  # row 5's log sigma of unit 0 onto the edge (fp32 rounding)
+    m = _ties.clamp_ties(st.pi, bt.s, lo, hi, rel=1e-6)
+    assert m[5] and m.sum() == 1
+    ties = _ties.step_ties(st, hp, bt, et, ea, rel=1e-6)[0]
+    assert ties["clamp(s)"][5] and ties["clamp(s)"].sum() == 1
+    for off in (1e-3, -1e-3):
+        st.pi.b[-1][2] = b0 + np.float32(e + off) - raw[5, 0]
+        assert not _ties.clamp_ties(st.pi, bt.s, lo, hi, rel=1e-6).any()
+        assert "clamp(s)" not in _ties.step_ties(st, hp, bt, et, ea, rel=1e-6)[0]
+
+
+def test_tie_free_draw_redraws_a_clamp_edge_row():
+    """tie_free_draw replaces a row whose log sigma sits on a clamp edge."""
+    obs, act, B, n = 5, 2, 8, 64
+    st, hp = _state(obs, act, [16, 16], 0)
+    hp.policy = O.PolicyCfg(-0.1, 0.1, 1.0)
+    g = np.random.default_rng(3)
+    s = g.standard_normal((n + 1, obs)).astype(np.float32)
+    rows = dict(obs=s[:n], next_obs=s[1:], act=g.uniform(-1, 1, (n, act)).astype(np.float32),
+                rew=g.standard_normal(n).astype(np.float32), done=(g.random(n) < 0.3).astype(np.float32))
+    idx0 = np.random.default_rng(5).choice(n, size=B, replace=False)  # the draw tie_free_draw makes first
+    raw = st.pi.forward(rows["obs"][idx0])[0][:, act:]
+    st.pi.b[-1][act] += np.float32(0.1) - raw[2, 0]
+    idx, et, ea, bt, outs, redrawn, seen = _ties.tie_free_draw(np.random.default_rng(5), rows, n, B, act, hp, [st],
+                                                               rel=1e-6)
+    assert seen.get("clamp(s)") == 1 and redrawn >= 1 and idx[2] != idx0[2]
+    assert not _ties.step_ties(st, hp, bt, et, ea, rel=1e-6)[0]
+
+
 def test_tie_free_draw_leaves_no_tie():
     obs, act, B, n = 6, 2, 512, 2048
     st, hp = _state(obs, act, [64, 64], 2)
