@@ -175,6 +175,18 @@ int sac_engine_train_graph(sac_engine *e, const sac_replay *rb, int32_t n_steps,
 int sac_policy_act(sac_engine *e, const float *obs, int32_t n, const float *eps,
                    float *action, float *log_pi, void *stream);
 
+/* Q1 and Q2 of n (state, action) rows: q[n][2].  Rows i at obs + i*obs_stride,
+ * act + i*act_stride (strides in floats, >= obs_dim / act_dim).  target != 0
+ * evaluates the target critics.  Replaces: the critic forwards of
+ * SAC._log_q_values (sac/agent.py:493-500). */
+int sac_q_values(sac_engine *e, const float *obs, int64_t obs_stride, const float *act, int64_t act_stride,
+                 int32_t n, int32_t target, float *q, void *stream);
+
+/* The same for n consecutive ring slots of a replay buffer, starting at
+ * first_slot and wrapping at capacity: (next_obs if use_next_obs else obs, act). */
+int sac_q_values_replay(sac_engine *e, const sac_replay *rb, int64_t first_slot, int32_t n,
+                        int32_t use_next_obs, int32_t target, float *q, void *stream);
+
 /* Append n transitions (packed rows [n][2*obs+act+2] = s|a|r|s'|d, device) at
  * host-tracked (size, pos); writes the new (size, pos) to rb->state.
  * Replaces: ReplayBuffer.push (sac/replay_buffer.py:21-30). */

@@ -63,6 +63,12 @@ int sac_debug_rollout_eps_host(uint64_t seed, uint64_t t, int32_t n, int32_t act
  * t).  Counter (t, i, which << 16 | k / 4), key seed (the environments');
  * output word k % 4: u = (word >> 8) * 2^-24, obs = 2u - 1 in [-1, 1). */
 int sac_debug_env_obs_host(uint64_t seed, uint64_t t, int32_t which, int32_t n, int32_t obs_dim, float *out);
+/* A host-only engine: the validated config and no device state (no HIP call is
+ * made).  For the argument checks of sac_q_values / sac_q_values_replay on a
+ * machine without a device: with valid arguments they return SAC_E_INVALID
+ * ("no device state") where the launch would be.  Pass it to no other entry
+ * point but sac_engine_destroy. */
+int sac_debug_engine_host(const sac_engine_config *cfg, sac_engine **out);
 #ifdef __cplusplus
 }
 #endif

@@ -1176,6 +1176,7 @@ static void set_lds_attrs(size_t bytes) {
   (void)hipFuncSetAttribute((const void*)sac_actor<T, true>, hipFuncAttributeMaxDynamicSharedMemorySize, b);
   (void)hipFuncSetAttribute((const void*)sac_policy_act_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, b);
   (void)hipFuncSetAttribute((const void*)sac_rollout_step_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, b);
+  (void)hipFuncSetAttribute((const void*)sac_q_values_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, b);
   (void)hipFuncSetAttribute((const void*)sac_target_critic_split<T>, hipFuncAttributeMaxDynamicSharedMemorySize, b);
   (void)hipFuncSetAttribute((const void*)sac_target_critic_pairs<T>, hipFuncAttributeMaxDynamicSharedMemorySize, b);
   (void)hipFuncSetAttribute((const void*)sac_actor_pairs<T>, hipFuncAttributeMaxDynamicSharedMemorySize, b);
@@ -1564,6 +1565,83 @@ int sac_policy_act(sac_engine* e, const float* obs, int32_t n, const float* eps,
   else
     sac_policy_act_kernel<float><<<blocks, SAC_THREADS, e->lds_bytes, s>>>(e->d, obs, n, eps, action, log_pi);
   HIPCHK(hipGetLastError());
+  return SAC_OK;
+}
+
+// The critics run on the policy kernel's row-tile LDS layout: plan() sizes ld /
+// ldo over all five networks, so this holds for every engine create accepts; it
+// is checked where it is relied on.
+static bool q_rowtile_fits(const sac_engine* e) {
+  const EngineDev& h = e->h;
+  const NetDev& q = h.net[NET_Q1];
+  for (int l = 0; l < q.L; ++l) {
+    if (q.l[l].Kp + 4 > h.ld) return false;
+    if (l == q.L - 1 ? q.l[l].Np + 4 > h.ldo : q.l[l].Np + 4 > h.ld) return false;
+  }
+  const size_t ends[4] = {(size_t)h.o_X + SAC_ROWS * h.ld, (size_t)h.o_Y + SAC_ROWS * h.ld,
+                          (size_t)h.o_out + SAC_ROWS * h.ldo, (size_t)h.o_outp + SAC_ROWS * h.ldo};
+  return *std::max_element(ends, ends + 4) * 4 <= e->lds_bytes && e->lds_bytes <= 160 * 1024;
+}
+
+// every argument validated by the caller; one launch, no host-side state
+static int launch_q_values(sac_engine* e, const QRows& rows, int32_t n, int32_t target, float* q, void* stream) {
+  if (!e->d) return fail(SAC_E_INVALID, "q_values: the engine has no device state (host-only test engine)");
+  if (!q_rowtile_fits(e))
+    return fail(SAC_E_INVALID, "q_values: the row-tile LDS layout does not hold the critics' layer widths");
+  const dim3 grid((unsigned)((n + SAC_ROWS - 1) / SAC_ROWS), 2);
+  hipStream_t s = (hipStream_t)stream;
+  if (e->cfg.precision == SAC_PREC_BF16)
+    sac_q_values_kernel<bf16><<<grid, SAC_THREADS, e->lds_bytes, s>>>(e->d, rows, n, target ? 1 : 0, q);
+  else
+    sac_q_values_kernel<float><<<grid, SAC_THREADS, e->lds_bytes, s>>>(e->d, rows, n, target ? 1 : 0, q);
+  HIPCHK(hipGetLastError());
+  return SAC_OK;
+}
+
+int sac_q_values(sac_engine* e, const float* obs, int64_t obs_stride, const float* act, int64_t act_stride, int32_t n,
+                 int32_t target, float* q, void* stream) {
+  if (!obs || !act) return fail(SAC_E_INVALID, "q_values: null input (obs or act)");
+  if (!q) return fail(SAC_E_INVALID, "q_values: null output");
+  if (n < 1) return fail(SAC_E_INVALID, "q_values: n >= 1");
+  if (!e) return fail(SAC_E_INVALID, "null engine");
+  if (obs_stride < e->cfg.obs_dim || act_stride < e->cfg.act_dim)
+    return fail(SAC_E_INVALID, "q_values: stride below the field width (obs_stride " + std::to_string(obs_stride) +
+                                   " < " + std::to_string(e->cfg.obs_dim) + " or act_stride " +
+                                   std::to_string(act_stride) + " < " + std::to_string(e->cfg.act_dim) + ")");
+  return launch_q_values(e, QRows{obs, obs_stride, act, act_stride, 0, 0}, n, target, q, stream);
+}
+
+int sac_q_values_replay(sac_engine* e, const sac_replay* rb, int64_t first_slot, int32_t n, int32_t use_next_obs,
+                        int32_t target, float* q, void* stream) {
+  if (!rb || !rb->obs || !rb->act || !rb->next_obs) return fail(SAC_E_INVALID, "q_values_replay: null replay buffer");
+  if (!q) return fail(SAC_E_INVALID, "q_values_replay: null output");
+  if (n < 1) return fail(SAC_E_INVALID, "q_values_replay: n >= 1");
+  const int64_t cap = rb->capacity;
+  if (cap < 1 || first_slot < 0 || first_slot >= cap)
+    return fail(SAC_E_INVALID, "q_values_replay: first_slot (" + std::to_string(first_slot) +
+                                   ") outside [0, capacity " + std::to_string(cap) + ")");
+  if (n > cap)
+    return fail(SAC_E_INVALID, "q_values_replay: n (" + std::to_string(n) + ") exceeds the replay capacity (" +
+                                   std::to_string(cap) + ")");
+  if (!e) return fail(SAC_E_INVALID, "null engine");
+  if (rb->obs_dim != e->cfg.obs_dim || rb->act_dim != e->cfg.act_dim)
+    return fail(SAC_E_INVALID, "replay dims do not match the engine");
+  const RowStrides rs = row_strides(rb->row_stride, rb->obs_dim, rb->act_dim);
+  if (rs.obs < rb->obs_dim || rs.act < rb->act_dim)
+    return fail(SAC_E_INVALID, "q_values_replay: record stride below the field width");
+  return launch_q_values(e, QRows{use_next_obs ? rb->next_obs : rb->obs, rs.obs, rb->act, rs.act, first_slot, cap}, n,
+                         target, q, stream);
+}
+
+int sac_debug_engine_host(const sac_engine_config* cfg, sac_engine** out) {
+  if (!out) return fail(SAC_E_INVALID, "null out");
+  int rc = validate(cfg);
+  if (rc) return rc;
+  sac_engine* e = new sac_engine();
+  e->cfg = *cfg;
+  memset(&e->buf, 0, sizeof(e->buf));
+  memset(&e->h, 0, sizeof(e->h));
+  *out = e;
   return SAC_OK;
 }
 

@@ -2404,3 +2404,62 @@ __global__ void __launch_bounds__(SAC_THREADS) sac_policy_act_kernel(const Engin
     if (eps && log_pi) log_pi[b] = lp_sum - corr_sum;
   }
 }
+
+// ============================================================================ critics
+// Where the (state, action) rows of a sac_q_values launch live: row i is
+// physical row first + i (modulo == 0) or (first + i) % modulo (a ring), its
+// state at obs + row * obs_stride and its action at act + row * act_stride
+// (strides in floats).  One descriptor covers dense tensors, column views of a
+// records table and the struct-of-arrays replay.
+struct QRows {
+  const float* obs;
+  int64_t obs_stride;
+  const float* act;
+  int64_t act_stride;
+  int64_t first, modulo;
+};
+
+// Q1 and Q2 of n rows, forward only: q[n][2].  One workgroup per (row tile,
+// critic): blockIdx.x the tile, blockIdx.y the critic.  Sibling of
+// sac_policy_act_kernel (same LDS layout, same mlp_forward call) on the packed
+// compute copies the training kernels read and phase B rewrites.  Every
+// workgroup reads its own input rows and writes its own outputs: no hand-offs,
+// nothing depends on the order workgroups run in.  A row's sums do not depend
+// on the other rows of its tile (an MFMA row accumulates alone), nor on the
+// tile or slot it lands in.
+template <typename T>
+__global__ void __launch_bounds__(SAC_THREADS) sac_q_values_kernel(const EngineDev* __restrict__ Ep, QRows rows, int n,
+                                                                   int target, float* __restrict__ q_) {
+  PREFETCH_ARG(Ep);
+  const AS_C EngineDev& E = *(const AS_C EngineDev*)Ep;
+  extern __shared__ float lds_raw[];
+  lf* lds = (lf*)lds_raw;
+  constexpr int R = SAC_ROWS;
+  const int tid = threadIdx.x, O = E.O, A = E.A, ld = E.ld, ldo = E.ldo;
+  const int r0 = blockIdx.x * R, c = blockIdx.y;
+  const int nvalid = min(R, n - r0);
+  const AS_G float* obs = GPC(float, rows.obs);
+  const AS_G float* act = GPC(float, rows.act);
+  AS_G float* qo = GP(float, q_);
+  lf* Xb = lds + E.o_X;
+  lf* Yb = lds + E.o_Y;
+  lf* outB = lds + E.o_out;
+  lf* outP = lds + E.o_outp;
+  const AS_C NetDev& q = E.net[(target ? NET_Q1T : NET_Q1) + c];
+  const int Kp0 = q.l[0].Kp;
+  for (int i = tid; i < R * Kp0; i += SAC_THREADS) {
+    const int r = i / Kp0, k = i % Kp0;
+    float v = 0.f;
+    if (r < nvalid && k < O + A) {
+      int64_t row = rows.first + r0 + r;
+      if (rows.modulo) row %= rows.modulo;
+      v = k < O ? obs[row * rows.obs_stride + k] : act[row * rows.act_stride + (k - O)];
+    }
+    Xb[r * ld + k] = v;
+  }
+  __syncthreads();
+  Pf<T> pf;
+  pf.tag = nullptr;
+  mlp_forward<T, R>(q, Xb, Yb, ld, outP, outB, ldo, E.o_P1, E.ldp1, lds, false, false, 0, 0, 0, pf, gw_none());
+  if (tid < nvalid) qo[(size_t)(r0 + tid) * 2 + c] = outB[tid * ldo];
+}

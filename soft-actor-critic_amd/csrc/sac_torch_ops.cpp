@@ -15,6 +15,8 @@
 //   train_step           SAC.training_step            (sac/agent.py:302-327)
 //   train_graph          a loop of training_step      (sac/agent.py:361-364), hipGraph-replayed
 //   policy_act           SAC.select_action            (sac/agent.py:149-156; models.py:79-92)
+//   q_values             the critic forwards of SAC._log_q_values (sac/agent.py:493-500), ONE kernel
+//   q_values_replay      the same on ring slots of a replay buffer (no gather, no copy)
 //   envs_reset           SyncVectorEnv.reset          (sac/vector_env.py:39-46 over sac/envs.py)
 //   envs_step            SyncVectorEnv.step           (sac/vector_env.py:55-71 over sac/envs.py)
 //   rollout_step         select_actions + env.step + store_transitions of one vector step, ONE kernel
@@ -59,6 +61,8 @@ struct EngineApi {
   decltype(&sac_engine_train) engine_train = nullptr;
   decltype(&sac_engine_train_graph) engine_train_graph = nullptr;
   decltype(&sac_policy_act) policy_act = nullptr;
+  decltype(&sac_q_values) q_values = nullptr;
+  decltype(&sac_q_values_replay) q_values_replay = nullptr;
   decltype(&sac_envs_reset) envs_reset = nullptr;
   decltype(&sac_envs_step) envs_step = nullptr;
   decltype(&sac_rollout_step) rollout_step = nullptr;
@@ -86,6 +90,8 @@ void bind_engine_library(c10::string_view path_) {
   resolve(h, "sac_engine_train", a.engine_train);
   resolve(h, "sac_engine_train_graph", a.engine_train_graph);
   resolve(h, "sac_policy_act", a.policy_act);
+  resolve(h, "sac_q_values", a.q_values);
+  resolve(h, "sac_q_values_replay", a.q_values_replay);
   resolve(h, "sac_envs_reset", a.envs_reset);
   resolve(h, "sac_envs_step", a.envs_step);
   resolve(h, "sac_rollout_step", a.rollout_step);
@@ -283,6 +289,47 @@ std::tuple<at::Tensor, at::Tensor> policy_act(int64_t engine, const at::Tensor& 
   return {act, lp};
 }
 
+// rows of a [n][width] fp32 device tensor addressed by (data_ptr, stride(0)): a
+// column view of a wider table works without a copy
+void check_rows(const at::Tensor& t, const char* what) {
+  TORCH_CHECK(t.is_cuda(), what, " must be a HIP device tensor");
+  TORCH_CHECK(t.scalar_type() == at::kFloat, what, " must be float32");
+  TORCH_CHECK(t.dim() == 2 && t.size(1) >= 1, what, " must be [n][width]");
+  TORCH_CHECK(t.size(1) == 1 || t.stride(1) == 1, what, " must have unit inner stride");
+  TORCH_CHECK(t.size(0) <= 1 || t.stride(0) >= t.size(1), what, " rows overlap (row stride below the width)");
+}
+
+at::Tensor q_values(int64_t engine, const at::Tensor& obs, const at::Tensor& act, bool target) {
+  TORCH_CHECK(engine != 0, "null engine handle");
+  check_rows(obs, "obs");
+  check_rows(act, "act");
+  TORCH_CHECK(obs.size(0) == act.size(0) && obs.device() == act.device(),
+              "obs and act must hold the same number of rows on one device");
+  const int64_t n = obs.size(0);
+  TORCH_CHECK(n <= INT32_MAX, "too many rows");
+  at::Tensor q = at::empty({n, 2}, obs.options());
+  if (n) {
+    Guard g(obs.device());
+    // one row: any stride addresses it; pass the width
+    const int64_t so = n > 1 ? obs.stride(0) : obs.size(1), sa = n > 1 ? act.stride(0) : act.size(1);
+    check_rc(api().q_values(reinterpret_cast<sac_engine*>(engine), obs.data_ptr<float>(), so, act.data_ptr<float>(), sa,
+                            static_cast<int32_t>(n), target ? 1 : 0, q.data_ptr<float>(), stream_of(obs)));
+  }
+  return q;
+}
+
+at::Tensor q_values_replay(int64_t engine, const at::Tensor& storage, const at::Tensor& rstate, at::IntArrayRef layout,
+                           int64_t first_slot, int64_t n, bool next_obs, bool target) {
+  TORCH_CHECK(engine != 0, "null engine handle");
+  Replay r = make_replay(storage, rstate, layout);
+  TORCH_CHECK(n >= 1 && n <= r.d.capacity, "n must be in [1, capacity]");
+  at::Tensor q = at::empty({n, 2}, storage.options());
+  Guard g(storage.device());
+  check_rc(api().q_values_replay(reinterpret_cast<sac_engine*>(engine), &r.d, first_slot, static_cast<int32_t>(n),
+                                 next_obs ? 1 : 0, target ? 1 : 0, q.data_ptr<float>(), stream_of(storage)));
+  return q;
+}
+
 // ---------------------------------------------------------------- environments
 sac_envs make_envs(const at::Tensor& obs, const at::Tensor& counters, const at::Tensor& dstate,
                    const std::optional<at::Tensor>& ring, at::IntArrayRef icfg, at::ArrayRef<double> params,
@@ -409,6 +456,15 @@ std::tuple<at::Tensor, at::Tensor> policy_act_meta(int64_t, const at::Tensor& ob
   return {at::empty({n, act_dim}, obs.options()), at::empty({lp ? n : 0}, obs.options())};
 }
 
+at::Tensor q_values_meta(int64_t, const at::Tensor& obs, const at::Tensor&, bool) {
+  return at::empty({obs.size(0), 2}, obs.options());
+}
+
+at::Tensor q_values_replay_meta(int64_t, const at::Tensor& storage, const at::Tensor&, at::IntArrayRef, int64_t,
+                                int64_t n, bool, bool) {
+  return at::empty({n, 2}, storage.options());
+}
+
 void envs_reset_meta(at::Tensor&, at::Tensor&, at::Tensor&, at::IntArrayRef, at::ArrayRef<double>, int64_t) {}
 
 std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor> envs_step_meta(
@@ -439,6 +495,9 @@ TORCH_LIBRARY(sac_hip, m) {
   m.def("train_graph(int engine, Tensor(a!)[] state, Tensor storage, Tensor replay_state, int[] layout, "
         "int n_steps, int chunk) -> ()");
   m.def("policy_act(int engine, Tensor obs, Tensor? eps, int act_dim, bool want_log_pi=False) -> (Tensor, Tensor)");
+  m.def("q_values(int engine, Tensor obs, Tensor act, bool target=False) -> Tensor");
+  m.def("q_values_replay(int engine, Tensor storage, Tensor replay_state, int[] layout, int first_slot, int n, "
+        "bool next_obs=True, bool target=False) -> Tensor");
   m.def("envs_reset(Tensor(a!) obs, Tensor(b!) counters, Tensor(c!) dstate, int[] icfg, float[] params, int seed) "
         "-> ()");
   m.def("envs_step(Tensor(a!) obs, Tensor(b!) counters, Tensor(c!) dstate, Tensor(d!)? ring, int[] icfg, "
@@ -456,6 +515,8 @@ TORCH_LIBRARY_IMPL(sac_hip, CUDA, m) {
   m.impl("train_step", &train_step);
   m.impl("train_graph", &train_graph);
   m.impl("policy_act", &policy_act);
+  m.impl("q_values", &q_values);
+  m.impl("q_values_replay", &q_values_replay);
   m.impl("envs_reset", &envs_reset);
   m.impl("envs_step", &envs_step);
   m.impl("rollout_step", &rollout_step);
@@ -469,6 +530,8 @@ TORCH_LIBRARY_IMPL(sac_hip, Meta, m) {
   m.impl("train_step", &train_step_meta);
   m.impl("train_graph", &train_graph_meta);
   m.impl("policy_act", &policy_act_meta);
+  m.impl("q_values", &q_values_meta);
+  m.impl("q_values_replay", &q_values_replay_meta);
   m.impl("envs_reset", &envs_reset_meta);
   m.impl("envs_step", &envs_step_meta);
   m.impl("rollout_step", &rollout_step_meta);

@@ -113,6 +113,12 @@ SIGNATURES = {
                                               ctypes.c_int32, ctypes.c_void_p]),
     "sac_policy_act": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "sac_q_values": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                    ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
+                                    ctypes.c_void_p]),
+    "sac_q_values_replay": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ReplayDesc), ctypes.c_int64,
+                                           ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
+                                           ctypes.c_void_p]),
     "sac_replay_push": (ctypes.c_int, [ctypes.POINTER(ReplayDesc), ctypes.c_void_p, ctypes.c_int64,
                                        ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p]),
     "sac_replay_gather": (ctypes.c_int, [ctypes.POINTER(ReplayDesc), ctypes.c_void_p, ctypes.c_int32]
@@ -172,8 +178,8 @@ def ops_library_path() -> str:
 def ops():
     """``torch.ops.sac_hip``: the PyTorch custom ops over the C ABI
     (csrc/sac_torch_ops.cpp: replay_push, replay_gather, replay_sample,
-    replay_sample_gather, train_step, train_graph, policy_act, envs_reset,
-    envs_step, rollout_step).  The op library
+    replay_sample_gather, train_step, train_graph, policy_act, q_values,
+    q_values_replay, envs_reset, envs_step, rollout_step).  The op library
     dlopens the engine library ctypes loaded (bind_engine_library: the same file,
     so the same instance owns the engine handles).  Raises EngineUnavailable
     when it is not built."""

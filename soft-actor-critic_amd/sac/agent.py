@@ -377,6 +377,22 @@ class SAC:
             act = eng.policy_act(obs, eps)
         return act.cpu().numpy()
 
+    def q_values(self, states: Any, actions: Any, target: bool = False):
+        """(q1, q2) of n (state, action) pairs as float32 arrays of length n:
+        ONE launch of the critic-evaluation kernel on the weights the engine
+        trains with (``target``: the target critics).  Host arrays go up
+        through pinned memory; device tensors are read in place."""
+        eng = self._engine()
+
+        def rows(x, width):
+            if isinstance(x, torch.Tensor):
+                return x.detach().to(torch.float32).reshape(-1, width).to(self.device)
+            t = torch.from_numpy(np.ascontiguousarray(np.asarray(x, dtype=np.float32).reshape(-1, width)))
+            return t.pin_memory().to(self.device, non_blocking=True) if self.device.type == "cuda" else t
+
+        q = eng.q_values(rows(states, self.obs_size), rows(actions, self.action_size), target=target).cpu().numpy()
+        return q[:, 0].copy(), q[:, 1].copy()
+
     def store_transitions(self, states: Any, actions: Any, rewards: Any, next_states: Any, dones: Any) -> None:
         """N transitions in env order: one pinned H2D copy + one push kernel."""
         self.replay_buffer.push_batch(states, actions, rewards, next_states, dones)
@@ -700,7 +716,7 @@ class SAC:
     def run_device_training_loop(self, total_env_steps: int, vec_env: Any = None, logger=None,
                                  print_rewards: bool = False, seed: Optional[int] = None,
                                  callback: Optional[Callable[[Dict[str, float]], None]] = None,
-                                 drain_every: int = 64) -> Dict[str, float]:
+                                 drain_every: int = 64, device_q_values: bool = False) -> Dict[str, float]:
         """``run_vectorized_training_loop`` over a ``DeviceVectorEnv``: the envs
         live on the device and act -> step -> store is ONE launch
         (``SacEngine.rollout_step``), so a vector step is that launch plus the
@@ -722,15 +738,27 @@ class SAC:
 
         Actions are sampled with the engine's device RNG (Philox, ``which`` =
         2), not torch's generator, so a seeded run differs from the vectorised
-        loop's in its noise draws, not in distribution.  ``logger.log_q_values``
-        is not supported here (it evaluates the critics per env step on host
-        inputs): ValueError."""
-        from .device_envs import EpisodeDrain
+        loop's in its noise draws, not in distribution.
+
+        ``logger.log_q_values``: the host ``QValueLog`` evaluates the critics
+        per env step on host inputs, which this loop does not have, so by
+        default a config with it on is refused (ValueError).  With
+        ``device_q_values=True`` the values are logged on the device instead
+        (``sac.device_envs.DeviceQValueLog``): after each vector step's
+        gradient steps ONE launch of the critic-evaluation kernel reads the N
+        transitions just written from the replay ring and writes Q1 / Q2 of
+        (final_obs_i, a_i) into a device ring, drained every ``drain_every``
+        vector steps like the episodes -- the quantity the vectorised loop
+        logs, from the packed weights the engine trains with (in bf16 mode
+        those are the bf16 copies, not the fp32 eager forward).  With the
+        config key off, ``device_q_values`` logs and launches nothing."""
+        from .device_envs import DeviceQValueLog, EpisodeDrain
 
         env = self._device_env(vec_env, "run_device_training_loop")
-        if self.config["logger"]["log_q_values"]:
-            raise ValueError("run_device_training_loop does not support logger.log_q_values (per-env-step Q values "
-                             "need the transitions on the host); use run_vectorized_training_loop or turn it off")
+        if self.config["logger"]["log_q_values"] and not device_q_values:
+            raise ValueError("run_device_training_loop does not support logger.log_q_values through the host path "
+                             "(per-env-step Q values need the transitions on the host); pass device_q_values=True "
+                             "to log them on the device, use run_vectorized_training_loop, or turn it off")
         eng = self._engine()
         active_logger = logger or self.logger
         tr = self.config["train"]
@@ -756,8 +784,14 @@ class SAC:
             st["episodes"] += 1
 
         drain = EpisodeDrain(env, on_episode, drain_every)
+        q_log = None
+        if device_q_values and active_logger is not None and self.config["logger"]["log_q_values"]:
+            q_log = DeviceQValueLog(eng, self.replay_buffer, N, active_logger, drain_every)
         for _ in range((int(total_env_steps) + N - 1) // N):
             len_before = len(self.replay_buffer)
+            if q_log is not None:
+                self.replay_buffer.flush()  # rows pushed from the host go in first: they move the write slot
+            first_slot = self.replay_buffer._pos  # the step's N rows go to ring slots first_slot + i
             eng.rollout_step(env, self.replay_buffer)
             old = total_steps
             total_steps += N
@@ -768,6 +802,8 @@ class SAC:
                 grad_steps += due
                 if loss_log is not None:
                     loss_log.after_updates(total_steps)
+            if q_log is not None:  # env step old + 1 + i logs Q(s'_i, a_i) under the critics after this vector step
+                q_log.after_step(first_slot, old + 1)
             drain.after_step()
             if callback is not None:
                 callback({"env_steps": total_steps, "gradient_steps": grad_steps, "episodes": st["episodes"],
@@ -776,6 +812,8 @@ class SAC:
         drain.finish()
         if loss_log is not None:
             loss_log.finish()
+        if q_log is not None:
+            q_log.finish()
         metrics = {"total_episodes": st["episodes"], "best_avg_return": st["best"],
                    "final_avg_return": st["avg"], "total_env_steps": total_steps, "gradient_steps": grad_steps}
         if active_logger is not None:

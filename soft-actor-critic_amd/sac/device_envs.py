@@ -227,4 +227,84 @@ class EpisodeDrain:
         self._consume(block=True)
 
 
-__all__ = ["DeviceVectorEnv", "EpisodeDrain", "KINDS", "kind_name"]
+class DeviceQValueLog:
+    """``QValues/Q1`` and ``QValues/Q2`` per env step of the device-resident
+    loop: the device counterpart of ``sac.agent.QValueLog``, built like
+    ``EpisodeDrain``.
+
+    ``after_step(first_slot, first_step)`` queues ONE launch of the
+    critic-evaluation kernel (``SacEngine.q_values_replay``) that reads the N
+    transitions the rollout step just wrote from the replay ring in place and
+    writes Q1 / Q2 of (final_obs_i, a_i) under the critics of that moment into
+    cell ``t % S`` of a device ring ``[S][N][2]`` -- the quantity
+    ``run_vectorized_training_loop`` logs per env step.  Every ``every`` vector
+    steps the new cells are copied to pinned memory behind the launches;
+    once a copy's event has completed its values go to
+    ``logger.log_q_values(q1, q2, step)``, steps ``first_step + i`` in order.
+    ``finish`` consumes the rest, blocking.  Nothing else synchronises."""
+
+    RING_STEPS = 256
+
+    def __init__(self, engine, replay, num_envs: int, logger, every: int = 64, ring_steps: Optional[int] = None):
+        self.engine, self.replay, self.logger = engine, replay, logger
+        self.num_envs = int(num_envs)
+        self.ring_steps = int(ring_steps or self.RING_STEPS)
+        if self.ring_steps < 1:
+            raise ValueError("ring_steps must be >= 1")
+        self.every = max(1, min(int(every), self.ring_steps))
+        self.ring = torch.zeros(self.ring_steps, self.num_envs, 2, dtype=torch.float32, device=engine.device)
+        self.t = 0          # cells written
+        self.copied_to = 0  # cells queued for copy
+        self.first_steps: List[int] = []  # first env step of the cells not yet queued
+        self.pending: List[tuple] = []
+
+    def after_step(self, first_slot: int, first_step: int) -> None:
+        """The rollout step wrote its N rows at ring slots ``first_slot + i``
+        (wrapping); row i is logged at env step ``first_step + i``."""
+        self.engine.q_values_replay(self.replay, first_slot, self.num_envs, next_obs=True,
+                                    out=self.ring[self.t % self.ring_steps])
+        self.t += 1
+        self.first_steps.append(int(first_step))
+        if self.t - self.copied_to >= self.every:
+            self._queue()
+        self._consume(block=False)
+
+    def _queue(self) -> None:
+        n = self.t - self.copied_to
+        if n < 1:
+            return
+        S = self.ring_steps
+        host = torch.empty(n, self.num_envs, 2, dtype=torch.float32, pin_memory=True)
+        a, b = self.copied_to % S, (self.t - 1) % S
+        with torch.cuda.device(self.engine.device):
+            if a <= b:
+                host.copy_(self.ring[a:b + 1], non_blocking=True)
+            else:  # the range wraps the ring
+                k = S - a
+                host[:k].copy_(self.ring[a:], non_blocking=True)
+                host[k:].copy_(self.ring[:b + 1], non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+        # later launches into these cells queue behind this copy on the stream
+        self.pending.append((host, ev, self.first_steps))
+        self.first_steps = []
+        self.copied_to = self.t
+
+    def _consume(self, block: bool) -> None:
+        while self.pending:
+            host, ev, firsts = self.pending[0]
+            if not block and not ev.query():
+                return
+            ev.synchronize()
+            for cell, first in zip(host.tolist(), firsts):
+                for i, (q1, q2) in enumerate(cell):
+                    self.logger.log_q_values(q1, q2, first + i)
+            self.pending.pop(0)
+
+    def finish(self) -> None:
+        """Blocking: every value recorded up to now."""
+        self._queue()
+        self._consume(block=True)
+
+
+__all__ = ["DeviceVectorEnv", "DeviceQValueLog", "EpisodeDrain", "KINDS", "kind_name"]

@@ -301,6 +301,61 @@ class SacEngine:
                                           bool(want_log_pi and eps is not None))
         return (act, lp if lp.numel() else None) if want_log_pi else act
 
+    def _q_out(self, out: torch.Tensor, n: int) -> None:
+        same_device = out.is_cuda and self.device.index in (None, out.device.index)  # "cuda" is the current device
+        if not (same_device and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (n, 2)):
+            raise ValueError(f"out must be a contiguous float32 [{n}][2] tensor on {self.device}")
+
+    def q_values(self, obs: torch.Tensor, act: torch.Tensor, target: bool = False,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Q1 and Q2 of n (state, action) rows -> [n][2] fp32, ONE launch of the
+        critic-evaluation kernel on the packed copies the training kernels
+        use (``target``: the target critics).  Row strides are taken from the
+        tensors, so a column view of a wider table is read in place.  ``out``:
+        a contiguous [n][2] device tensor to write into instead of a new one.
+        Asynchronous on the current stream; no synchronisation."""
+        obs = obs.to(self.device, torch.float32)
+        act = act.to(self.device, torch.float32)
+        if obs.dim() != 2 or act.dim() != 2 or obs.shape[1] != self.cfg.obs_dim or act.shape[1] != self.cfg.act_dim \
+                or obs.shape[0] != act.shape[0]:
+            raise ValueError(f"q_values takes obs [n][{self.cfg.obs_dim}] and act [n][{self.cfg.act_dim}]; got "
+                             f"{tuple(obs.shape)} and {tuple(act.shape)}")
+        if obs.shape[1] > 1 and obs.stride(1) != 1 or obs.shape[0] > 1 and obs.stride(0) < obs.shape[1]:
+            obs = obs.contiguous()
+        if act.shape[1] > 1 and act.stride(1) != 1 or act.shape[0] > 1 and act.stride(0) < act.shape[1]:
+            act = act.contiguous()
+        n = obs.shape[0]
+        with torch.cuda.device(self.device):
+            if out is None:
+                return self.ops.q_values(self.handle.value, obs, act, bool(target))
+            self._q_out(out, n)
+            if n:
+                so = obs.stride(0) if n > 1 else obs.shape[1]
+                sa = act.stride(0) if n > 1 else act.shape[1]
+                E.check(self.lib.sac_q_values(self.handle, E.ptr(obs), so, E.ptr(act), sa, n, int(bool(target)),
+                                              E.ptr(out), self._stream()))
+        return out
+
+    def q_values_replay(self, replay, first_slot: int, n: int, next_obs: bool = True, target: bool = False,
+                        out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Q1 and Q2 of (next_obs if ``next_obs`` else obs, act) of ``n``
+        consecutive ring slots of ``replay`` from ``first_slot``, wrapping at
+        its capacity -> [n][2] fp32.  ONE launch that reads the replay storage
+        in place (records or struct-of-arrays); no gather, no copy, no
+        synchronisation."""
+        replay.flush()
+        n, first_slot = int(n), int(first_slot)
+        if not 0 <= first_slot < replay.capacity or not 1 <= n <= replay.capacity:
+            raise ValueError(f"q_values_replay: first_slot {first_slot} / n {n} outside a ring of {replay.capacity}")
+        with torch.cuda.device(self.device):
+            if out is None:
+                return self.ops.q_values_replay(self.handle.value, replay.storage, replay.state, replay.layout_spec,
+                                                first_slot, n, bool(next_obs), bool(target))
+            self._q_out(out, n)
+            E.check(self.lib.sac_q_values_replay(self.handle, ctypes.byref(replay.desc), first_slot, n,
+                                                 int(bool(next_obs)), int(bool(target)), E.ptr(out), self._stream()))
+        return out
+
     def rollout_step(self, envs, replay, deterministic: bool = False, store: bool = True) -> None:
         """One vector step of a ``sac.device_envs.DeviceVectorEnv`` in ONE
         launch: the policy's actions for the envs' current observations (the

@@ -23,7 +23,9 @@ gymnasium id (the reference's own envs).
 ``--device-envs`` (probe envs only) keeps the environments on the device
 (``sac.device_envs.DeviceVectorEnv``) and trains through
 ``SAC.run_device_training_loop``: act -> step -> store is one launch per
-vector step, with no per-step host<->device traffic.
+vector step, with no per-step host<->device traffic.  A config with
+``logger.log_q_values: true`` runs there unchanged: the per-env-step Q values
+are evaluated and logged on the device (``device_q_values=True``).
 """
 from __future__ import annotations
 
@@ -106,8 +108,12 @@ def train_replica(config: dict, make_env: Callable[[], object], num_envs: int, e
         raise E.EngineUnavailable(f"replica {rank}: replica training needs the HIP engine on an MI355X "
                                   f"(train.device={cfg['train'].get('device')!r}); there is no CPU fallback")
     agg = ReplicaAggregator(agent.engine, every)
-    loop = agent.run_device_training_loop if device_envs else agent.run_vectorized_training_loop
-    metrics = loop(env_steps, callback=agg, seed=cfg["train"]["seed"])
+    if device_envs:
+        # a config with logger.log_q_values (every probe config of the reference) logs them on the device
+        metrics = agent.run_device_training_loop(env_steps, callback=agg, seed=cfg["train"]["seed"],
+                                                 device_q_values=True)
+    else:
+        metrics = agent.run_vectorized_training_loop(env_steps, callback=agg, seed=cfg["train"]["seed"])
     return {"metrics": metrics, "aggregate": agg.finish()}
 
 
