@@ -116,7 +116,7 @@ def oracle_fresh_state(c, seed=3):
     return O.SacState.fresh(*mlps, hp, c["act"]), hp
 
 
-def build_engine(c, precision, seed=3, device=None, layout=None):
+def build_engine(c, precision, seed=3, device=None, layout=None, replay=None):
     """Engine + synthetic replay of a config dict, as bench.build_engine builds
     them (same seeding, hyper-parameters and replay rows), with the fields that
     one leaves at its defaults:
@@ -131,6 +131,9 @@ def build_engine(c, precision, seed=3, device=None, layout=None):
       replay_seed: their seed, default the engine's);
       layout (kernel layout overrides of sac.engine.SacEngine; the `layout`
       argument is merged over it).
+    replay: a caller's ReplayBuffer, returned as it is in place of the
+    synthetic one (a ring state of tests/_ring.py, say; c's capacity is then
+    not used).
     The engine gains `.split` (sac_engine_uses_split, include/
     sac_engine_testing.h) next to .roles / .pairs / .wide.  Returns (engine,
     replay, c)."""
@@ -151,6 +154,9 @@ def build_engine(c, precision, seed=3, device=None, layout=None):
                     betas=tuple(h["betas"]), eps=h["adam_eps"], target_entropy=h["target_entropy"], layout=lay or None)
     eng.lib.sac_engine_uses_split.argtypes = [ctypes.c_void_p]
     eng.split = bool(eng.lib.sac_engine_uses_split(eng.handle))
+    if replay is not None:
+        assert (replay.obs_dim, replay.act_dim) == (c["obs"], c["act"])
+        return eng, replay, c
     rb = ReplayBuffer(c["capacity"], device=device, obs_dim=c["obs"], act_dim=c["act"])
     if c.get("done_p") is None:
         bench.synthetic_replay(rb, c["capacity"], c["obs"], c["act"], seed)
