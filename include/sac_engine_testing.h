@@ -64,8 +64,9 @@ int sac_debug_rollout_eps_host(uint64_t seed, uint64_t t, int32_t n, int32_t act
  * output word k % 4: u = (word >> 8) * 2^-24, obs = 2u - 1 in [-1, 1). */
 int sac_debug_env_obs_host(uint64_t seed, uint64_t t, int32_t which, int32_t n, int32_t obs_dim, float *out);
 /* A host-only engine: the validated config and no device state (no HIP call is
- * made).  For the argument checks of sac_q_values / sac_q_values_replay on a
- * machine without a device: with valid arguments they return SAC_E_INVALID
+ * made).  For the argument checks of the forward-only entry points --
+ * sac_q_values, sac_q_values_replay, sac_policy_act and sac_rollout_step -- on
+ * a machine without a device: with valid arguments they return SAC_E_INVALID
  * ("no device state") where the launch would be.  Pass it to no other entry
  * point but sac_engine_destroy. */
 int sac_debug_engine_host(const sac_engine_config *cfg, sac_engine **out);

@@ -1555,9 +1555,35 @@ int sac_engine_train_graph(sac_engine* e, const sac_replay* rb, int32_t n_steps,
   return SAC_OK;
 }
 
+// The forward-only kernels (policy_act, rollout_step, q_values) run one network
+// on the row-tile LDS layout: plan() sizes ld / ldo over all five networks, so
+// this holds for every engine create accepts; it is checked where it is relied on.
+static bool rowtile_fits(const sac_engine* e, int net) {
+  const EngineDev& h = e->h;
+  const NetDev& q = h.net[net];
+  for (int l = 0; l < q.L; ++l) {
+    if (q.l[l].Kp + 4 > h.ld) return false;
+    if (l == q.L - 1 ? q.l[l].Np + 4 > h.ldo : q.l[l].Np + 4 > h.ld) return false;
+  }
+  const size_t ends[4] = {(size_t)h.o_X + SAC_ROWS * h.ld, (size_t)h.o_Y + SAC_ROWS * h.ld,
+                          (size_t)h.o_out + SAC_ROWS * h.ldo, (size_t)h.o_outp + SAC_ROWS * h.ldo};
+  return *std::max_element(ends, ends + 4) * 4 <= e->lds_bytes && e->lds_bytes <= 160 * 1024;
+}
+
+// what a launch of the policy's forward-only kernels needs of the engine
+static int check_policy_forward(const sac_engine* e, const char* who) {
+  if (!e->d)
+    return fail(SAC_E_INVALID, std::string(who) + ": the engine has no device state (host-only test engine)");
+  if (!rowtile_fits(e, NET_PI))
+    return fail(SAC_E_INVALID, std::string(who) + ": the row-tile LDS layout does not hold the policy's layer widths");
+  return SAC_OK;
+}
+
 int sac_policy_act(sac_engine* e, const float* obs, int32_t n, const float* eps, float* action, float* log_pi,
                    void* stream) {
   if (!e || !obs || !action || n < 1) return fail(SAC_E_INVALID, "bad policy_act arguments");
+  int rc = check_policy_forward(e, "policy_act");
+  if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
   const int blocks = (n + SAC_ROWS - 1) / SAC_ROWS;
   if (e->cfg.precision == SAC_PREC_BF16)
@@ -1568,25 +1594,10 @@ int sac_policy_act(sac_engine* e, const float* obs, int32_t n, const float* eps,
   return SAC_OK;
 }
 
-// The critics run on the policy kernel's row-tile LDS layout: plan() sizes ld /
-// ldo over all five networks, so this holds for every engine create accepts; it
-// is checked where it is relied on.
-static bool q_rowtile_fits(const sac_engine* e) {
-  const EngineDev& h = e->h;
-  const NetDev& q = h.net[NET_Q1];
-  for (int l = 0; l < q.L; ++l) {
-    if (q.l[l].Kp + 4 > h.ld) return false;
-    if (l == q.L - 1 ? q.l[l].Np + 4 > h.ldo : q.l[l].Np + 4 > h.ld) return false;
-  }
-  const size_t ends[4] = {(size_t)h.o_X + SAC_ROWS * h.ld, (size_t)h.o_Y + SAC_ROWS * h.ld,
-                          (size_t)h.o_out + SAC_ROWS * h.ldo, (size_t)h.o_outp + SAC_ROWS * h.ldo};
-  return *std::max_element(ends, ends + 4) * 4 <= e->lds_bytes && e->lds_bytes <= 160 * 1024;
-}
-
 // every argument validated by the caller; one launch, no host-side state
 static int launch_q_values(sac_engine* e, const QRows& rows, int32_t n, int32_t target, float* q, void* stream) {
   if (!e->d) return fail(SAC_E_INVALID, "q_values: the engine has no device state (host-only test engine)");
-  if (!q_rowtile_fits(e))
+  if (!rowtile_fits(e, NET_Q1))
     return fail(SAC_E_INVALID, "q_values: the row-tile LDS layout does not hold the critics' layer widths");
   const dim3 grid((unsigned)((n + SAC_ROWS - 1) / SAC_ROWS), 2);
   hipStream_t s = (hipStream_t)stream;
@@ -1684,6 +1695,8 @@ int sac_rollout_step(sac_engine* e, const sac_envs* envs, const sac_replay* rb, 
   if (!e) return fail(SAC_E_INVALID, "null engine");
   if (e->cfg.obs_dim != envs->cfg.obs_dim || e->cfg.act_dim != SAC_ENV_ACT_DIM)
     return fail(SAC_E_INVALID, "engine dims do not match the environments (act_dim 1)");
+  rc = check_policy_forward(e, "rollout_step");
+  if (rc) return rc;
   const int64_t new_size = std::min(cap, size_host + n);
   const int64_t new_pos = (pos_host + n) % cap;
   const int blocks = (int)((n + SAC_ROWS - 1) / SAC_ROWS);

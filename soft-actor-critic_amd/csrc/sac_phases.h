@@ -2396,9 +2396,9 @@ __global__ void __launch_bounds__(SAC_THREADS) sac_policy_act_kernel(const Engin
       const float sd = expf(ls);
       const float z = mu + e * sd;
       action[(size_t)b * A + j] = tanhf(z) * scale;
-      const float diff = z - mu;
-      const float var = sd * sd;
-      lp_sum += -(diff * diff) / (2.f * var) - logf(sd) - HALF_LOG_2PI;
+      // (z - mu)^2 / (2 sd^2) = e^2 / 2 and log sd = ls, taken from e and ls themselves: z - mu
+      // loses e * sd to rounding once sd is far below |mu| (at the lower clamp, sd = e^-20, all of it)
+      lp_sum += -0.5f * e * e - ls - HALF_LOG_2PI;
       corr_sum += 2.f * ((LOG2F - z) - softplus20(-2.f * z));
     }
     if (eps && log_pi) log_pi[b] = lp_sum - corr_sum;

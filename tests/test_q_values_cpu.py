@@ -3,7 +3,8 @@ their ctypes signatures are the header's, and every argument check of
 sac_q_values / sac_q_values_replay returns SAC_E_INVALID with its message before
 any HIP call.  The checks that compare against the engine's dims run on a
 host-only engine (include/sac_engine_testing.h sac_debug_engine_host: the
-validated config, no device state)."""
+validated config, no device state).  sac_policy_act and sac_rollout_step, the
+other two forward-only entry points, refuse that engine the same way."""
 import ctypes
 import os
 import re
@@ -183,6 +184,64 @@ def test_q_values_replay_valid_arguments_reach_the_launch(lib, host_engine, stri
     rb = _replay(E, stride=stride)
     assert lib.sac_q_values_replay(host_engine, ctypes.byref(rb), first, n, use_next, target, PTR, None) == INVALID
     assert "no device state" in _err(lib)
+
+
+# ---------------------------------------------------------------- sac_policy_act / sac_rollout_step
+@pytest.mark.parametrize("n,eps,log_pi", [(1, None, None), (33, PTR, None), (16, PTR, PTR)])
+def test_policy_act_valid_arguments_reach_the_launch(lib, host_engine, n, eps, log_pi):
+    """The policy kernel is guarded like the critic kernel: a host-only engine is refused before the launch."""
+    assert lib.sac_policy_act(host_engine, PTR, n, eps, PTR, log_pi, None) == INVALID
+    assert "policy_act" in _err(lib) and "no device state" in _err(lib)
+
+
+def test_policy_act_still_rejects_bad_arguments_first(lib, host_engine):
+    for args in ((None, PTR, 4, None, PTR), (host_engine, None, 4, None, PTR), (host_engine, PTR, 4, None, None),
+                 (host_engine, PTR, 0, None, PTR)):
+        assert lib.sac_policy_act(*args, None, None) == INVALID and "bad policy_act arguments" in _err(lib)
+
+
+def _envs(E, kind=2, n=17, obs=5, null=()):
+    d = E.EnvsDesc()
+    d.cfg.kind, d.cfg.num_envs, d.cfg.obs_dim, d.cfg.max_steps = kind, n, obs, 4
+    for field in ("obs", "step", "ep_length", "pos", "ep_return", "episodes"):
+        setattr(d, field, None if field in null else PTR)
+    d.ring_steps = 8
+    return d
+
+
+@pytest.fixture()
+def host_engine_act1(lib):
+    """A host-only engine of obs 5 / act 1, the fused rollout step's action width."""
+    from sac import _engine as E
+
+    h = ctypes.c_void_p()
+    cfg = _config(E, obs=5, act=1, hidden=(64, 64))
+    assert lib.sac_debug_engine_host(ctypes.byref(cfg), ctypes.byref(h)) == 0 and h.value
+    yield h
+    lib.sac_engine_destroy(h)
+
+
+@pytest.mark.parametrize("size,pos,deterministic,store", [(0, 0, 0, 1), (64, 47, 1, 1), (17, 17, 0, 0)])
+def test_rollout_step_valid_arguments_reach_the_launch(lib, host_engine_act1, size, pos, deterministic, store):
+    from sac import _engine as E
+
+    ev, rb = _envs(E), _replay(E, cap=64, obs=5, act=1, stride=8)
+    rc = lib.sac_rollout_step(host_engine_act1, ctypes.byref(ev), ctypes.byref(rb), size, pos, 1, deterministic, store,
+                              None)
+    assert rc == INVALID and "rollout_step" in _err(lib) and "no device state" in _err(lib)
+
+
+def test_rollout_step_still_rejects_bad_arguments_first(lib, host_engine, host_engine_act1):
+    from sac import _engine as E
+
+    ev, rb = _envs(E), _replay(E, cap=64, obs=5, act=1, stride=8)
+    call = lambda e, ev, rb, size=0, pos=0: lib.sac_rollout_step(  # noqa: E731
+        e, ctypes.byref(ev), ctypes.byref(rb), size, pos, 1, 0, 1, None)
+    assert call(host_engine_act1, _envs(E, null=("episodes",)), rb) == INVALID and "episode ring" in _err(lib)
+    assert call(host_engine_act1, ev, _replay(E, cap=16, obs=5, act=1)) == INVALID and "exceeds the replay" in _err(lib)
+    assert call(host_engine_act1, ev, rb, pos=64) == INVALID and "out of range" in _err(lib)
+    assert call(None, ev, rb) == INVALID and "null engine" in _err(lib)
+    assert call(host_engine, ev, rb) == INVALID and "engine dims do not match" in _err(lib)  # act 3
 
 
 # ---------------------------------------------------------------- torch ops
