@@ -289,6 +289,54 @@ __device__ __forceinline__ void gemm_ksplit(const lf* __restrict__ A, int lda, c
   __syncthreads();
 }
 
+// ---------------------------------------------------------------------------- narrow steps
+// Phase C's critic layer 2 in fp32 (N = 1: one W2 row).  As a k-split GEMM it
+// costs an LDS write of its input, a barrier, MFMAs on a tile that is 15/16
+// padding, an LDS write of the per-wave partials, a barrier and an LDS
+// reduction.  Fused (SAC_NARROW_FUSED), the dot product is formed in layer 1's
+// epilogue: the lane multiplies its column's four row values by the column's
+// W2 element from the fp32 master, rows16_sum adds the 16 lanes of a column
+// group in a fixed order, one value per (wave, row) goes to LDS, and after the
+// barrier that follows layer 1 anyway the waves are added in wave order.  Only
+// the summation order differs from the k-split path, which still runs for a
+// hidden activation other than ReLU / identity, for N != 1 and in bf16 (its
+// layer 2 multiplies bf16-rounded activations).  Same-box A/B at C2 fp32:
+// +0.85% steps/s (C 17.4 -> 16.5 us).  Measured and dropped: the same fusion
+// of phase A's layer 2 (-0.7%), of phase C's dX0 of the action columns into
+// layer 1's dX epilogue (-3%; A scattered master loads per dY0 column and 4 A
+// accumulators per lane), pi(s')'s head writing a~' straight into X (neutral):
+// profiles/ab_narrow_items.txt.
+// SAC_NARROW_SMALL: phase C changes that move no float operation -- the critic
+// roles' s / a~ go global -> register -> X with one barrier (+1.0%), and pi
+// computes every head-backward term that does not need the critics' da before
+// it polls for them (+1.0%).  =0 for both: the earlier path.
+#ifndef SAC_NARROW_FUSED
+#define SAC_NARROW_FUSED 1
+#endif
+#ifndef SAC_NARROW_SMALL
+#define SAC_NARROW_SMALL 1
+#endif
+
+// p[i]: the lane's value for its row i (i < 4) -- a gemm_hs epilogue's lane
+// (c = lane & 15, g = lane >> 4) holds rows 4 g + i of column c.  Returns the
+// sum over the 16 lanes of the column group for row 4 g + (c >> 2), the same
+// bits in the four lanes that share c >> 2.  Rows are exchanged first (xor 8,
+// xor 4: a lane keeps half of its rows and takes the peer's partials of
+// them), so 5 cross-lane moves instead of 16.  The order of additions is
+// fixed by the lane numbers alone.
+__device__ __forceinline__ float rows16_sum(const float (&p)[4]) {
+  const int c = threadIdx.x & 15;
+  const bool b3 = c & 8, b2 = c & 4;
+  const float m0 = b3 ? p[2] : p[0], o0 = b3 ? p[0] : p[2];
+  const float m1 = b3 ? p[3] : p[1], o1 = b3 ? p[1] : p[3];
+  const float q0 = m0 + __shfl_xor(o0, 8, 64), q1 = m1 + __shfl_xor(o1, 8, 64);
+  const float m = b2 ? q1 : q0, o = b2 ? q0 : q1;
+  float v = m + __shfl_xor(o, 4, 64);
+  v += __shfl_xor(v, 1, 64);
+  v += __shfl_xor(v, 2, 64);
+  return v;
+}
+
 // ---------------------------------------------------------------------------- phase A
 template <typename T>
 __device__ __forceinline__ void target_critic_split_body(const EngineDev* __restrict__ Ep, const sac_replay& rb,
@@ -928,21 +976,41 @@ __device__ __forceinline__ void actor_split_body(const EngineDev* __restrict__ E
     // the W2 (fp32 master) element of this thread's column n = tid % HQ of the unit-seed backward
     static_assert(SAC_THREADS % HQ == 0, "one W2 column per thread in the unit-seed loop");
     const float w2n = GPC(float, net.P + L2.w_off)[h * HQ + tid % HQ];
-    for (int i = tid; i < R * O; i += SAC_THREADS) sB[i] = GPC(float, E.s_st)[(size_t)r0 * O + i];
-    for (int i = tid; i < R * A; i += SAC_THREADS) aB[i] = GPC(float, E.a_st)[(size_t)r0 * A + i];
-    if (SAC_KS_C) {  // behind the inputs: waiting for s / a~ must not wait for these (loads retire in order)
-      ks_issue<T, decltype(kc2)::MAXC>(kc2, w2);
+    const int act = net.hid_act;
+    const int Kp0 = L0.Kp;
+    // fp32, N = 1: layer 2 (the partial q) fused into layer 1's epilogue, see rows16_sum
+    const bool relu_id = act == ACT_RELU || act == ACT_ID;
+    const bool fuse2 = SAC_NARROW_FUSED && sizeof(T) == 4 && L2.N == 1 && relu_id;
+    const int lane = tid & 63, wv = wave_id();
+    float w2l = 0.f;
+    // one thread per element of X when it fits: s / a~ go global -> register -> X, one barrier
+    const bool x_direct = SAC_NARROW_SMALL && R * Kp0 <= SAC_THREADS;
+    float xv = 0.f;
+    if (x_direct) {
+      const int r = tid / Kp0, k = tid % Kp0;
+      if (tid < R * Kp0 && k < O + A)
+        xv = k < O ? GPC(float, E.s_st)[(size_t)r0 * O + r * O + k] : GPC(float, E.a_st)[(size_t)r0 * A + r * A + (k - O)];
+    } else {
+      for (int i = tid; i < R * O; i += SAC_THREADS) sB[i] = GPC(float, E.s_st)[(size_t)r0 * O + i];
+      for (int i = tid; i < R * A; i += SAC_THREADS) aB[i] = GPC(float, E.a_st)[(size_t)r0 * A + i];
+    }
+    // behind the inputs: waiting for s / a~ must not wait for these (loads retire in order)
+    if (fuse2) w2l = GPC(float, net.P + L2.w_off)[h * HQ + (wv < w1.NT ? wv : 0) * 16 + (lane & 15)];
+    if (SAC_KS_C) {
+      if (!fuse2) ks_issue<T, decltype(kc2)::MAXC>(kc2, w2);
       if (sizeof(T) == 2) ks_issue<T, decltype(kc0)::MAXC>(kc0, wt0);  // fp32: after layer 1 (its held W1 part is dead then; from here it spilled)
     }
-    __syncthreads();
-    const int Kp0 = L0.Kp;
-    for (int i = tid; i < R * Kp0; i += SAC_THREADS) {
-      const int r = i / Kp0, k = i % Kp0;
-      Xb[r * ld + k] = k < O ? sB[r * O + k] : (k < O + A ? aB[r * A + (k - O)] : 0.f);
+    if (x_direct) {
+      if (tid < R * Kp0) Xb[(tid / Kp0) * ld + tid % Kp0] = xv;
+    } else {
+      __syncthreads();
+      for (int i = tid; i < R * Kp0; i += SAC_THREADS) {
+        const int r = i / Kp0, k = i % Kp0;
+        Xb[r * ld + k] = k < O ? sB[r * O + k] : (k < O + A ? aB[r * A + (k - O)] : 0.f);
+      }
     }
     __syncthreads();
     STAMP(33);
-    const int act = net.hid_act;
     gemm_hs<T, 2, HC0, false>(Xb, ld, w0, &h0, [&](int j, int col, const f32x4& acc) {
       const bool nv = col < L0.N;
       const float bn = h0.b[j];
@@ -958,18 +1026,33 @@ __device__ __forceinline__ void actor_split_body(const EngineDev* __restrict__ E
     __syncthreads();
     gemm_hs<T, 1, NCH_H, false>(H0, ld, w1, &h1, [&](int j, int col, const f32x4& acc) {
       const float bn = h1.b[j];
+      float q2[4];
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int r = (((threadIdx.x & 63) >> 4) << 2) + i;
         const float p = acc[i] + bn;
+        const float hv = act == ACT_RELU ? (p > 0.f ? p : 0.f) : p;
         P1[r * ldp1 + col] = p;
-        H1[r * ldh1 + col] = act == ACT_RELU ? (p > 0.f ? p : 0.f) : p;
+        if (!fuse2) H1[r * ldh1 + col] = hv;
+        q2[i] = hv * w2l;
+      }
+      if (fuse2) {  // uniform: this wave's partial q of its 16 columns, one value per row
+        const float s2 = rows16_sum(q2);
+        if ((lane & 3) == 0) red[wv * R + ((lane >> 4) << 2) + ((lane & 15) >> 2)] = s2;
       }
     });
     if (SAC_KS_C && sizeof(T) == 4) ks_issue<T, decltype(kc0)::MAXC>(kc0, wt0);
     if (act != ACT_RELU && act != ACT_ID) act_pass_fwd<R>(H1, ldh1, HQ >> 4, act);
     __syncthreads();
-    gemm_ksplit<T, false, decltype(kc2)::MAXC>(H1, ldh1, w2, red, outB, ldo, &kc2);  // partial q
+    if (fuse2) {  // the waves' partials, in wave order; outB[r][0] is read by thread r only
+      if (tid < R) {
+        float s = red[tid];
+        for (int w = 1; w < w1.NT && w < SAC_NW; ++w) s += red[w * R + tid];
+        outB[tid * ldo] = s;
+      }
+    } else {
+      gemm_ksplit<T, false, decltype(kc2)::MAXC>(H1, ldh1, w2, red, outB, ldo, &kc2);  // partial q
+    }
     STAMP(36 + qi);
     // unit-seed backward down to a~ (the pi role applies the min-Q weights and act'(q))
     {
@@ -1045,6 +1128,33 @@ __device__ __forceinline__ void actor_split_body(const EngineDev* __restrict__ E
     for (int q = 0; q < 4; ++q) hsv[q] = ldf<false>(hs + q * A + tid % A);
   }
   const float bq1 = ldf<false>(E.net[NET_Q1].l[2].bias), bq2 = ldf<false>(E.net[NET_Q2].l[2].bias);
+  // Every term of the head backward (below) that does not depend on the critics'
+  // da, computed while the role waits for them: the same operations in the
+  // same order, only earlier.  hb_*: this thread's (row, action dim).
+  float hb_omt = 0.f, hb_sp = 0.f, hb_gstd = 0.f, hb_gdiff = 0.f, hb_sd = 0.f;
+  if (SAC_NARROW_SMALL) {
+    if (tid < R * A) {
+      const bool v = tid / A < nvalid;
+      const float gl = v ? alpha32 * (1.0f / (float)B) : 0.f;
+      const float lo = E.ls_min, hi = E.ls_max;
+      const float mu = hsv[0], lsr = hsv[1], z = hsv[2];
+      const float ls = lsr < lo ? lo : (lsr > hi ? hi : lsr);
+      const float sd = expf(ls);
+      const float t = tanhf(z);
+      const float diff = z - mu, var = sd * sd;
+      hb_omt = 1.f - t * t;
+      hb_sp = (-gl) * 2.f * (-1.f + 2.f * softplus20_grad(-2.f * z));
+      const float two_var = 2.f * var;
+      const float g_sq = -gl / two_var;
+      const float g_twovar = gl * (diff * diff) / (two_var * two_var);
+      const float g_var = 2.f * g_twovar;
+      hb_gstd = 2.f * sd * g_var - gl / sd;
+      hb_gdiff = 2.f * diff * g_sq;
+      hb_sd = sd;
+    }
+    const int NOp = L2.Np, pad = NOp - 2 * A;
+    for (int i = tid; i < R * pad; i += SAC_THREADS) goutB[(i / pad) * ldo + 2 * A + i % pad] = 0.f;
+  }
   __syncthreads();
   STAMP(34);
   // combine the critics' unit-seed partials with the min-Q weights (L_pi = mean(alpha logpi - min Q))
@@ -1174,7 +1284,23 @@ __device__ __forceinline__ void actor_split_body(const EngineDev* __restrict__ E
   STAMP(39);
   // squashed-Gaussian head backward (models.py:79-87), one lane per (row, action dim)
   static_assert(SAC_ROWS * 32 <= SAC_THREADS, "one (row, action dim) per thread");
-  if (tid < R * A) {
+  if (SAC_NARROW_SMALL) {
+    if (tid < R * A) {  // only the terms that need the critics' da are left (hb_*: before the poll)
+      const int r = tid / A, j = tid % A;
+      const bool v = r < nvalid;
+      const float lo = E.ls_min, hi = E.ls_max, scale = E.scale;
+      const float lsr = hsv[1], e = hsv[3];
+      float g_z = (gaB[r * A + j] * scale) * hb_omt;
+      g_z = g_z + hb_sp;
+      g_z = g_z + hb_gdiff;
+      const float g_mu = -hb_gdiff + g_z;
+      const float g_std = hb_gstd + g_z * e;
+      const float g_ls = g_std * hb_sd;
+      const bool in_range = (lsr >= lo) && (lsr <= hi);
+      goutB[r * ldo + j] = v ? g_mu : 0.f;
+      goutB[r * ldo + A + j] = (v && in_range) ? g_ls : 0.f;
+    }
+  } else if (tid < R * A) {
     const int i = tid;
     const int r = i / A, j = i % A;
     const bool v = r < nvalid;
@@ -1201,7 +1327,7 @@ __device__ __forceinline__ void actor_split_body(const EngineDev* __restrict__ E
     goutB[r * ldo + j] = v ? g_mu : 0.f;
     goutB[r * ldo + A + j] = (v && in_range) ? g_ls : 0.f;
   }
-  {
+  if (!SAC_NARROW_SMALL) {
     const int NOp = L2.Np, pad = NOp - 2 * A;
     for (int i = tid; i < R * pad; i += SAC_THREADS) goutB[(i / pad) * ldo + 2 * A + i % pad] = 0.f;
   }
