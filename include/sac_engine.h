@@ -333,6 +333,49 @@ int sac_envs_step(const sac_envs *envs, const float *actions, uint64_t t, float 
 int sac_rollout_step(sac_engine *e, const sac_envs *envs, const sac_replay *rb, int64_t size_host,
                      int64_t pos_host, uint64_t t, int32_t deterministic, int32_t store, void *stream);
 
+/* ---- device loop cursor ----------------------------------------------------
+ * A caller-owned device array int64 cursor[2][4]; slot p holds {replay size,
+ * next write slot, vector steps taken t, reserved 0}.  A launch that takes
+ * (cursor, parity) reads slot `parity`; the rollout step also writes the
+ * advanced cursor to slot parity ^ 1, so consecutive vector steps alternate
+ * parity and no launch reads a word it writes.  The caller seeds slot 0 (or the
+ * slot of its first parity) from its host mirrors; nothing else on the host
+ * has to follow the loop, which is what lets sac_engine_loop_graph replay whole
+ * iterations from one hipGraph. */
+
+/* sac_rollout_step with (size, pos, t) read from cursor[parity]: the vector
+ * step's RNG step is t + 1.  Writes cursor[parity ^ 1] = {min(capacity, size +
+ * num_envs), (pos + num_envs) % capacity, t + 1, 0} and rb->state as
+ * sac_rollout_step does; store = 0 writes {size, pos, t + 1, 0} and leaves the
+ * replay alone.  A slot whose (size, pos) lie outside the ring (never seeded)
+ * makes the launch a no-op. */
+int sac_rollout_step_dev(sac_engine *e, const sac_envs *envs, const sac_replay *rb, int64_t *cursor,
+                         int32_t parity, int32_t deterministic, int32_t store, void *stream);
+
+/* sac_q_values_replay over the n rows written by the vector step whose
+ * pre-step cursor is cursor[parity] (first slot = that slot's pos, wrapping at
+ * capacity), into cell (t + 1) % q_ring_steps of q_ring[q_ring_steps][n][2]. */
+int sac_q_values_replay_dev(sac_engine *e, const sac_replay *rb, const int64_t *cursor, int32_t parity,
+                            int32_t n, int32_t use_next_obs, int32_t target, float *q_ring,
+                            int32_t q_ring_steps, void *stream);
+
+/* k_steps (even, >= 2) iterations of the device-resident loop as ONE hipGraph,
+ * replayed n_replays times (0: capture only).  Iteration j is the rollout step
+ * at parity j & 1 (sampled actions, store = 1), grad_steps_host[j] gradient
+ * steps (device sampler and device eps, as sac_engine_train_graph; the caller
+ * guarantees batch <= size by then), and, if q_ring is not NULL, the critic
+ * evaluation of (next_obs, act) of the step's num_envs rows into its cell of
+ * q_ring[q_ring_steps][num_envs][2].  Every replay starts at parity 0: the
+ * caller seeds cursor[0] before the first replay of a run, and after any vector
+ * step it issued another way.  The graph is cached on (envs, rb, cursor,
+ * k_steps, the gradient-step counts, q_ring, q_ring_steps) -- a call with
+ * another key captures again -- apart from sac_engine_train_graph's cache.
+ * Replaces: k_steps iterations of SAC.run_vectorized_training_loop
+ * (sac/agent.py:343-364 of the reference per environment). */
+int sac_engine_loop_graph(sac_engine *e, const sac_envs *envs, const sac_replay *rb, int64_t *cursor,
+                          int32_t k_steps, const int32_t *grad_steps_host, float *q_ring,
+                          int32_t q_ring_steps, int32_t n_replays, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -347,6 +347,18 @@ struct sac_engine {
   int gchunk = 0;
   sac_replay gkey{};
   hipStream_t cap = nullptr;
+  // loop-graph cache (sac_engine_loop_graph): its own graph, exec and key
+  struct LoopKey {
+    sac_envs envs;
+    sac_replay rb;
+    int64_t* cursor;
+    float* q_ring;
+    int32_t q_ring_steps;
+    std::vector<int32_t> grad;  // gradient steps after each rollout: its size is k_steps
+  };
+  hipGraphExec_t lgexec = nullptr;
+  hipGraph_t lgraph = nullptr;
+  LoopKey lkey{};
 };
 
 static inline int rup(int x, int m) { return (x + m - 1) / m * m; }
@@ -1176,6 +1188,7 @@ static void set_lds_attrs(size_t bytes) {
   (void)hipFuncSetAttribute((const void*)sac_actor<T, true>, hipFuncAttributeMaxDynamicSharedMemorySize, b);
   (void)hipFuncSetAttribute((const void*)sac_policy_act_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, b);
   (void)hipFuncSetAttribute((const void*)sac_rollout_step_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, b);
+  (void)hipFuncSetAttribute((const void*)sac_rollout_step_dev_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, b);
   (void)hipFuncSetAttribute((const void*)sac_q_values_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, b);
   (void)hipFuncSetAttribute((const void*)sac_target_critic_split<T>, hipFuncAttributeMaxDynamicSharedMemorySize, b);
   (void)hipFuncSetAttribute((const void*)sac_target_critic_pairs<T>, hipFuncAttributeMaxDynamicSharedMemorySize, b);
@@ -1510,6 +1523,8 @@ void sac_engine_destroy(sac_engine* e) {
   if (!e) return;
   if (e->gexec) (void)hipGraphExecDestroy(e->gexec);
   if (e->graph) (void)hipGraphDestroy(e->graph);
+  if (e->lgexec) (void)hipGraphExecDestroy(e->lgexec);
+  if (e->lgraph) (void)hipGraphDestroy(e->lgraph);
   if (e->cap) (void)hipStreamDestroy(e->cap);
   delete e;
 }
@@ -1594,11 +1609,18 @@ int sac_policy_act(sac_engine* e, const float* obs, int32_t n, const float* eps,
   return SAC_OK;
 }
 
-// every argument validated by the caller; one launch, no host-side state
-static int launch_q_values(sac_engine* e, const QRows& rows, int32_t n, int32_t target, float* q, void* stream) {
+// what a launch of the critic-evaluation kernel needs of the engine
+static int check_q_forward(const sac_engine* e) {
   if (!e->d) return fail(SAC_E_INVALID, "q_values: the engine has no device state (host-only test engine)");
   if (!rowtile_fits(e, NET_Q1))
     return fail(SAC_E_INVALID, "q_values: the row-tile LDS layout does not hold the critics' layer widths");
+  return SAC_OK;
+}
+
+// every argument validated by the caller; one launch, no host-side state
+static int launch_q_values(sac_engine* e, const QRows& rows, int32_t n, int32_t target, float* q, void* stream) {
+  const int rc = check_q_forward(e);
+  if (rc) return rc;
   const dim3 grid((unsigned)((n + SAC_ROWS - 1) / SAC_ROWS), 2);
   hipStream_t s = (hipStream_t)stream;
   if (e->cfg.precision == SAC_PREC_BF16)
@@ -1619,7 +1641,24 @@ int sac_q_values(sac_engine* e, const float* obs, int64_t obs_stride, const floa
     return fail(SAC_E_INVALID, "q_values: stride below the field width (obs_stride " + std::to_string(obs_stride) +
                                    " < " + std::to_string(e->cfg.obs_dim) + " or act_stride " +
                                    std::to_string(act_stride) + " < " + std::to_string(e->cfg.act_dim) + ")");
-  return launch_q_values(e, QRows{obs, obs_stride, act, act_stride, 0, 0}, n, target, q, stream);
+  return launch_q_values(e, QRows{obs, obs_stride, act, act_stride, 0, 0, nullptr, 0}, n, target, q, stream);
+}
+
+// The descriptor of n ring rows of a replay buffer (first left 0) once rb's pointers, n >= 1 and
+// capacity >= 1 are known good: the checks the two replay entry points share.
+static int q_replay_rows(sac_engine* e, const sac_replay* rb, int32_t n, int32_t use_next_obs, QRows* rows) {
+  const int64_t cap = rb->capacity;
+  if (n > cap)
+    return fail(SAC_E_INVALID, "q_values_replay: n (" + std::to_string(n) + ") exceeds the replay capacity (" +
+                                   std::to_string(cap) + ")");
+  if (!e) return fail(SAC_E_INVALID, "null engine");
+  if (rb->obs_dim != e->cfg.obs_dim || rb->act_dim != e->cfg.act_dim)
+    return fail(SAC_E_INVALID, "replay dims do not match the engine");
+  const RowStrides rs = row_strides(rb->row_stride, rb->obs_dim, rb->act_dim);
+  if (rs.obs < rb->obs_dim || rs.act < rb->act_dim)
+    return fail(SAC_E_INVALID, "q_values_replay: record stride below the field width");
+  *rows = QRows{use_next_obs ? rb->next_obs : rb->obs, rs.obs, rb->act, rs.act, 0, cap, nullptr, 0};
+  return SAC_OK;
 }
 
 int sac_q_values_replay(sac_engine* e, const sac_replay* rb, int64_t first_slot, int32_t n, int32_t use_next_obs,
@@ -1631,17 +1670,37 @@ int sac_q_values_replay(sac_engine* e, const sac_replay* rb, int64_t first_slot,
   if (cap < 1 || first_slot < 0 || first_slot >= cap)
     return fail(SAC_E_INVALID, "q_values_replay: first_slot (" + std::to_string(first_slot) +
                                    ") outside [0, capacity " + std::to_string(cap) + ")");
-  if (n > cap)
-    return fail(SAC_E_INVALID, "q_values_replay: n (" + std::to_string(n) + ") exceeds the replay capacity (" +
-                                   std::to_string(cap) + ")");
-  if (!e) return fail(SAC_E_INVALID, "null engine");
-  if (rb->obs_dim != e->cfg.obs_dim || rb->act_dim != e->cfg.act_dim)
-    return fail(SAC_E_INVALID, "replay dims do not match the engine");
-  const RowStrides rs = row_strides(rb->row_stride, rb->obs_dim, rb->act_dim);
-  if (rs.obs < rb->obs_dim || rs.act < rb->act_dim)
-    return fail(SAC_E_INVALID, "q_values_replay: record stride below the field width");
-  return launch_q_values(e, QRows{use_next_obs ? rb->next_obs : rb->obs, rs.obs, rb->act, rs.act, first_slot, cap}, n,
-                         target, q, stream);
+  QRows rows;
+  const int rc = q_replay_rows(e, rb, n, use_next_obs, &rows);
+  if (rc) return rc;
+  rows.first = first_slot;
+  return launch_q_values(e, rows, n, target, q, stream);
+}
+
+// One slot of a device loop cursor and its parity, as the cursor entry points take them.
+static int check_cursor(const int64_t* cursor, int32_t parity, const char* who) {
+  if (!cursor) return fail(SAC_E_INVALID, std::string(who) + ": null cursor");
+  if (parity != 0 && parity != 1)
+    return fail(SAC_E_INVALID, std::string(who) + ": parity (" + std::to_string(parity) + ") must be 0 or 1");
+  return SAC_OK;
+}
+
+int sac_q_values_replay_dev(sac_engine* e, const sac_replay* rb, const int64_t* cursor, int32_t parity, int32_t n,
+                            int32_t use_next_obs, int32_t target, float* q_ring, int32_t q_ring_steps, void* stream) {
+  if (!rb || !rb->obs || !rb->act || !rb->next_obs)
+    return fail(SAC_E_INVALID, "q_values_replay_dev: null replay buffer");
+  if (!q_ring) return fail(SAC_E_INVALID, "q_values_replay_dev: null output ring");
+  int rc = check_cursor(cursor, parity, "q_values_replay_dev");
+  if (rc) return rc;
+  if (n < 1) return fail(SAC_E_INVALID, "q_values_replay_dev: n >= 1");
+  if (q_ring_steps < 1) return fail(SAC_E_INVALID, "q_values_replay_dev: q_ring_steps >= 1");
+  if (rb->capacity < 1) return fail(SAC_E_INVALID, "q_values_replay_dev: capacity >= 1");
+  QRows rows;
+  rc = q_replay_rows(e, rb, n, use_next_obs, &rows);
+  if (rc) return rc;
+  rows.cursor = cursor + 4 * parity;
+  rows.ring_steps = q_ring_steps;
+  return launch_q_values(e, rows, n, target, q_ring, stream);
 }
 
 int sac_debug_engine_host(const sac_engine_config* cfg, sac_engine** out) {
@@ -1678,8 +1737,9 @@ int sac_envs_step(const sac_envs* envs, const float* actions, uint64_t t, float*
   return SAC_OK;
 }
 
-int sac_rollout_step(sac_engine* e, const sac_envs* envs, const sac_replay* rb, int64_t size_host, int64_t pos_host,
-                     uint64_t t, int32_t deterministic, int32_t store, void* stream) {
+// What a fused rollout step needs, in two parts (sac_rollout_step checks its host (size, pos) between
+// them): the environments with their episode ring, a whole replay buffer that holds one vector step ...
+static int check_rollout_buffers(const sac_envs* envs, const sac_replay* rb) {
   int rc = check_envs(envs, true);
   if (rc) return rc;
   if (!rb || !rb->obs || !rb->act || !rb->rew || !rb->next_obs || !rb->done || !rb->state)
@@ -1688,14 +1748,26 @@ int sac_rollout_step(sac_engine* e, const sac_envs* envs, const sac_replay* rb, 
   if (cap < 1 || n > cap)
     return fail(SAC_E_INVALID, "num_envs (" + std::to_string(n) + ") exceeds the replay capacity (" +
                                    std::to_string(cap) + ")");
-  if (size_host < 0 || size_host > cap || pos_host < 0 || pos_host >= cap)
-    return fail(SAC_E_INVALID, "replay (size, pos) out of range");
+  return SAC_OK;
+}
+// ... and replay, environments and engine of one shape, on an engine that can run the policy's forward.
+static int check_rollout_dims(const sac_engine* e, const sac_envs* envs, const sac_replay* rb, const char* who) {
   if (rb->obs_dim != envs->cfg.obs_dim || rb->act_dim != SAC_ENV_ACT_DIM)
     return fail(SAC_E_INVALID, "replay dims do not match the environments (act_dim 1)");
   if (!e) return fail(SAC_E_INVALID, "null engine");
   if (e->cfg.obs_dim != envs->cfg.obs_dim || e->cfg.act_dim != SAC_ENV_ACT_DIM)
     return fail(SAC_E_INVALID, "engine dims do not match the environments (act_dim 1)");
-  rc = check_policy_forward(e, "rollout_step");
+  return check_policy_forward(e, who);
+}
+
+int sac_rollout_step(sac_engine* e, const sac_envs* envs, const sac_replay* rb, int64_t size_host, int64_t pos_host,
+                     uint64_t t, int32_t deterministic, int32_t store, void* stream) {
+  int rc = check_rollout_buffers(envs, rb);
+  if (rc) return rc;
+  const int64_t n = envs->cfg.num_envs, cap = rb->capacity;
+  if (size_host < 0 || size_host > cap || pos_host < 0 || pos_host >= cap)
+    return fail(SAC_E_INVALID, "replay (size, pos) out of range");
+  rc = check_rollout_dims(e, envs, rb, "rollout_step");
   if (rc) return rc;
   const int64_t new_size = std::min(cap, size_host + n);
   const int64_t new_pos = (pos_host + n) % cap;
@@ -1708,6 +1780,101 @@ int sac_rollout_step(sac_engine* e, const sac_envs* envs, const sac_replay* rb, 
     sac_rollout_step_kernel<float><<<blocks, SAC_THREADS, e->lds_bytes, s>>>(e->d, *envs, *rb, pos_host, new_size, new_pos,
                                                                             t, deterministic ? 1 : 0, store ? 1 : 0);
   HIPCHK(hipGetLastError());
+  return SAC_OK;
+}
+
+// every argument validated by the caller; one launch, no host-side state
+static int launch_rollout_dev(sac_engine* e, const sac_envs* envs, const sac_replay* rb, int64_t* cursor, int parity,
+                              int deterministic, int store, hipStream_t s) {
+  const int blocks = (envs->cfg.num_envs + SAC_ROWS - 1) / SAC_ROWS;
+  const int64_t* cur = cursor + 4 * parity;
+  int64_t* nxt = cursor + 4 * (parity ^ 1);
+  if (e->cfg.precision == SAC_PREC_BF16)
+    sac_rollout_step_dev_kernel<bf16><<<blocks, SAC_THREADS, e->lds_bytes, s>>>(e->d, *envs, *rb, cur, nxt, deterministic,
+                                                                               store);
+  else
+    sac_rollout_step_dev_kernel<float><<<blocks, SAC_THREADS, e->lds_bytes, s>>>(e->d, *envs, *rb, cur, nxt, deterministic,
+                                                                                store);
+  HIPCHK(hipGetLastError());
+  return SAC_OK;
+}
+
+int sac_rollout_step_dev(sac_engine* e, const sac_envs* envs, const sac_replay* rb, int64_t* cursor, int32_t parity,
+                         int32_t deterministic, int32_t store, void* stream) {
+  int rc = check_rollout_buffers(envs, rb);
+  if (rc) return rc;
+  rc = check_cursor(cursor, parity, "rollout_step_dev");
+  if (rc) return rc;
+  rc = check_rollout_dims(e, envs, rb, "rollout_step_dev");
+  if (rc) return rc;
+  return launch_rollout_dev(e, envs, rb, cursor, parity, deterministic ? 1 : 0, store ? 1 : 0, (hipStream_t)stream);
+}
+
+int sac_engine_loop_graph(sac_engine* e, const sac_envs* envs, const sac_replay* rb, int64_t* cursor, int32_t k_steps,
+                          const int32_t* grad_steps_host, float* q_ring, int32_t q_ring_steps, int32_t n_replays,
+                          void* stream) {
+  int rc = check_rollout_buffers(envs, rb);
+  if (rc) return rc;
+  if (!cursor) return fail(SAC_E_INVALID, "loop_graph: null cursor");
+  if (k_steps < 2 || (k_steps & 1))
+    return fail(SAC_E_INVALID, "loop_graph: k_steps (" + std::to_string(k_steps) +
+                                   ") must be even and >= 2 (the cursor slot of vector step j is j & 1)");
+  if (!grad_steps_host) return fail(SAC_E_INVALID, "loop_graph: null gradient-step counts");
+  for (int j = 0; j < k_steps; ++j)
+    if (grad_steps_host[j] < 0)
+      return fail(SAC_E_INVALID, "loop_graph: negative gradient-step count at vector step " + std::to_string(j));
+  if (n_replays < 0) return fail(SAC_E_INVALID, "loop_graph: n_replays >= 0");
+  if (q_ring && q_ring_steps < 1) return fail(SAC_E_INVALID, "loop_graph: q_ring needs q_ring_steps >= 1");
+  rc = check_rollout_dims(e, envs, rb, "loop_graph");
+  if (rc) return rc;
+  rc = check_replay(e, rb);
+  if (rc) return rc;
+  const int n = envs->cfg.num_envs;
+  QRows rows{};
+  if (q_ring) {
+    rc = q_replay_rows(e, rb, n, 1, &rows);
+    if (rc) return rc;
+    rc = check_q_forward(e);
+    if (rc) return rc;
+    rows.ring_steps = q_ring_steps;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  const sac_engine::LoopKey& k = e->lkey;
+  const bool same = e->lgexec && !memcmp(&k.envs, envs, sizeof(sac_envs)) && !memcmp(&k.rb, rb, sizeof(sac_replay)) &&
+                    k.cursor == cursor && k.q_ring == q_ring && k.q_ring_steps == (q_ring ? q_ring_steps : 0) &&
+                    (int)k.grad.size() == k_steps && std::equal(k.grad.begin(), k.grad.end(), grad_steps_host);
+  if (!same) {
+    if (e->lgexec) (void)hipGraphExecDestroy(e->lgexec);
+    if (e->lgraph) (void)hipGraphDestroy(e->lgraph);
+    e->lgexec = nullptr;
+    e->lgraph = nullptr;
+    if (!e->cap) HIPCHK(hipStreamCreateWithFlags(&e->cap, hipStreamNonBlocking));
+    // one stream, no forks: node j + 1 follows node j, so the slot vector step j writes is the one j + 1 reads
+    HIPCHK(hipStreamBeginCapture(e->cap, hipStreamCaptureModeThreadLocal));
+    for (int j = 0; j < k_steps && !rc; ++j) {
+      rc = launch_rollout_dev(e, envs, rb, cursor, j & 1, 0, 1, e->cap);
+      if (!rc && grad_steps_host[j]) launch_steps(e, rb, grad_steps_host[j], nullptr, nullptr, e->cap);
+      if (!rc && q_ring) {
+        rows.cursor = cursor + 4 * (j & 1);  // the slot this vector step read: its pos is the step's first row
+        rc = launch_q_values(e, rows, n, 0, q_ring, e->cap);
+      }
+    }
+    const hipError_t end = hipStreamEndCapture(e->cap, &e->lgraph);
+    if (rc || end != hipSuccess) {
+      if (e->lgraph) (void)hipGraphDestroy(e->lgraph);
+      e->lgraph = nullptr;
+      return rc ? rc : fail(SAC_E_HIP, std::string("loop_graph capture: ") + hipGetErrorString(end));
+    }
+    HIPCHK(hipGraphInstantiate(&e->lgexec, e->lgraph, nullptr, nullptr, 0));
+    HIPCHK(hipGraphUpload(e->lgexec, s));  // as train_graph: not inside the first replay
+    e->lkey.envs = *envs;
+    e->lkey.rb = *rb;
+    e->lkey.cursor = cursor;
+    e->lkey.q_ring = q_ring;
+    e->lkey.q_ring_steps = q_ring ? q_ring_steps : 0;
+    e->lkey.grad.assign(grad_steps_host, grad_steps_host + k_steps);
+  }
+  for (int r = 0; r < n_replays; ++r) HIPCHK(hipGraphLaunch(e->lgexec, s));
   return SAC_OK;
 }
 
@@ -1829,6 +1996,12 @@ int sac_engine_debug_stamps(sac_engine* e, long long* dev_buf, void* stream) {
     (void)hipGraphDestroy(e->graph);
     e->gexec = nullptr;
     e->graph = nullptr;
+  }
+  if (e->lgexec) {
+    (void)hipGraphExecDestroy(e->lgexec);
+    (void)hipGraphDestroy(e->lgraph);
+    e->lgexec = nullptr;
+    e->lgraph = nullptr;
   }
   return SAC_OK;
 }

@@ -10,7 +10,10 @@
 //   * sac_rollout_step_kernel<T>: sibling of sac_policy_act_kernel<T> (same
 //     workgroup shape, LDS layout and mlp_forward call); the thread that owns
 //     environment row i samples its action, steps the environment and writes
-//     the transition into the replay ring.
+//     the transition into the replay ring;
+//   * sac_rollout_step_dev_kernel<T>: the same body with (size, pos, t) read
+//     from a two-slot cursor in device memory, so whole loop iterations replay
+//     from one hipGraph (sac_engine_loop_graph).
 //
 // State is caller-owned global memory (include/sac_engine.h sac_envs).  Every
 // environment row is read and written by exactly one thread of one launch, and
@@ -170,14 +173,15 @@ __global__ void sac_envs_step_kernel(sac_envs ev, const float* __restrict__ acti
   truncated[i] = o.truncated ? 1 : 0;
 }
 
-// One workgroup per SAC_ROWS environments.  new_size / new_pos: the replay's
-// (size, write slot) after this step, computed by the host as sac_replay_push
-// does.
+// The fused step of one workgroup (SAC_ROWS environments) at RNG step t, its
+// rows going to ring slots (pos + i) % capacity.  new_size / new_pos: the
+// replay's (size, write slot) after this step, as sac_replay_push computes
+// them.  Both kernels below are this body; they differ in where (pos, t) come
+// from.
 template <typename T>
-__global__ void __launch_bounds__(SAC_THREADS) sac_rollout_step_kernel(const EngineDev* __restrict__ Ep, sac_envs ev,
-                                                                      sac_replay rb, int64_t pos, int64_t new_size,
-                                                                      int64_t new_pos, uint64_t t, int deterministic,
-                                                                      int store) {
+__device__ __forceinline__ void rollout_step_body(const EngineDev* __restrict__ Ep, const sac_envs& ev,
+                                                  const sac_replay& rb, int64_t pos, int64_t new_size, int64_t new_pos,
+                                                  uint64_t t, int deterministic, int store) {
   PREFETCH_ARG(Ep);
   const AS_C EngineDev& E = *(const AS_C EngineDev*)Ep;
   extern __shared__ float lds_raw[];
@@ -244,5 +248,43 @@ __global__ void __launch_bounds__(SAC_THREADS) sac_rollout_step_kernel(const Eng
     rb.state[0] = new_size;
     rb.state[1] = new_pos;
     rb.state[2] += 1;  // push generation: a batch phase C staged before this step is stale
+  }
+}
+
+// One workgroup per SAC_ROWS environments; (size, pos, t) are host arguments,
+// new_size / new_pos computed by the host as sac_replay_push does.
+template <typename T>
+__global__ void __launch_bounds__(SAC_THREADS) sac_rollout_step_kernel(const EngineDev* __restrict__ Ep, sac_envs ev,
+                                                                      sac_replay rb, int64_t pos, int64_t new_size,
+                                                                      int64_t new_pos, uint64_t t, int deterministic,
+                                                                      int store) {
+  rollout_step_body<T>(Ep, ev, rb, pos, new_size, new_pos, t, deterministic, store);
+}
+
+// The same step with the loop cursor on the device (include/sac_engine.h
+// sac_rollout_step_dev): every workgroup reads {size, pos, t} from `cur`, one
+// slot of the caller's cursor[2][4], and block 0's thread 0 writes the
+// advanced cursor to `nxt`, the other slot.  No workgroup reads a word another
+// workgroup of the launch writes (cur is only read, nxt and rb.state only
+// written), so nothing depends on the order workgroups run in and the launch
+// can be replayed from a hipGraph with the slots alternating.  A cursor outside
+// the ring (never seeded) stores nothing and does not advance.
+template <typename T>
+__global__ void __launch_bounds__(SAC_THREADS) sac_rollout_step_dev_kernel(const EngineDev* __restrict__ Ep, sac_envs ev,
+                                                                          sac_replay rb,
+                                                                          const int64_t* __restrict__ cur,
+                                                                          int64_t* __restrict__ nxt, int deterministic,
+                                                                          int store) {
+  const int64_t size = cur[0], pos = cur[1], cap = rb.capacity, n = ev.cfg.num_envs;
+  const uint64_t t = (uint64_t)cur[2] + 1;  // the k-th step (k = 0, 1, ...) is RNG step k + 1
+  if (size < 0 || size > cap || pos < 0 || pos >= cap) return;
+  const int64_t new_size = store ? (size + n < cap ? size + n : cap) : size;
+  const int64_t new_pos = store ? (pos + n) % cap : pos;
+  rollout_step_body<T>(Ep, ev, rb, pos, new_size, new_pos, t, deterministic, store);
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    nxt[0] = new_size;
+    nxt[1] = new_pos;
+    nxt[2] = (int64_t)t;
+    nxt[3] = 0;
   }
 }

@@ -2410,13 +2410,17 @@ __global__ void __launch_bounds__(SAC_THREADS) sac_policy_act_kernel(const Engin
 // physical row first + i (modulo == 0) or (first + i) % modulo (a ring), its
 // state at obs + row * obs_stride and its action at act + row * act_stride
 // (strides in floats).  One descriptor covers dense tensors, column views of a
-// records table and the struct-of-arrays replay.
+// records table and the struct-of-arrays replay.  With `cursor` (one slot {size,
+// pos, t, 0} of a device loop cursor, sac_q_values_replay_dev) first is that
+// slot's pos and the output is cell (t + 1) % ring_steps of q[ring_steps][n][2].
 struct QRows {
   const float* obs;
   int64_t obs_stride;
   const float* act;
   int64_t act_stride;
   int64_t first, modulo;
+  const int64_t* cursor;
+  int64_t ring_steps;
 };
 
 // Q1 and Q2 of n rows, forward only: q[n][2].  One workgroup per (row tile,
@@ -2441,6 +2445,12 @@ __global__ void __launch_bounds__(SAC_THREADS) sac_q_values_kernel(const EngineD
   const AS_G float* obs = GPC(float, rows.obs);
   const AS_G float* act = GPC(float, rows.act);
   AS_G float* qo = GP(float, q_);
+  int64_t first = rows.first;
+  if (rows.cursor) {  // every workgroup reads the slot; nobody in this launch writes it
+    first = rows.cursor[1];
+    if (first < 0 || first >= rows.modulo) return;  // a cursor never seeded
+    qo += ((uint64_t)rows.cursor[2] + 1) % (uint64_t)rows.ring_steps * ((size_t)n * 2);
+  }
   lf* Xb = lds + E.o_X;
   lf* Yb = lds + E.o_Y;
   lf* outB = lds + E.o_out;
@@ -2451,7 +2461,7 @@ __global__ void __launch_bounds__(SAC_THREADS) sac_q_values_kernel(const EngineD
     const int r = i / Kp0, k = i % Kp0;
     float v = 0.f;
     if (r < nvalid && k < O + A) {
-      int64_t row = rows.first + r0 + r;
+      int64_t row = first + r0 + r;
       if (rows.modulo) row %= rows.modulo;
       v = k < O ? obs[row * rows.obs_stride + k] : act[row * rows.act_stride + (k - O)];
     }

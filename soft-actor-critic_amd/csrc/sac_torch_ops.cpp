@@ -20,6 +20,9 @@
 //   envs_reset           SyncVectorEnv.reset          (sac/vector_env.py:39-46 over sac/envs.py)
 //   envs_step            SyncVectorEnv.step           (sac/vector_env.py:55-71 over sac/envs.py)
 //   rollout_step         select_actions + env.step + store_transitions of one vector step, ONE kernel
+//   rollout_step_dev     the same with (size, pos, t) read from a device loop cursor
+//   q_values_replay_dev  q_values_replay on the rows of the vector step a cursor slot describes
+//   loop_graph           K iterations of the device-resident loop, ONE hipGraph replay
 //
 // Replay storage is ONE fp32 tensor per buffer; `layout` = [capacity, obs_dim,
 // act_dim, row_stride, off_obs, off_act, off_rew, off_next_obs, off_done]
@@ -66,6 +69,9 @@ struct EngineApi {
   decltype(&sac_envs_reset) envs_reset = nullptr;
   decltype(&sac_envs_step) envs_step = nullptr;
   decltype(&sac_rollout_step) rollout_step = nullptr;
+  decltype(&sac_rollout_step_dev) rollout_step_dev = nullptr;
+  decltype(&sac_q_values_replay_dev) q_values_replay_dev = nullptr;
+  decltype(&sac_engine_loop_graph) engine_loop_graph = nullptr;
 };
 EngineApi g_api;
 std::string g_bound_path;
@@ -95,6 +101,9 @@ void bind_engine_library(c10::string_view path_) {
   resolve(h, "sac_envs_reset", a.envs_reset);
   resolve(h, "sac_envs_step", a.envs_step);
   resolve(h, "sac_rollout_step", a.rollout_step);
+  resolve(h, "sac_rollout_step_dev", a.rollout_step_dev);
+  resolve(h, "sac_q_values_replay_dev", a.q_values_replay_dev);
+  resolve(h, "sac_engine_loop_graph", a.engine_loop_graph);
   g_api = a;
   g_bound_path = path;
 }
@@ -423,6 +432,79 @@ void rollout_step(int64_t engine, at::Tensor& obs, at::Tensor& counters, at::Ten
                               deterministic ? 1 : 0, store ? 1 : 0, stream_of(obs)));
 }
 
+// ---------------------------------------------------------------- device loop cursor
+int64_t* cursor_of(const at::Tensor& cursor, const at::Tensor& like) {
+  TORCH_CHECK(cursor.is_cuda() && cursor.scalar_type() == at::kLong && cursor.is_contiguous() && cursor.dim() == 2 &&
+                  cursor.size(0) == 2 && cursor.size(1) == 4 && cursor.device() == like.device(),
+              "cursor must be a contiguous int64 [2][4] tensor on the replay's device");
+  return cursor.data_ptr<int64_t>();
+}
+
+float* q_ring_of(const at::Tensor& q_ring, int64_t n, const at::Tensor& like) {
+  check_f32(q_ring, "q_ring");
+  TORCH_CHECK(q_ring.dim() == 3 && q_ring.size(0) >= 1 && q_ring.size(0) <= INT32_MAX && q_ring.size(1) == n &&
+                  q_ring.size(2) == 2 && q_ring.device() == like.device(),
+              "q_ring must be [steps][", n, "][2] on the replay's device");
+  return q_ring.data_ptr<float>();
+}
+
+void rollout_step_dev(int64_t engine, at::Tensor& obs, at::Tensor& counters, at::Tensor& dstate, at::Tensor& ring,
+                      at::IntArrayRef icfg, at::ArrayRef<double> params, int64_t seed, at::Tensor& storage,
+                      at::Tensor& rstate, at::IntArrayRef layout, at::Tensor& cursor, int64_t parity, bool deterministic,
+                      bool store) {
+  TORCH_CHECK(engine != 0, "null engine handle");
+  sac_envs ev = make_envs(obs, counters, dstate, ring, icfg, params, seed);
+  Replay r = make_replay(storage, rstate, layout);
+  TORCH_CHECK(storage.device() == obs.device(), "replay and environments on different devices");
+  int64_t* cur = cursor_of(cursor, storage);
+  TORCH_CHECK(parity == 0 || parity == 1, "parity must be 0 or 1");
+  Guard g(obs.device());
+  check_rc(api().rollout_step_dev(reinterpret_cast<sac_engine*>(engine), &ev, &r.d, cur, static_cast<int32_t>(parity),
+                                  deterministic ? 1 : 0, store ? 1 : 0, stream_of(obs)));
+}
+
+void q_values_replay_dev(int64_t engine, const at::Tensor& storage, const at::Tensor& rstate, at::IntArrayRef layout,
+                         const at::Tensor& cursor, int64_t parity, int64_t n, bool next_obs, bool target,
+                         at::Tensor& q_ring) {
+  TORCH_CHECK(engine != 0, "null engine handle");
+  Replay r = make_replay(storage, rstate, layout);
+  TORCH_CHECK(n >= 1 && n <= r.d.capacity, "n must be in [1, capacity]");
+  const int64_t* cur = cursor_of(cursor, storage);
+  TORCH_CHECK(parity == 0 || parity == 1, "parity must be 0 or 1");
+  float* q = q_ring_of(q_ring, n, storage);
+  Guard g(storage.device());
+  check_rc(api().q_values_replay_dev(reinterpret_cast<sac_engine*>(engine), &r.d, cur, static_cast<int32_t>(parity),
+                                     static_cast<int32_t>(n), next_obs ? 1 : 0, target ? 1 : 0, q,
+                                     static_cast<int32_t>(q_ring.size(0)), stream_of(storage)));
+}
+
+void loop_graph(int64_t engine, at::TensorList state, at::Tensor& obs, at::Tensor& counters, at::Tensor& dstate,
+                at::Tensor& ring, at::IntArrayRef icfg, at::ArrayRef<double> params, int64_t seed, at::Tensor& storage,
+                at::Tensor& rstate, at::IntArrayRef layout, at::Tensor& cursor, at::IntArrayRef grad_steps,
+                int64_t n_replays, const std::optional<at::Tensor>& q_ring) {
+  sac_envs ev = make_envs(obs, counters, dstate, ring, icfg, params, seed);
+  Replay r = make_replay(storage, rstate, layout);
+  sac_engine* e = engine_of(engine, state, storage);
+  TORCH_CHECK(storage.device() == obs.device(), "replay and environments on different devices");
+  int64_t* cur = cursor_of(cursor, storage);
+  TORCH_CHECK(grad_steps.size() <= INT32_MAX && n_replays >= 0 && n_replays <= INT32_MAX,
+              "grad_steps / n_replays out of range");
+  std::vector<int32_t> g32;
+  for (int64_t v : grad_steps) {
+    TORCH_CHECK(v >= 0 && v <= INT32_MAX, "gradient-step counts must be >= 0");
+    g32.push_back(static_cast<int32_t>(v));
+  }
+  float* q = nullptr;
+  int32_t q_steps = 0;
+  if (q_ring && q_ring->defined()) {
+    q = q_ring_of(*q_ring, ev.cfg.num_envs, storage);
+    q_steps = static_cast<int32_t>(q_ring->size(0));
+  }
+  Guard g(storage.device());
+  check_rc(api().engine_loop_graph(e, &ev, &r.d, cur, static_cast<int32_t>(g32.size()), g32.data(), q, q_steps,
+                                   static_cast<int32_t>(n_replays), stream_of(storage)));
+}
+
 // ---------------------------------------------------------------- meta (shapes only)
 void replay_push_meta(at::Tensor&, at::Tensor&, at::IntArrayRef, const at::Tensor&, int64_t, int64_t) {}
 
@@ -480,6 +562,17 @@ void rollout_step_meta(int64_t, at::Tensor&, at::Tensor&, at::Tensor&, at::Tenso
                        at::ArrayRef<double>, int64_t, at::Tensor&, at::Tensor&, at::IntArrayRef, int64_t, int64_t,
                        int64_t, bool, bool) {}
 
+void rollout_step_dev_meta(int64_t, at::Tensor&, at::Tensor&, at::Tensor&, at::Tensor&, at::IntArrayRef,
+                           at::ArrayRef<double>, int64_t, at::Tensor&, at::Tensor&, at::IntArrayRef, at::Tensor&, int64_t,
+                           bool, bool) {}
+
+void q_values_replay_dev_meta(int64_t, const at::Tensor&, const at::Tensor&, at::IntArrayRef, const at::Tensor&, int64_t,
+                              int64_t, bool, bool, at::Tensor&) {}
+
+void loop_graph_meta(int64_t, at::TensorList, at::Tensor&, at::Tensor&, at::Tensor&, at::Tensor&, at::IntArrayRef,
+                     at::ArrayRef<double>, int64_t, at::Tensor&, at::Tensor&, at::IntArrayRef, at::Tensor&,
+                     at::IntArrayRef, int64_t, const std::optional<at::Tensor>&) {}
+
 }  // namespace
 
 TORCH_LIBRARY(sac_hip, m) {
@@ -505,6 +598,14 @@ TORCH_LIBRARY(sac_hip, m) {
   m.def("rollout_step(int engine, Tensor(a!) obs, Tensor(b!) counters, Tensor(c!) dstate, Tensor(d!) ring, "
         "int[] icfg, float[] params, int seed, Tensor(e!) storage, Tensor(f!) replay_state, int[] layout, "
         "int size, int pos, int t, bool deterministic=False, bool store=True) -> ()");
+  m.def("rollout_step_dev(int engine, Tensor(a!) obs, Tensor(b!) counters, Tensor(c!) dstate, Tensor(d!) ring, "
+        "int[] icfg, float[] params, int seed, Tensor(e!) storage, Tensor(f!) replay_state, int[] layout, "
+        "Tensor(g!) cursor, int parity, bool deterministic=False, bool store=True) -> ()");
+  m.def("q_values_replay_dev(int engine, Tensor storage, Tensor replay_state, int[] layout, Tensor cursor, "
+        "int parity, int n, bool next_obs, bool target, Tensor(a!) q_ring) -> ()");
+  m.def("loop_graph(int engine, Tensor(a!)[] state, Tensor(b!) obs, Tensor(c!) counters, Tensor(d!) dstate, "
+        "Tensor(e!) ring, int[] icfg, float[] params, int seed, Tensor(f!) storage, Tensor(g!) replay_state, "
+        "int[] layout, Tensor(h!) cursor, int[] grad_steps, int n_replays, Tensor(i!)? q_ring=None) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(sac_hip, CUDA, m) {
@@ -520,6 +621,9 @@ TORCH_LIBRARY_IMPL(sac_hip, CUDA, m) {
   m.impl("envs_reset", &envs_reset);
   m.impl("envs_step", &envs_step);
   m.impl("rollout_step", &rollout_step);
+  m.impl("rollout_step_dev", &rollout_step_dev);
+  m.impl("q_values_replay_dev", &q_values_replay_dev);
+  m.impl("loop_graph", &loop_graph);
 }
 
 TORCH_LIBRARY_IMPL(sac_hip, Meta, m) {
@@ -535,4 +639,7 @@ TORCH_LIBRARY_IMPL(sac_hip, Meta, m) {
   m.impl("envs_reset", &envs_reset_meta);
   m.impl("envs_step", &envs_step_meta);
   m.impl("rollout_step", &rollout_step_meta);
+  m.impl("rollout_step_dev", &rollout_step_dev_meta);
+  m.impl("q_values_replay_dev", &q_values_replay_dev_meta);
+  m.impl("loop_graph", &loop_graph_meta);
 }

@@ -140,6 +140,15 @@ SIGNATURES = {
     "sac_rollout_step": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(EnvsDesc), ctypes.POINTER(ReplayDesc),
                                         ctypes.c_int64, ctypes.c_int64, ctypes.c_uint64, ctypes.c_int32,
                                         ctypes.c_int32, ctypes.c_void_p]),
+    "sac_rollout_step_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(EnvsDesc), ctypes.POINTER(ReplayDesc),
+                                            ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                            ctypes.c_void_p]),
+    "sac_q_values_replay_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ReplayDesc), ctypes.c_void_p,
+                                               ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                               ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]),
+    "sac_engine_loop_graph": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(EnvsDesc), ctypes.POINTER(ReplayDesc),
+                                             ctypes.c_void_p, ctypes.c_int32, c_int32_p, ctypes.c_void_p,
+                                             ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p]),
 }
 
 _lib: Optional[ctypes.CDLL] = None
@@ -179,7 +188,8 @@ def ops():
     """``torch.ops.sac_hip``: the PyTorch custom ops over the C ABI
     (csrc/sac_torch_ops.cpp: replay_push, replay_gather, replay_sample,
     replay_sample_gather, train_step, train_graph, policy_act, q_values,
-    q_values_replay, envs_reset, envs_step, rollout_step).  The op library
+    q_values_replay, envs_reset, envs_step, rollout_step, rollout_step_dev,
+    q_values_replay_dev, loop_graph).  The op library
     dlopens the engine library ctypes loaded (bind_engine_library: the same file,
     so the same instance owns the engine handles).  Raises EngineUnavailable
     when it is not built."""

@@ -40,7 +40,7 @@ import time
 import warnings
 from collections import deque
 from copy import deepcopy
-from typing import Callable, Any, Dict, Optional
+from typing import Callable, Any, Dict, List, Optional
 
 import numpy as np
 import torch
@@ -101,6 +101,61 @@ def due_updates_gated(old_steps: int, new_steps: int, len_before: int, capacity:
     if first > new_steps:
         return 0
     return due_updates(first - 1, new_steps, update_frequency, gradient_steps)
+
+
+#: times ``run_device_training_loop(graph_steps=K)`` captures its loop graph again because the block's
+#: gradient-step pattern changed; after that a block with another pattern runs stepwise
+MAX_RECAPTURES = 4
+
+
+def plan_graph_block(total_steps: int, len_replay: int, capacity: int, warming_steps: int, update_frequency: int,
+                     gradient_steps: int, num_envs: int, k_steps: int) -> List[int]:
+    """Gradient steps the device-resident loop runs after each of its next
+    ``k_steps`` vector steps, from its bookkeeping before the first of them
+    (env steps taken, rows in the replay buffer): vector step j moves the env
+    step counter by ``num_envs`` and runs ``due_updates_gated`` of that move if
+    ``can_update()`` holds after it, exactly as the stepwise loop does."""
+    counts = []
+    for _ in range(k_steps):
+        due = due_updates_gated(total_steps, total_steps + num_envs, len_replay, capacity, warming_steps,
+                                update_frequency, gradient_steps)
+        total_steps += num_envs
+        len_replay = min(capacity, len_replay + num_envs)
+        counts.append(due if len_replay >= warming_steps else 0)
+    return counts
+
+
+def graph_block_ready(counts: List[int], len_replay: int, capacity: int, warming_steps: int, batch: int,
+                      num_envs: int) -> bool:
+    """Whether a block with these per-vector-step gradient counts may run from
+    the loop graph: the warm-up is over by its first vector step
+    (``can_update()`` holds after it) and every gradient step finds at least
+    ``batch`` rows.  A block that fails runs stepwise, which raises what the
+    stepwise loop raises."""
+    if min(capacity, len_replay + num_envs) < warming_steps:
+        return False
+    return all(min(capacity, len_replay + (j + 1) * num_envs) >= batch for j, g in enumerate(counts) if g)
+
+
+class GraphBlockPolicy:
+    """Which blocks replay the captured loop graph: the first ready block
+    captures; a ready block with the captured pattern replays; one with
+    another pattern captures again, ``max_recaptures`` times in all, and runs
+    stepwise after that."""
+
+    def __init__(self, max_recaptures: int = MAX_RECAPTURES):
+        self.captured: Optional[List[int]] = None
+        self.left = int(max_recaptures)
+
+    def admit(self, counts: List[int]) -> bool:
+        if counts == self.captured:
+            return True
+        if self.captured is not None:
+            if self.left <= 0:
+                return False
+            self.left -= 1
+        self.captured = list(counts)
+        return True
 
 
 class LossLog:
@@ -716,7 +771,8 @@ class SAC:
     def run_device_training_loop(self, total_env_steps: int, vec_env: Any = None, logger=None,
                                  print_rewards: bool = False, seed: Optional[int] = None,
                                  callback: Optional[Callable[[Dict[str, float]], None]] = None,
-                                 drain_every: int = 64, device_q_values: bool = False) -> Dict[str, float]:
+                                 drain_every: int = 64, device_q_values: bool = False,
+                                 graph_steps: int = 0) -> Dict[str, float]:
         """``run_vectorized_training_loop`` over a ``DeviceVectorEnv``: the envs
         live on the device and act -> step -> store is ONE launch
         (``SacEngine.rollout_step``), so a vector step is that launch plus the
@@ -751,10 +807,44 @@ class SAC:
         vector steps like the episodes -- the quantity the vectorised loop
         logs, from the packed weights the engine trains with (in bf16 mode
         those are the bf16 copies, not the fp32 eager forward).  With the
-        config key off, ``device_q_values`` logs and launches nothing."""
+        config key off, ``device_q_values`` logs and launches nothing.
+
+        ``graph_steps = K`` (even, >= 2; 0 = off, the loop above unchanged):
+        whole blocks of K vector steps -- rollout, the gradient steps due after
+        each (``plan_graph_block``), the Q-value launch -- are ONE hipGraph
+        replay (``SacEngine.loop_graph``) with the loop cursor (replay size,
+        write slot, step number) kept on the device, so a block costs the host
+        one call.  A block goes through the graph when K whole vector steps
+        remain, the warm-up is over and every gradient step finds a full batch
+        (``graph_block_ready``), and its gradient-step pattern is the captured
+        one; a new pattern captures again, at most ``MAX_RECAPTURES`` times.
+        Every other block (warm-up, another pattern after that, the tail) runs
+        stepwise as above, and the device cursor is re-seeded from the host
+        mirrors before the next graph block (one asynchronous copy).  The
+        results are those of ``graph_steps = 0`` bit for bit.  The loss log,
+        the episode drain, the Q-value drain, the status poll and ``callback``
+        run once per block: a callback sees ``env_steps`` advance by K * N.
+        Needs ``K + drain_every <= `` the episode ring's (and the Q ring's)
+        steps, and the device RNG (``rng_mode`` "reference" feeds the gradient
+        step from the host): otherwise ValueError before any launch."""
         from .device_envs import DeviceQValueLog, EpisodeDrain
 
         env = self._device_env(vec_env, "run_device_training_loop")
+        K = int(graph_steps)
+        if K:
+            if K < 2 or K % 2:
+                raise ValueError(f"graph_steps must be 0 or an even number >= 2 (the device cursor alternates between "
+                                 f"two slots); got {graph_steps}")
+            if self.rng_mode == "reference":
+                raise ValueError("graph_steps needs the device RNG: rng_mode 'reference' draws every gradient step's "
+                                 "indices and noise on the host")
+            if K + max(1, int(drain_every)) > env.ring_steps:
+                raise ValueError(f"graph_steps ({K}) + drain_every ({max(1, int(drain_every))}) exceeds the episode "
+                                 f"ring's {env.ring_steps} steps: a block would overwrite cells not yet copied")
+            if device_q_values and (logger or self.logger) is not None and self.config["logger"]["log_q_values"] \
+                    and K + max(1, int(drain_every)) > DeviceQValueLog.RING_STEPS:
+                raise ValueError(f"graph_steps ({K}) + drain_every ({max(1, int(drain_every))}) exceeds the Q-value "
+                                 f"ring's {DeviceQValueLog.RING_STEPS} steps")
         if self.config["logger"]["log_q_values"] and not device_q_values:
             raise ValueError("run_device_training_loop does not support logger.log_q_values through the host path "
                              "(per-env-step Q values need the transitions on the host); pass device_q_values=True "
@@ -786,8 +876,57 @@ class SAC:
         drain = EpisodeDrain(env, on_episode, drain_every)
         q_log = None
         if device_q_values and active_logger is not None and self.config["logger"]["log_q_values"]:
-            q_log = DeviceQValueLog(eng, self.replay_buffer, N, active_logger, drain_every)
-        for _ in range((int(total_env_steps) + N - 1) // N):
+            # with the graph, cell = RNG step % S on both paths: the graph's kernel indexes its cell that way
+            q_log = DeviceQValueLog(eng, self.replay_buffer, N, active_logger, drain_every,
+                                    first_cell=env.t + 1 if K else 0)
+        vec_steps = (int(total_env_steps) + N - 1) // N
+
+        def report() -> None:
+            drain.after_step()
+            if callback is not None:
+                callback({"env_steps": total_steps, "gradient_steps": grad_steps, "episodes": st["episodes"],
+                          "avg_return": st["avg"]})
+
+        if K:
+            cursor, policy, seeded, done = eng.loop_cursor(), GraphBlockPolicy(), False, 0
+            batch, cap = tr["batch_size"], self.replay_buffer.capacity
+            while done < vec_steps:
+                counts = plan_graph_block(total_steps, len(self.replay_buffer), cap, tr["warming_steps"],
+                                          update_every, n_grad, N, K)
+                if vec_steps - done >= K and graph_block_ready(counts, len(self.replay_buffer), cap,
+                                                               tr["warming_steps"], batch, N) \
+                        and policy.admit(counts):
+                    if not seeded:  # the last block moved the host mirrors only
+                        eng.seed_cursor(cursor, env, self.replay_buffer)
+                        seeded = True
+                    eng.loop_graph(env, self.replay_buffer, cursor, counts, 1, None if q_log is None else q_log.ring)
+                    if q_log is not None:
+                        q_log.after_graph(K, total_steps + 1)
+                    total_steps += K * N
+                    grad_steps += sum(counts)
+                    if loss_log is not None and sum(counts):
+                        loss_log.after_updates(total_steps)
+                    done += K
+                else:
+                    seeded = False
+                    for due in counts[:min(K, vec_steps - done)]:
+                        if q_log is not None:
+                            self.replay_buffer.flush()
+                        first_slot = self.replay_buffer._pos
+                        eng.rollout_step(env, self.replay_buffer)
+                        old = total_steps
+                        total_steps += N
+                        if self.can_update() and due:
+                            self._run_updates(due)
+                            grad_steps += due
+                            if loss_log is not None:
+                                loss_log.after_updates(total_steps)
+                        if q_log is not None:
+                            q_log.after_step(first_slot, old + 1)
+                        done += 1
+                report()
+            vec_steps = 0  # all taken
+        for _ in range(vec_steps):
             len_before = len(self.replay_buffer)
             if q_log is not None:
                 self.replay_buffer.flush()  # rows pushed from the host go in first: they move the write slot

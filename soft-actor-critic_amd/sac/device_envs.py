@@ -241,12 +241,20 @@ class DeviceQValueLog:
     steps the new cells are copied to pinned memory behind the launches;
     once a copy's event has completed its values go to
     ``logger.log_q_values(q1, q2, step)``, steps ``first_step + i`` in order.
-    ``finish`` consumes the rest, blocking.  Nothing else synchronises."""
+    ``finish`` consumes the rest, blocking.  Nothing else synchronises.
+
+    ``first_cell`` shifts the cells: the k-th cell written is ``(first_cell +
+    k) % S``.  A loop graph (``SacEngine.loop_graph(..., q_ring=log.ring)``)
+    writes its vector steps' cells itself, at ``RNG step % S``; a log created
+    with ``first_cell`` = the RNG step of the next vector step then only has to
+    be told about them (``after_graph``) and drains them with the rest."""
 
     RING_STEPS = 256
 
-    def __init__(self, engine, replay, num_envs: int, logger, every: int = 64, ring_steps: Optional[int] = None):
+    def __init__(self, engine, replay, num_envs: int, logger, every: int = 64, ring_steps: Optional[int] = None,
+                 first_cell: int = 0):
         self.engine, self.replay, self.logger = engine, replay, logger
+        self.first_cell = int(first_cell)
         self.num_envs = int(num_envs)
         self.ring_steps = int(ring_steps or self.RING_STEPS)
         if self.ring_steps < 1:
@@ -262,9 +270,20 @@ class DeviceQValueLog:
         """The rollout step wrote its N rows at ring slots ``first_slot + i``
         (wrapping); row i is logged at env step ``first_step + i``."""
         self.engine.q_values_replay(self.replay, first_slot, self.num_envs, next_obs=True,
-                                    out=self.ring[self.t % self.ring_steps])
+                                    out=self.ring[(self.first_cell + self.t) % self.ring_steps])
         self.t += 1
         self.first_steps.append(int(first_step))
+        if self.t - self.copied_to >= self.every:
+            self._queue()
+        self._consume(block=False)
+
+    def after_graph(self, k_steps: int, first_step: int) -> None:
+        """A loop graph just queued ``k_steps`` vector steps that write the
+        next ``k_steps`` cells; the rows of the first are logged from env step
+        ``first_step``.  Launches nothing."""
+        for j in range(int(k_steps)):
+            self.first_steps.append(int(first_step) + j * self.num_envs)
+        self.t += int(k_steps)
         if self.t - self.copied_to >= self.every:
             self._queue()
         self._consume(block=False)
@@ -275,7 +294,7 @@ class DeviceQValueLog:
             return
         S = self.ring_steps
         host = torch.empty(n, self.num_envs, 2, dtype=torch.float32, pin_memory=True)
-        a, b = self.copied_to % S, (self.t - 1) % S
+        a, b = (self.first_cell + self.copied_to) % S, (self.first_cell + self.t - 1) % S
         with torch.cuda.device(self.engine.device):
             if a <= b:
                 host.copy_(self.ring[a:b + 1], non_blocking=True)

@@ -381,6 +381,99 @@ class SacEngine:
             replay._size = min(replay.capacity, replay._size + n)
             replay._pos = (replay._pos + n) % replay.capacity
 
+    # ------------------------------------------------------------------ device loop cursor
+    def new_cursor(self) -> torch.Tensor:
+        """A device loop cursor (include/sac_engine.h): int64 [2][4], slot p =
+        {replay size, next write slot, vector steps taken, 0}."""
+        return torch.zeros(2, 4, dtype=torch.int64, device=self.device)
+
+    def loop_cursor(self) -> torch.Tensor:
+        """The engine's own cursor, made on first use: a loop that keeps using
+        it keeps ``loop_graph``'s captured graph from one call to the next."""
+        if getattr(self, "_loop_cursor", None) is None:
+            self._loop_cursor = self.new_cursor()
+        return self._loop_cursor
+
+    def seed_cursor(self, cursor: torch.Tensor, envs, replay, parity: int = 0) -> None:
+        """Write the host mirrors (``replay._size``, ``replay._pos``,
+        ``envs.t``) into slot ``parity``: one asynchronous copy from a pinned
+        buffer on the current stream, no synchronisation."""
+        replay.flush()
+        host = torch.empty(4, dtype=torch.int64, pin_memory=True)
+        host[0], host[1], host[2], host[3] = replay._size, replay._pos, envs.t, 0
+        with torch.cuda.device(self.device):
+            cursor[int(parity)].copy_(host, non_blocking=True)
+
+    def _rollout_ready(self, envs, replay, what: str) -> None:
+        if not replay._alloc_done:
+            replay._alloc(envs.obs_dim, envs.act_dim)
+        replay.flush()
+        if not envs._reset_done:
+            envs.reset()
+        if envs.num_envs > replay.capacity:
+            raise ValueError(f"{what}: num_envs ({envs.num_envs}) exceeds the replay capacity ({replay.capacity})")
+
+    def rollout_step_dev(self, envs, replay, cursor: torch.Tensor, parity: int, deterministic: bool = False,
+                         store: bool = True) -> None:
+        """``rollout_step`` with (size, pos, t) read on the device from
+        ``cursor[parity]`` -- which the caller has seeded (``seed_cursor``) or
+        the previous ``rollout_step_dev`` at the other parity has written --
+        and the advanced cursor written to ``cursor[parity ^ 1]``.  The host
+        mirrors advance by the same deterministic amounts, so the two paths can
+        be mixed as long as the slot read holds the mirrors' values."""
+        self._rollout_ready(envs, replay, "rollout_step_dev")
+        if parity not in (0, 1):
+            raise ValueError(f"rollout_step_dev: parity {parity!r} must be 0 or 1")
+        n = envs.num_envs
+        with torch.cuda.device(self.device):
+            self.ops.rollout_step_dev(self.handle.value, envs.obs, envs.counters, envs.dstate, envs.ring, envs._icfg,
+                                      envs._params, envs.seed, replay.storage, replay.state, replay.layout_spec,
+                                      cursor, int(parity), bool(deterministic), bool(store))
+        envs.t += 1
+        if store:
+            replay._size = min(replay.capacity, replay._size + n)
+            replay._pos = (replay._pos + n) % replay.capacity
+
+    def loop_graph(self, envs, replay, cursor: torch.Tensor, grad_steps, n_replays: int,
+                   q_ring: Optional[torch.Tensor] = None) -> None:
+        """``n_replays`` replays of ONE hipGraph holding ``K = len(grad_steps)``
+        (even, >= 2) iterations of the device-resident loop: per iteration j
+        the fused rollout step (sampled actions, stored), ``grad_steps[j]``
+        gradient steps (device sampler and noise) and, with ``q_ring``
+        ([S][N][2] fp32), the critic evaluation of the step's N rows into cell
+        ``t % S`` (t the step's RNG step).  ``cursor[0]`` must hold the host
+        mirrors when the first replay starts (``seed_cursor``; a replay leaves
+        it so for the next one).  The graph is captured on the first call and
+        again whenever envs, replay, cursor, the counts or the ring change
+        (``n_replays = 0`` captures only); ``train_graph``'s graph is a
+        separate cache.  The host mirrors (``replay._size`` / ``_pos``,
+        ``envs.t``, ``steps_done``) advance by the deterministic amounts.  No
+        host work per vector step and no synchronisation."""
+        self._rollout_ready(envs, replay, "loop_graph")
+        grad_steps = [int(g) for g in grad_steps]
+        K, n_replays, n, cap = len(grad_steps), int(n_replays), envs.num_envs, replay.capacity
+        if K < 2 or K % 2:
+            raise ValueError(f"loop_graph: {K} vector steps per graph; need an even number >= 2")
+        if n_replays < 0 or min(grad_steps) < 0:
+            raise ValueError("loop_graph: n_replays and every gradient-step count must be >= 0")
+        for j, g in enumerate(grad_steps):  # the first replay holds the fewest rows
+            if g and min(cap, replay._size + (j + 1) * n) < self.batch and n_replays:
+                raise ValueError(
+                    f"Not enough samples in the replay buffer to sample {self.batch} transitions at vector step {j} "
+                    f"of the graph. Current size: {min(cap, replay._size + (j + 1) * n)}")
+        self._poll_status()
+        with torch.cuda.device(self.device):
+            self.ops.loop_graph(self.handle.value, self.state_list, envs.obs, envs.counters, envs.dstate, envs.ring,
+                                envs._icfg, envs._params, envs.seed, replay.storage, replay.state, replay.layout_spec,
+                                cursor, grad_steps, n_replays, q_ring)
+        steps = K * n_replays
+        envs.t += steps
+        replay._size = min(cap, replay._size + steps * n)
+        replay._pos = (replay._pos + steps * n) % cap
+        self.steps_done += sum(grad_steps) * n_replays
+        if n_replays:
+            self._after_launch()
+
     def time_phases(self, replay, n_steps: int) -> List[float]:
         """[A, B, C, D, gap]: mean hipEvent interval per phase launch (ms) and
         that of an empty kernel launched the same way (see sac_engine.h)."""

@@ -26,6 +26,10 @@ gymnasium id (the reference's own envs).
 vector step, with no per-step host<->device traffic.  A config with
 ``logger.log_q_values: true`` runs there unchanged: the per-env-step Q values
 are evaluated and logged on the device (``device_q_values=True``).
+``--graph-steps K`` (even, >= 2; with ``--device-envs``) replays blocks of K
+vector steps from one hipGraph with the loop cursor on the device
+(``run_device_training_loop(graph_steps=K)``); the aggregation callback then
+runs once per block.
 """
 from __future__ import annotations
 
@@ -74,13 +78,13 @@ def rank_env() -> tuple:
 
 def train_replica(config: dict, make_env: Callable[[], object], num_envs: int, env_steps: int, every: int,
                   rank: int, device: Optional[str] = None, agent_cls=None, vec_env_cls=None,
-                  device_envs: bool = False) -> dict:
+                  device_envs: bool = False, graph_steps: int = 0) -> dict:
     """Train this rank's replica and return {"metrics": its loop metrics,
     "aggregate": the all-reduced METRICS summary}.  ``agent_cls`` /
     ``vec_env_cls`` default to sac.agent.SAC / sac.vector_env.SyncVectorEnv
     (tests pass host stubs).  ``device_envs``: ``make_env`` must build a probe
     env of sac.envs; num_envs device copies of it (DeviceVectorEnv.from_env)
-    train through ``run_device_training_loop``."""
+    train through ``run_device_training_loop`` (``graph_steps``: its argument)."""
     if agent_cls is None:
         from sac.agent import SAC as agent_cls  # noqa: N813
     if vec_env_cls is None:
@@ -110,8 +114,9 @@ def train_replica(config: dict, make_env: Callable[[], object], num_envs: int, e
     agg = ReplicaAggregator(agent.engine, every)
     if device_envs:
         # a config with logger.log_q_values (every probe config of the reference) logs them on the device
+        extra = {"graph_steps": graph_steps} if graph_steps else {}
         metrics = agent.run_device_training_loop(env_steps, callback=agg, seed=cfg["train"]["seed"],
-                                                 device_q_values=True)
+                                                 device_q_values=True, **extra)
     else:
         metrics = agent.run_vectorized_training_loop(env_steps, callback=agg, seed=cfg["train"]["seed"])
     return {"metrics": metrics, "aggregate": agg.finish()}
@@ -126,9 +131,13 @@ def main(argv=None) -> int:
     ap.add_argument("--aggregate-every", type=int, default=1000, help="gradient steps between all-reduces")
     ap.add_argument("--device-envs", action="store_true",
                     help="keep the (probe) environments on the device: one fused act/step/store launch per vector step")
+    ap.add_argument("--graph-steps", type=int, default=0,
+                    help="with --device-envs: vector steps per hipGraph replay of the loop (even, >= 2; 0 = stepwise)")
     a = ap.parse_args(argv)
     if a.device_envs and a.env not in PROBE_ENVS:
         raise SystemExit(f"--device-envs: {a.env!r} is not a probe env ({sorted(PROBE_ENVS)})")
+    if a.graph_steps and not a.device_envs:
+        raise SystemExit("--graph-steps needs --device-envs (the loop graph holds the device-resident loop)")
     import yaml
 
     with open(a.config) as f:
@@ -145,7 +154,7 @@ def main(argv=None) -> int:
         dist.init_process_group("nccl")  # RCCL on ROCm: the metric all-reduce only
     try:
         out = train_replica(config, env_factory(a.env), a.num_envs, a.env_steps, a.aggregate_every, rank, device,
-                            device_envs=a.device_envs)
+                            device_envs=a.device_envs, graph_steps=a.graph_steps)
     finally:
         if world > 1:
             import torch.distributed as dist
