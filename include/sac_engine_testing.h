@@ -70,6 +70,27 @@ int sac_debug_env_obs_host(uint64_t seed, uint64_t t, int32_t which, int32_t n, 
  * ("no device state") where the launch would be.  Pass it to no other entry
  * point but sac_engine_destroy. */
 int sac_debug_engine_host(const sac_engine_config *cfg, sac_engine **out);
+/* The plan sac_engine_create would make of cfg on a device of ncu compute
+ * units, as one JSON object in out[cap]; no HIP call is made and nothing is
+ * dereferenced.  The config is validated and planned as create does it, and
+ * refused (SAC_E_INVALID, sac_last_error()) where and as create refuses it
+ * before its first HIP call; also when cap is too small.  Fields: "path"
+ * ("split" | "roles" | "pairs" | "rows" | "wide"), the scalars workspace_bytes,
+ * lds_bytes, upd_lds, upd_lds_b, upd_threads_b, nB, nD, nrt, xs, role_xcd,
+ * stage, upd_slots; "launch": grid, threads and dynamic LDS bytes of phases A,
+ * B, C, D (the stage path: B, D and "stages", its launch list: kind, j0, j1,
+ * grid, phase, last, lds); "hash": FNV-1a 64 of the bytes of the device
+ * descriptor, the update-tile arrays of phases B and D, and the stage path's
+ * descriptor and job array (of no bytes off the stage path).
+ * Device addresses in the hashed descriptors are these fake ones: the
+ * workspace at SAC_PLAN_FAKE_WORKSPACE, buffer i of sac_engine_buffers (pi,
+ * q1, ... stats: the fifteen pointers before workspace, in struct order) at
+ * SAC_PLAN_FAKE_BUFFER0 + i * SAC_PLAN_FAKE_BUFFER_STEP: 256-byte aligned and
+ * 1 TiB apart, further than any buffer or workspace reaches. */
+#define SAC_PLAN_FAKE_WORKSPACE 0x200000000000ull
+#define SAC_PLAN_FAKE_BUFFER0 0x010000000000ull
+#define SAC_PLAN_FAKE_BUFFER_STEP 0x010000000000ull
+int sac_debug_plan_host(const sac_engine_config *cfg, int32_t ncu, char *out, size_t cap);
 #ifdef __cplusplus
 }
 #endif

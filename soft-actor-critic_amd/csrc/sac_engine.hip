@@ -21,6 +21,7 @@
 // compute copies in the MFMA dtype ([out][in] and [in][out], 32-padded) that the
 // update kernels rewrite in place, so nothing is re-packed per step.
 #include "../../include/sac_engine.h"
+#include "../../include/sac_engine_testing.h"
 
 #include <algorithm>
 #include <math.h>
@@ -37,6 +38,7 @@
 #include "sac_wide.h"
 #include "sac_pairs.h"
 #include "sac_envs.h"
+#include "sac_plan.h"
 
 // ============================================================================ params / replay
 template <typename T>
@@ -301,79 +303,6 @@ static int fail(int code, const std::string& msg) {
     if (_e != hipSuccess) return fail(SAC_E_HIP, std::string(#x ": ") + hipGetErrorString(_e));    \
   } while (0)
 
-// Workspace offsets of the large-batch stage path (sac_wide.h), from plan()
-struct WideLay {
-  int on = 0, Brw = 0, hp = 0, hq = 0;
-  size_t o_dev = 0, o_jobs = 0;
-  size_t o_xpi0 = 0, o_xq0 = 0, o_xqt0 = 0, o_xc0 = 0, o_r = 0, o_d = 0, o_lp2 = 0, o_piop = 0;
-  size_t o_outpi = 0, o_outq[2] = {0, 0}, o_outqt[2] = {0, 0}, o_outc[2] = {0, 0}, o_da[2] = {0, 0};
-  size_t o_P[5][SAC_DEV_LAYERS] = {};      // phase A pre-activations (pi on [s'; s], Q1, Q2, Q1t, Q2t)
-  size_t o_Pc[2][SAC_DEV_LAYERS] = {};     // phase C critics
-  size_t o_DYq[2][SAC_DEV_LAYERS] = {}, o_DYc[2][SAC_DEV_LAYERS] = {}, o_DYpi[SAC_DEV_LAYERS] = {};
-};
-#define WIDE_MAX_JOBS 64
-
-struct sac_engine {
-  sac_engine_config cfg;
-  sac_engine_buffers buf;
-  EngineDev h;            // host mirror of the device struct
-  EngineDev* d = nullptr; // in workspace
-  TileDesc* tilesB = nullptr;
-  TileDesc* tilesD = nullptr;
-  std::vector<TileDesc> hostB, hostD;
-  int nB = 0, nD = 0;
-  size_t lds_bytes = 0;
-  size_t upd_lds = 0;  // dynamic LDS of an update tile (SAC_UPD_LDS_FOR(upd_slots))
-  int upd_ut_b = SAC_UPD_THREADS;  // phase B's workgroup size (SAC_UPD_UT=512: two per CU, two slots)
-  size_t upd_lds_b = 0;
-  int nrt = 0;
-  int ncu = 256;  // compute units of the device
-  // large-batch stage path (sac_wide.h): layout offsets, stages, jobs
-  WideLay wl;
-  int wide = 0;
-  WideDev wdh;
-  WideDev* wdd = nullptr;
-  WJob* wjobs = nullptr;
-  std::vector<WJob> hostW;
-  struct WStage {
-    int kind;   // 0 gather, 1 GEMM jobs [j0, j1), 2 pi heads, 3 phase B, 4 phase D
-    int j0, j1, grid, phase, last;  // grid: workgroups
-    size_t lds;
-  };
-  std::vector<WStage> wst;
-  // graph cache
-  hipGraphExec_t gexec = nullptr;
-  hipGraph_t graph = nullptr;
-  int gchunk = 0;
-  sac_replay gkey{};
-  hipStream_t cap = nullptr;
-  // loop-graph cache (sac_engine_loop_graph): its own graph, exec and key
-  struct LoopKey {
-    sac_envs envs;
-    sac_replay rb;
-    int64_t* cursor;
-    float* q_ring;
-    int32_t q_ring_steps;
-    std::vector<int32_t> grad;  // gradient steps after each rollout: its size is k_steps
-  };
-  hipGraphExec_t lgexec = nullptr;
-  hipGraph_t lgraph = nullptr;
-  LoopKey lkey{};
-};
-
-static inline int rup(int x, int m) { return (x + m - 1) / m * m; }
-
-
-struct Layout {
-  size_t off = 0;
-  size_t take(size_t bytes) {
-    off = (off + 255) & ~(size_t)255;
-    const size_t o = off;
-    off += bytes;
-    return o;
-  }
-};
-
 static int validate(const sac_engine_config* c) {
   if (!c) return fail(SAC_E_INVALID, "null config");
   if (c->obs_dim < 1 || c->act_dim < 1 || c->act_dim > 32) return fail(SAC_E_INVALID, "obs_dim >= 1, 1 <= act_dim <= 32");
@@ -398,784 +327,6 @@ static int validate(const sac_engine_config* c) {
     return fail(SAC_E_INVALID, "bad layout override (layout 0..3, stage_path -1..1, stage_batch -1..0, "
                                "upd_parts 0..4, upd_threads 0 / 512 / 1024)");
   return SAC_OK;
-}
-
-// Lays out everything; when e != nullptr also fills e->h pointers (base = workspace).
-static void xcd_order(std::vector<TileDesc>& tiles);
-
-
-// The large-batch path's device descriptor, jobs and stage list (sac_wide.h):
-// per step  gather | A forward stages | pi heads | Qt forward stages | critic
-// backward stages | B | C critic forward | critic dX | pi backward | D.
-static void build_wide(sac_engine* e, char* base) {
-  const WideLay& wl = e->wl;
-  const EngineDev& h = e->h;
-  const int esz = e->cfg.precision == SAC_PREC_BF16 ? 2 : 4;
-  auto F = [&](size_t o) { return (float*)(base + o); };
-  WideDev& W = e->wdh;
-  memset(&W, 0, sizeof(W));
-  const int B = h.B, A = h.A, O = h.O, Brw = wl.Brw, hp = wl.hp, hq = wl.hq;
-  const NetDev& np = h.net[NET_PI];
-  const NetDev& nq1 = h.net[NET_Q1];
-  W.B = B;
-  W.Bp = h.Bp;
-  W.Brw = Brw;
-  W.nrt = h.nrt;
-  W.O = O;
-  W.A = A;
-  W.ldpi0 = np.l[0].Kp;
-  W.ldq0 = nq1.l[0].Kp;
-  W.Xpi0 = F(wl.o_xpi0);
-  W.Xq0 = F(wl.o_xq0);
-  W.Xqt0 = F(wl.o_xqt0);
-  W.Xc0 = F(wl.o_xc0);
-  W.R = F(wl.o_r);
-  W.Dn = F(wl.o_d);
-  W.LP2 = F(wl.o_lp2);
-  W.PIOP = F(wl.o_piop);
-  W.ncb_pi = (np.l[hp - 1].Np + 63) / 64;
-  W.ncb_q = (nq1.l[hq - 1].Np + 63) / 64;
-  W.ncb_da = (nq1.l[0].Np + 63) / 64;
-  W.cbs_pi = (long)2 * Brw * 2 * A;
-  W.cbs_q = Brw;
-  W.cbs_da = (long)Brw * A;
-  W.OUTPpi = F(wl.o_outpi);
-  for (int qi = 0; qi < 2; ++qi) {
-    W.OUTPq[qi] = F(wl.o_outq[qi]);
-    W.OUTPqt[qi] = F(wl.o_outqt[qi]);
-    W.OUTPc[qi] = F(wl.o_outc[qi]);
-    W.DA[qi] = F(wl.o_da[qi]);
-    W.GTq_out[qi] = h.net[NET_Q1 + qi].l[hq].GT;
-    W.dbpq_out[qi] = h.net[NET_Q1 + qi].l[hq].dbp;
-  }
-  W.GTpi_out = np.l[hp].GT;
-  W.dbppi_out = np.l[hp].dbp;
-  W.rng_step = e->buf.rng_step;
-  W.stamp_stage = -1;
-#ifdef SAC_STAMPS  // diagnostic build only: the stage that writes stamps (tools/wide_stamps.py)
-  if (const char* v = getenv("SAC_WIDE_STAMP_STAGE")) W.stamp_stage = atoi(v);
-#endif
-  e->wdd = (WideDev*)(base + wl.o_dev);
-  e->wjobs = (WJob*)(base + wl.o_jobs);
-  std::vector<WJob>& JB = e->hostW;
-  JB.clear();
-  e->wst.clear();
-  // the two K-block buffers + the epilogue's weight slices (WWS floats); WA_OUTBWD
-  // adds the row seeds and the output layer's weights
-  // K-block buffers: as many (2..4) as keep the stage's workgroups co-resident
-  // in one round (items / CUs per CU) in 160 KiB of LDS per CU
-  const size_t kbuf = esz == 4 ? WK<float>::BUF : WK<bf16>::BUF;  // floats
-  const int ncu = e->ncu > 0 ? e->ncu : 256;
-  auto stage_gemm = [&](std::vector<WJob> js, int phase, int last) {
-    int item = 0;
-    size_t extra = WWS;  // floats past the K buffers
-    for (WJob& j : js) {
-      if (j.amode != js[0].amode) fprintf(stderr, "sac_engine: internal: mixed A modes in one stage\n"), abort();
-      j.item0 = item;
-      item += j.nrb * j.ncb;
-      if (j.amode == WA_OUTBWD) extra = std::max(extra, (size_t)WWS + 64 * WLDD + (size_t)j.J * j.Kp);
-      if ((j.OUTP && (size_t)j.Nout * WBN > WWS) || (j.DA && (size_t)WBN * A > WWS)) extra = ~(size_t)0 / 64;  // refused
-    }
-    const int per_cu = std::max(1, (item + ncu - 1) / ncu);
-    int nb = 2;
-    for (int b = 4; b > 2; --b)
-      if ((size_t)per_cu * (b * kbuf + extra) * 4 <= 160 * 1024) {
-        nb = b;
-        break;
-      }
-    for (WJob& j : js) j.nbuf = nb;
-    const size_t lf = nb * kbuf + extra;
-    sac_engine::WStage st{1, (int)JB.size(), (int)(JB.size() + js.size()), item, phase, last, lf * 4};
-    e->wst.push_back(st);
-    JB.insert(JB.end(), js.begin(), js.end());
-  };
-  auto fwd = [&](int ni, int l, int M, const float* X, float* Pd, void* XT, int xt_row0, long xt_par, float* OUTP,
-                 int p_row0 = 0) {
-    const NetDev& nd = h.net[ni];
-    const LayerDev& ly = nd.l[l];
-    WJob j;
-    memset(&j, 0, sizeof(j));
-    j.M = M;
-    j.K = ly.K;
-    j.Kp = ly.Kp;
-    j.N = ly.N;
-    j.Np = ly.Np;
-    j.nrb = M / 64;
-    j.ncb = (ly.Np + 63) / 64;
-    j.amode = l == 0 ? WA_PLAIN : WA_ACT;
-    j.aact = nd.hid_act;
-    j.X = X;
-    j.ldx = ly.Kp;
-    j.Wp = ly.Wc;
-    j.tcols = ly.Kp;
-    j.bias = nd.P + ly.b_off;
-    j.emode = WE_FWD;
-    j.P = Pd;
-    j.p_row0 = p_row0;
-    j.ldp = ly.Np;
-    j.oact = nd.hid_act;
-    j.XT = XT;
-    j.xt_row0 = xt_row0;
-    j.xt_ld = h.Bp;
-    j.xt_par = xt_par;
-    if (OUTP) {
-      const LayerDev& lo = nd.l[nd.L - 1];
-      j.Wout = nd.P + lo.w_off;
-      j.ldwout = lo.K;
-      j.Nout = lo.N;
-      j.OUTP = OUTP;
-      j.outp_cb = (long)M * lo.N;
-    }
-    j.pact = -1;
-    return j;
-  };
-  // backward GEMM through layer d: dX_d = dY_d W_d -> dY_{d-1} = act'(P_{d-1}) dX_d
-  auto bwd = [&](int ni, int d, int M, const float* X, bool first, int rowpro, int qi, const float* Pprev, float* DY,
-                 void* GT, float* dbp, float* DA) {
-    const NetDev& nd = h.net[ni];
-    const LayerDev& ly = nd.l[d];
-    const LayerDev& lb = nd.l[d - 1];
-    const LayerDev& lo = nd.l[nd.L - 1];
-    WJob j;
-    memset(&j, 0, sizeof(j));
-    j.M = M;
-    j.K = ly.N;
-    j.Kp = ly.Np;
-    j.N = ly.K;
-    j.Np = ly.Kp;
-    j.nrb = M / 64;
-    j.ncb = (ly.Kp + 63) / 64;
-    j.amode = first ? WA_OUTBWD : WA_PLAIN;
-    j.aact = nd.hid_act;
-    j.X = X;
-    j.ldx = ly.Np;
-    if (first) {
-      j.Wo = nd.P + lo.w_off;
-      j.ldwo = lo.K;
-      j.J = lo.N;
-      j.rowpro = rowpro;
-      j.qi = qi;
-      if (GT) {  // phase A / pi: the generated dY of layer d is a dW operand too
-        j.AGT = ly.GT;
-        j.Adbp = ly.dbp;
-        j.adbp_ld = ly.N;
-      }
-    }
-    j.Wp = ly.WTc;
-    j.tcols = ly.Np;
-    j.emode = WE_BWD;
-    j.Pprev = Pprev;
-    j.ldpp = lb.Np;
-    j.pact = nd.hid_act;
-    j.DY = DY;
-    j.lddy = lb.Np;
-    j.GT = GT;
-    j.gt_ld = h.Bp;
-    j.dbp = dbp;
-    j.dbp_ld = lb.N;
-    if (DA) {
-      const LayerDev& l0 = nd.l[0];
-      j.W0a = nd.P + l0.w_off;
-      j.ldw0 = l0.K;
-      j.a_off = O;
-      j.DA = DA;
-      j.da_cb = (long)Brw * A;
-    }
-    return j;
-  };
-  auto add = [&](int kind, int grid, int phase) {
-    sac_engine::WStage st{kind, 0, 0, grid, phase, 0, 0};
-    e->wst.push_back(st);
-  };
-  // ---- phase A
-  add(0, (B + WGR - 1) / WGR, 0);  // gather
-  for (int d = 0; d < std::max(hp, hq); ++d) {
-    std::vector<WJob> js;
-    if (d < hp)
-      // the last hidden layer's P is read by pi's backward only: actor rows [Brw, 2 Brw)
-      js.push_back(fwd(NET_PI, d, 2 * Brw, d ? F(wl.o_P[0][d - 1]) : W.Xpi0, F(wl.o_P[0][d]), np.l[d + 1].XT, Brw,
-                       np.l[d + 1].xt_par, d == hp - 1 ? W.OUTPpi : nullptr, d == hp - 1 ? Brw : 0));
-    for (int qi = 0; qi < 2; ++qi)
-      if (d < hq)
-        js.push_back(fwd(NET_Q1 + qi, d, Brw, d ? F(wl.o_P[1 + qi][d - 1]) : W.Xq0, F(wl.o_P[1 + qi][d]),
-                         h.net[NET_Q1 + qi].l[d + 1].XT, 0, 0, d == hq - 1 ? W.OUTPq[qi] : nullptr));
-    stage_gemm(js, 0, 0);
-  }
-  {
-    const int AP = A <= 1 ? 1 : 1 << (32 - __builtin_clz(A - 1));
-    const int rpb = WG_T / AP;
-    add(2, (2 * Brw + rpb - 1) / rpb, 0);  // pi heads
-  }
-  for (int d = 0; d < hq; ++d) {
-    std::vector<WJob> js;
-    for (int qi = 0; qi < 2; ++qi)
-      js.push_back(fwd(NET_Q1T + qi, d, Brw, d ? F(wl.o_P[3 + qi][d - 1]) : W.Xqt0,
-                       d < hq - 1 ? F(wl.o_P[3 + qi][d]) : nullptr, nullptr, 0, 0,  // no backward: last P unread
-                       d == hq - 1 ? W.OUTPqt[qi] : nullptr));
-    stage_gemm(js, 0, 0);
-  }
-  for (int d = hq - 1; d >= 1; --d) {
-    std::vector<WJob> js;
-    for (int qi = 0; qi < 2; ++qi) {
-      const NetDev& nq = h.net[NET_Q1 + qi];
-      const bool first = d == hq - 1;
-      js.push_back(bwd(NET_Q1 + qi, d, Brw, first ? F(wl.o_P[1 + qi][d]) : F(wl.o_DYq[qi][d]), first, WR_YSEED, qi,
-                       F(wl.o_P[1 + qi][d - 1]), d - 1 >= 1 ? F(wl.o_DYq[qi][d - 1]) : nullptr, nq.l[d - 1].GT,
-                       nq.l[d - 1].dbp, nullptr));
-    }
-    stage_gemm(js, 0, 0);
-  }
-  add(3, 0, 1);  // phase B
-  // ---- phase C
-  for (int d = 0; d < hq; ++d) {
-    std::vector<WJob> js;
-    for (int qi = 0; qi < 2; ++qi)
-      js.push_back(fwd(NET_Q1 + qi, d, Brw, d ? F(wl.o_Pc[qi][d - 1]) : W.Xc0, F(wl.o_Pc[qi][d]), nullptr, 0, 0,
-                       d == hq - 1 ? W.OUTPc[qi] : nullptr));
-    stage_gemm(js, 2, 0);
-  }
-  for (int d = hq - 1; d >= 1; --d) {
-    std::vector<WJob> js;
-    for (int qi = 0; qi < 2; ++qi) {
-      const bool first = d == hq - 1;
-      js.push_back(bwd(NET_Q1 + qi, d, Brw, first ? F(wl.o_Pc[qi][d]) : F(wl.o_DYc[qi][d]), first, WR_MINQ, qi,
-                       F(wl.o_Pc[qi][d - 1]), d - 1 >= 1 ? F(wl.o_DYc[qi][d - 1]) : nullptr, nullptr, nullptr,
-                       d == 1 ? W.DA[qi] : nullptr));
-    }
-    stage_gemm(js, 2, 0);
-  }
-  for (int d = hp - 1; d >= 1; --d) {
-    const bool first = d == hp - 1;
-    std::vector<WJob> js;
-    js.push_back(bwd(NET_PI, d, Brw, first ? F(wl.o_P[0][d]) + (size_t)Brw * np.l[d].Np : F(wl.o_DYpi[d]), first,
-                     WR_PIHEAD, 0, F(wl.o_P[0][d - 1]) + (size_t)Brw * np.l[d - 1].Np,
-                     d - 1 >= 1 ? F(wl.o_DYpi[d - 1]) : nullptr, np.l[d - 1].GT, np.l[d - 1].dbp, nullptr));
-    stage_gemm(js, 2, d == 1);
-  }
-  add(4, 0, 3);  // phase D
-}
-
-static size_t plan(const sac_engine_config* c, sac_engine* e, char* base) {
-  const int esz = c->precision == SAC_PREC_BF16 ? 2 : 4;
-  // Br: rows of the per-row stashes, whole pairs of row tiles (the pair-tile kernels write 2R rows)
-  const int B = c->batch, Bp = rup(B, 32), nrt = (B + SAC_ROWS - 1) / SAC_ROWS, Br = rup(nrt, 2) * SAC_ROWS;
-  const int O = c->obs_dim, A = c->act_dim;
-  Layout lay;
-  const size_t o_E = lay.take(4096);  // EngineDev, padded for prefetch_engine()
-  EngineDev h;
-  memset(&h, 0, sizeof(h));
-  auto P = [&](size_t o) -> void* { return base ? (void*)(base + o) : nullptr; };
-  int maxKp = 32, maxNo = 32;
-  size_t xt_q0 = 0;
-  const int nrt0 = (B + SAC_ROWS - 1) / SAC_ROWS;
-  // dims-only pre-pass: the padded widths the phase kernels' LDS layout needs
-  EngineDev probe;
-  memset(&probe, 0, sizeof(probe));
-  for (int ni = 0; ni < 5; ++ni) {
-    const bool is_pi = ni == NET_PI;
-    const int L = is_pi ? c->pi_layers : c->q_layers;
-    const int* dims = is_pi ? c->pi_dims : c->q_dims;
-    for (int l = 0; l < L; ++l) {
-      probe.net[ni].l[l].Kp = rup(dims[l], SAC_PAD);
-      probe.net[ni].l[l].Np = rup(dims[l + 1], SAC_PAD);
-      maxKp = std::max(maxKp, probe.net[ni].l[l].Kp);
-      if (l < L - 1) maxKp = std::max(maxKp, probe.net[ni].l[l].Np);
-      else maxNo = std::max(maxNo, probe.net[ni].l[l].Np);
-    }
-  }
-  int split = 0;  // decided below; the layout lambda reads it
-  // pairs: the pair-tile kernels (sac_pairs.h): every per-row buffer 2R rows,
-  // pre-activations for one critic or pi at a time (no P2 / second outputs)
-  auto lds_layout = [&](EngineDev& hh, int xrows, bool full, bool pairs = false) -> int {
-    const int R = pairs ? 2 * SAC_ROWS : SAC_ROWS;
-    hh.ld = maxKp + 4;
-    hh.ldo = maxNo + 4;
-    int lo = 0;
-    auto lt = [&](int floats) {
-      lo = (lo + 3) & ~3;  // 16-B alignment
-      const int o = lo;
-      lo += floats;
-      return o;
-    };
-    hh.o_X = lt(xrows * hh.ld);
-    hh.o_Y = lt(xrows * hh.ld);
-    const int Lhq = c->q_layers - 1, Lhp = c->pi_layers - 1;
-    for (int l = 0; full && l < std::max(Lhq, Lhp); ++l) {
-      int np = 0;
-      if (l < Lhq) np = std::max(np, hh.net[NET_Q1].l[l].Np);
-      if (l < Lhp) np = std::max(np, hh.net[NET_PI].l[l].Np);
-      hh.ldp1[l] = np + 4;
-      hh.o_P1[l] = lt(R * hh.ldp1[l]);
-    }
-    for (int l = 0; full && !pairs && l < Lhq; ++l) {
-      hh.ldp2[l] = hh.net[NET_Q2].l[l].Np + 4;
-      hh.o_P2[l] = lt(R * hh.ldp2[l]);
-    }
-    hh.o_s = lt(R * O);
-    hh.o_s2 = lt(R * O);
-    hh.o_a = lt(R * A);
-    hh.o_a2 = lt(R * A);
-    hh.o_r = lt(R);
-    hh.o_d = lt(R);
-    hh.o_et = lt(R * A);
-    hh.o_ea = lt(R * A);
-    hh.o_out = lt(xrows * hh.ldo);
-    hh.o_outp = lt(xrows * hh.ldo);
-    hh.o_out2 = pairs ? 0 : lt(R * hh.ldo);
-    hh.o_outp2 = pairs ? 0 : lt(R * hh.ldo);
-    hh.o_lp = lt(R);
-    hh.o_qt = lt(2 * R);
-    hh.o_y = lt(R);
-    hh.o_g = lt(pairs ? 2 * R : R * hh.ldo);
-    hh.o_g2 = pairs ? 0 : lt(R * hh.ldo);
-    hh.o_ga = lt(R * A);
-    hh.o_gout = lt(R * hh.ldo);
-    hh.o_slot = lt(2 * R);  // int64[R]
-    hh.o_red = split ? lt(SAC_NW * 256) : 0;
-    return lo;
-  };
-  // does the phase kernels' layout fit a CU?  (per-network roles: R rows; one
-  // block per row tile: pi on [s'; s], 2R rows)
-  const bool lds_fits_roles = (size_t)lds_layout(probe, SAC_ROWS, true) * 4 <= 160 * 1024;
-  const bool lds_fits_rows = (size_t)lds_layout(probe, 2 * SAC_ROWS, true) * 4 <= 160 * 1024;
-  const bool lds_fits_pairs = (size_t)lds_layout(probe, 2 * SAC_ROWS, true, true) * 4 <= 160 * 1024;
-  // hidden-split role kernels (sac_split.h): two hidden layers of width 256 in
-  // both nets, identity pi output, 2 act <= 32, and 12 * nrt co-resident blocks
-  split = lds_fits_roles && c->q_layers == 3 && c->pi_layers == 3 && c->q_dims[1] == SPLIT_H && c->q_dims[2] == SPLIT_H &&
-              c->pi_dims[1] == SPLIT_H && c->pi_dims[2] == SPLIT_H && c->pi_out_act == SAC_ACT_IDENTITY &&
-              2 * A <= 32 && (10 + split_wpi(esz)) * nrt0 <= 256 && (2 * split_wcq(esz) + split_wc(esz) + 1) * nrt0 <= 256 &&
-              SAC_ROWS * (A + 1) <= SAC_HAND_STRIDE;
-  split = split && c->layout == SAC_LAYOUT_AUTO;
-  // batch columns of layer 0's operands under the split: X^T 2 Bp (phase A's two
-  // halves store it), dY^T 2 Bp for the critics (phase A halves), split_wc Bp for
-  // pi (phase C parts)
-  const int wc = split_wc(esz);
-  const int bp0 = split ? 2 * Bp : Bp;
-  const int bp0_pi = split ? wc * Bp : Bp;
-  for (int ni = 0; ni < 5; ++ni) {
-    const bool is_pi = ni == NET_PI;
-    const bool trainable = ni <= NET_Q2;
-    const int L = is_pi ? c->pi_layers : c->q_layers;
-    const int* dims = is_pi ? c->pi_dims : c->q_dims;
-    NetDev& nd = h.net[ni];
-    nd.L = L;
-    nd.hid_act = is_pi ? c->pi_hidden_act : c->q_hidden_act;
-    nd.out_act = is_pi ? c->pi_out_act : c->q_out_act;
-    int off = 0;
-    for (int l = 0; l < L; ++l) {
-      LayerDev& ly = nd.l[l];
-      ly.K = dims[l];
-      ly.N = dims[l + 1];
-      ly.Kp = rup(ly.K, SAC_PAD);
-      ly.Np = rup(ly.N, SAC_PAD);
-      ly.w_off = off;
-      off += ly.K * ly.N;
-      ly.b_off = off;
-      off += ly.N;
-      maxKp = std::max(maxKp, ly.Kp);
-      if (l < L - 1) maxKp = std::max(maxKp, ly.Np);
-      else maxNo = std::max(maxNo, ly.Np);
-      ly.Wc = P(lay.take((size_t)ly.Np * ly.Kp * esz));
-      if (trainable) {
-        const int bpl = l == 0 ? bp0 : Bp;
-        ly.WTc = P(lay.take((size_t)ly.Kp * ly.Np * esz));
-        if (ni == NET_Q2 && l == 0) {
-          ly.XT = P(xt_q0);
-        } else {
-          // pi: two copies by step parity (from the fused step, where phase D of
-          // step k read one while phase A of step k + 1 wrote the other in one
-          // launch; with one phase per launch they only alternate)
-          const size_t o = lay.take((size_t)ly.Kp * bpl * esz * (is_pi ? 2 : 1));
-          if (ni == NET_Q1 && l == 0) xt_q0 = o;
-          ly.XT = P(o);
-          ly.xt_par = is_pi ? (long)ly.Kp * bpl : 0;
-        }
-        const int bpg = (l == 0 && is_pi) ? bp0_pi : bpl;
-        ly.GT = P(lay.take((size_t)ly.Np * bpg * esz));
-        // the update tiles sum the bias gradient from their staged dY^T rows:
-        // no per-row-tile partials (TileDesc / store_T with dbp == null)
-        ly.dbp = nullptr;
-      }
-      if (is_pi) ly.pstash = (float*)P(lay.take((size_t)Br * ly.Np * 4));
-      if (is_pi) ly.pmask = (uint32_t*)P(lay.take((size_t)Br * ((ly.Np + 31) / 32) * 4));
-    }
-  }
-  h.s_st = (float*)P(lay.take((size_t)Br * O * 4));
-  h.a_st = (float*)P(lay.take((size_t)Br * A * 4));
-  h.lp_st = (float*)P(lay.take((size_t)2 * Br * 4));
-  h.head_st = (float*)P(lay.take((size_t)Br * 4 * A * 4));
-  h.lossp = (float*)P(lay.take((size_t)2 * nrt * 4 * 4));
-  h.seedq = (float*)P(lay.take((size_t)2 * Bp * 4));
-  h.adam_sc = (float*)P(lay.take(2 * 6 * 4));
-  h.alpha_sc = (double*)P(lay.take(2 * 2 * 8));
-  h.sync = (uint32_t*)P(lay.take((size_t)(SYNC_FLAGS + HK_COUNT * nrt * 16) * 4));
-  h.hand = (float*)P(lay.take((size_t)HK_COUNT * nrt * SAC_HAND_STRIDE * 4));
-  h.gstride = SAC_ROWS * (A + 1);
-  h.gran = (uint64_t*)P(lay.take((size_t)G_COUNT * nrt * h.gstride * 8));
-  h.stg_stride = (16 + 2 * SAC_ROWS * O + SAC_ROWS * A + 2 * SAC_ROWS + 15) / 16 * 16;
-  h.stg = (float*)P(lay.take((size_t)2 * nrt * h.stg_stride * 4));  // two records per row tile: by step parity
-  h.split = split;
-  h.gs2 = SAC_ROWS * std::max(2 * A, A + 1);
-  h.gran2 = (uint64_t*)P(lay.take((size_t)GS_COUNT * nrt * SPLIT_GP * h.gs2 * 8));
-  // Batch parts of an update tile (TileDesc.kpart): the hidden split's layer 0
-  // reduces over its parts' columns (critics 2: phase A halves; pi wc: phase C
-  // parts); a large batch (Bp > 1024) is split into P <= 4 parts per phase, P
-  // chosen for the fewest block rounds x the longest block: a block takes about
-  // 2 us + its operand bytes at ~25 GB/s (one workgroup per CU; measured on C3:
-  // 1024 fp32 columns = 256 KB of dY^T / X^T in ~12 us), so at C3 (160 critic
-  // tiles, 80 policy tiles) P = 3: 480 blocks (2 rounds) for B and 240 (one) for D.
-  // fp32 hidden-split layer 0: the parts' partial dY summed while staging in one
-  // block (TileDesc.gsum), which also sees every batch column of the tile -- the
-  // seeded bias sums of TileDesc.seed rely on that; bf16: a block per dY part
-  // with a granule hand-off to part 1
-  // fp32 split layer 0 (wc / 2 summed dY parts: the longest tiles of phases D /
-  // B, 5 / 3 operand row sets) is also split into 2 batch parts with a granule
-  // hand-off (the critics' producer parts also hand over their seeded bias
-  // sums): measured D 8.3 -> 7.6 us on C2.  bf16: the parts' bf16 dY added in
-  // fp32 and rounded once while staging, one block per tile (23.1K -> 23.6K
-  // steps/s on C2, B 7.0 -> 6.6, D 6.7 -> 6.2 us, profiles/r04_ab_gsum_bf16_c2.txt)
-  const int pi0_parts = esz == 4 ? 2 : 1, q0_parts = esz == 4 ? 2 : 1;
-  const int TS = 32;  // update tiles are 32 x 32 weight blocks (64 x 64 measured slower at C3: profiles/r04_ab_tile64_c3.txt)
-  // the 32 x 32 tiles sum the bias gradient from their staged dY rows (16-B
-  // LDS reads) instead of loading per-row-tile partials (at C3 256 strided
-  // loads per column made the k0 == 0 tiles the tail of phases B and D): C3
-  // 4.47K -> 4.57K fp32, 7.63K -> 8.0K bf16; C2 19.3K -> 19.5K fp32, 23.45K ->
-  // 24.0K bf16 (profiles/r04_ab_bias_staged.txt)
-  const size_t part_stride = SAC_PART_STRIDE;
-  auto ntiles_of = [&](const LayerDev& ly) { return ((ly.Np + TS - 1) / TS) * ((ly.Kp + TS - 1) / TS); };
-  int tilesBD[2] = {0, 0};  // [critics (B), policy (D)]
-  for (int ni = NET_PI; ni <= NET_Q2; ++ni)
-    for (int l = 0; l < h.net[ni].L; ++l) tilesBD[ni == NET_PI] += ntiles_of(h.net[ni].l[l]);
-  auto batch_parts = [&](int ntiles, int extra) {
-    if (Bp <= 1024) return 1;
-    if (c->upd_parts > 0) return std::min(4, (int)c->upd_parts);
-    int best = 4;
-    double bc = 1e30;
-    for (int P = 2; P <= 4; ++P) {
-      const int rounds = (ntiles * P + extra + 255) / 256;
-      const double c = rounds * (2.0 + 64.0 * rup((Bp + P - 1) / P, 32) * esz / 25e3);  // us
-      if (c < bc - 1e-9) bc = c, best = P;
-    }
-    return best;
-  };
-  const int bpartsB = batch_parts(tilesBD[0], 0);
-  const int bpartsD = batch_parts(tilesBD[1], 1);
-  auto tile_parts = [&](int ni, int l) {
-    if (l == 0 && split) return std::min(ni == NET_PI ? pi0_parts : q0_parts, Bp / 32);
-    return ni == NET_PI ? bpartsD : bpartsB;
-  };
-  int nB = 0, nD = 0, nhalf = 0;
-  for (int ni = NET_PI; ni <= NET_Q2; ++ni)
-    for (int l = 0; l < h.net[ni].L; ++l) {
-      const int t = ntiles_of(h.net[ni].l[l]);
-      const int parts = tile_parts(ni, l);
-      (ni == NET_PI ? nD : nB) += t * parts;
-      nhalf += t * (parts - 1);  // producer parts: one granule slot each
-    }
-  // Layer-synchronous stage path (sac_wide.h): where the phase
-  // kernels' LDS layout does not fit a CU (hidden layers wider than 256, wide
-  // inputs: the stage path takes any width), for nets with at least two hidden
-  // layers.  At C3 the row-tile kernels are faster (profiles/r04_ab_c3_paths.txt),
-  // so they keep the batches they fit; config.stage_path = 1 forces the stage
-  // path on any batch past the hidden split, -1 refuses it.
-  WideLay wl;
-  {
-    const int roles_pre = 6 * nrt0 <= 256 && SAC_ROWS * (A + 1) <= SAC_HAND_STRIDE && c->layout != SAC_LAYOUT_ROWS &&
-                          c->layout != SAC_LAYOUT_PAIRS;
-    const bool too_big = !(roles_pre ? lds_fits_roles : lds_fits_rows);
-    const bool able = !split && c->q_layers >= 3 && c->pi_layers >= 3 && 2 * A <= WJMAX;
-    int on = able && too_big;
-    if (c->stage_path > 0) on = able;
-    if (c->stage_path < 0) on = 0;
-    wl.on = on;
-  }
-  if (wl.on) {
-    const int Brw = rup(B, 64);
-    const NetDev& np = h.net[NET_PI];
-    const NetDev& nq = h.net[NET_Q1];
-    const int hp = c->pi_layers - 1, hq = c->q_layers - 1;
-    wl.Brw = Brw;
-    wl.hp = hp;
-    wl.hq = hq;
-    wl.o_dev = lay.take(sizeof(WideDev));
-    wl.o_jobs = lay.take(WIDE_MAX_JOBS * sizeof(WJob));
-    wl.o_xpi0 = lay.take((size_t)2 * Brw * np.l[0].Kp * 4);
-    wl.o_xq0 = lay.take((size_t)Brw * nq.l[0].Kp * 4);
-    wl.o_xqt0 = lay.take((size_t)Brw * nq.l[0].Kp * 4);
-    wl.o_xc0 = lay.take((size_t)Brw * nq.l[0].Kp * 4);
-    wl.o_r = lay.take((size_t)Brw * 4);
-    wl.o_d = lay.take((size_t)Brw * 4);
-    wl.o_lp2 = lay.take((size_t)Brw * 4);
-    wl.o_piop = lay.take((size_t)Brw * 2 * A * 4);
-    const int ncb_pi = (np.l[hp - 1].Np + 63) / 64, ncb_q = (nq.l[hq - 1].Np + 63) / 64, ncb_da = (nq.l[0].Np + 63) / 64;
-    wl.o_outpi = lay.take((size_t)ncb_pi * 2 * Brw * 2 * A * 4);
-    for (int qi = 0; qi < 2; ++qi) {
-      wl.o_outq[qi] = lay.take((size_t)ncb_q * Brw * 4);
-      wl.o_outqt[qi] = lay.take((size_t)ncb_q * Brw * 4);
-      wl.o_outc[qi] = lay.take((size_t)ncb_q * Brw * 4);
-      wl.o_da[qi] = lay.take((size_t)ncb_da * Brw * A * 4);
-    }
-    for (int l = 0; l < hp; ++l) wl.o_P[0][l] = lay.take((size_t)2 * Brw * np.l[l].Np * 4);
-    for (int l = 1; l + 1 < hp; ++l) wl.o_DYpi[l] = lay.take((size_t)Brw * np.l[l].Np * 4);
-    for (int qi = 0; qi < 2; ++qi) {
-      for (int l = 0; l < hq; ++l) {
-        const size_t bytes = (size_t)Brw * nq.l[l].Np * 4;
-        wl.o_P[1 + qi][l] = lay.take(bytes);
-        wl.o_P[3 + qi][l] = lay.take(bytes);
-        wl.o_Pc[qi][l] = lay.take(bytes);
-      }
-      for (int l = 1; l + 1 < hq; ++l) {
-        wl.o_DYq[qi][l] = lay.take((size_t)Brw * nq.l[l].Np * 4);
-        wl.o_DYc[qi][l] = lay.take((size_t)Brw * nq.l[l].Np * 4);
-      }
-    }
-  }
-  const size_t o_tB = lay.take((size_t)nB * sizeof(TileDesc));
-  const size_t o_tD = lay.take((size_t)nD * sizeof(TileDesc));
-  const size_t o_part = lay.take((size_t)nhalf * part_stride * 8);  // batch-part partial dW granules
-  const size_t total = lay.take(0);
-
-  // LDS layout (floats) of the row-tile / role kernels (policy_act included).
-  // role split of phases A/C (decided here: it sizes the LDS): 6 * nrt
-  // workgroups must be co-resident (one per CU).  Only the one-block-per-row-
-  // tile kernels run pi on [s'; s] (2R rows); with roles every MLP pass is R rows.
-  // The stage path (wl.on) launches none of them but policy_act: R rows, no
-  // pre-activation buffers.
-  int roles = 6 * nrt <= 256 && SAC_ROWS * (A + 1) <= SAC_HAND_STRIDE && c->layout != SAC_LAYOUT_ROWS &&
-              c->layout != SAC_LAYOUT_PAIRS;
-  roles = roles && !wl.on;
-  // pair-tile kernels (sac_pairs.h): two row tiles and one group of networks per
-  // workgroup; the critics' seeds are applied by phase B (TileDesc::seed).  The
-  // default past the role split wherever its LDS layout fits: C3 4.66K -> 4.90K
-  // steps/s fp32, 8.26K -> 9.58K bf16 (profiles/r05_ab_pair_tiles_c3.txt)
-  const int pairs = !split && !roles && !wl.on &&
-                    (c->layout == SAC_LAYOUT_PAIRS || c->layout == SAC_LAYOUT_AUTO) && lds_fits_pairs &&
-                    SAC_ROWS * (A + 1) <= SAC_HAND_STRIDE &&
-                    SAC_ROWS * (2 * O + A + 2) <= 4 * SAC_THREADS;  // pair_batch: a record in 4 loads per thread
-  const int lo = pairs ? lds_layout(h, 2 * SAC_ROWS, true, true)
-                       : lds_layout(h, wl.on || roles ? SAC_ROWS : 2 * SAC_ROWS, !wl.on);
-
-  if (e) {
-    h.B = B;
-    h.Bp = Bp;
-    h.Br = Br;
-    h.O = O;
-    h.A = A;
-    h.nrt = nrt;
-    {
-      int xs = 1;  // largest power of two <= 8 with nrt * xs <= 256 blocks
-      while (xs < 8 && nrt * xs * 2 <= 256) xs *= 2;
-      h.xs = xs;
-      // phase A's weight parts on one or two XCDs each: A's fetched bytes 11.0 -> 5.1
-      // MB per launch, phase B 8.6 -> 8.1 us, +1.2% steps/s (C2 fp32,
-      // profiles/r03_ab_role_xcd.txt)
-      h.role_xcd = split && (10 + split_wpi(esz)) * nrt % 8 == 0;
-      // role split of phases A/C: 6 * nrt workgroups must be co-resident (one per CU)
-      h.roles = roles;
-      h.pairs = pairs;
-      // phase C stages the next step's batch (config.stage_batch = -1 turns it off)
-      h.stage = c->stage_batch >= 0;
-    }
-    h.auto_entropy = c->auto_entropy;
-    h.alpha_update = 1;
-    h.gamma = c->gamma;
-    h.tau = c->tau;
-    h.ls_min = c->log_std_min;
-    h.ls_max = c->log_std_max;
-    h.scale = c->action_scale;
-    h.actor_lr = c->actor_lr;
-    h.critic_lr = c->critic_lr;
-    h.beta1 = c->beta1;
-    h.beta2 = c->beta2;
-    h.adam_eps = c->adam_eps;
-    h.target_entropy = c->target_entropy;
-    h.alpha_lr = c->alpha_lr;
-    h.seed = c->seed;
-    h.spin_limit = 1 << 22;
-    float* parts[5] = {e->buf.pi, e->buf.q1, e->buf.q2, e->buf.q1t, e->buf.q2t};
-    float* ms[3] = {e->buf.pi_m, e->buf.q1_m, e->buf.q2_m};
-    float* vs[3] = {e->buf.pi_v, e->buf.q1_v, e->buf.q2_v};
-    for (int ni = 0; ni < 5; ++ni) {
-      h.net[ni].P = parts[ni];
-      h.net[ni].M = ni < 3 ? ms[ni] : nullptr;
-      h.net[ni].V = ni < 3 ? vs[ni] : nullptr;
-      for (int l = 0; l < h.net[ni].L; ++l) h.net[ni].l[l].bias = parts[ni] + h.net[ni].l[l].b_off;
-    }
-    h.alpha_state = e->buf.alpha_state;
-    h.opt_steps = e->buf.opt_steps;
-    h.rng_step = e->buf.rng_step;
-    h.stats = e->buf.stats;
-    e->h = h;
-    e->d = (EngineDev*)(base + o_E);
-    e->tilesB = (TileDesc*)(base + o_tB);
-    e->tilesD = (TileDesc*)(base + o_tD);
-    e->nB = nB;
-    e->nD = nD;
-    e->h.tilesB = e->tilesB;
-    e->h.tilesD = e->tilesD;
-    e->h.nB = nB;
-    e->h.nD = nD;
-    e->lds_bytes = (size_t)lo * 4;
-    {  // update tiles stage up to 2 batch chunks of 512 B per operand row per round
-       // (every tile reduces over at most Bp columns: split layer 0 is two half tiles)
-      const int bch = 512 / esz;
-      e->h.upd_slots = std::min(2, (Bp + bch - 1) / bch);
-      e->upd_lds = SAC_UPD_LDS_FOR(e->h.upd_slots);
-      // phase B in 2 rounds of 1024-thread blocks (C3: 480 blocks) -> 512-thread
-      // blocks with 2 slots, two per CU, one round: C3 B 37.0 -> 33.5 us fp32,
-      // 20.0 -> 18.1 bf16 (profiles/r04_ab_upd_ut512_c3.txt); config.upd_threads =
-      // 512 / 1024 forces it (no summed layer-0 tiles: GS 1 only, so never with the
-      // hidden split)
-      int ut512 = nB > 256 && nB <= 512;
-      if (c->upd_threads) ut512 = c->upd_threads == 512;
-      e->upd_ut_b = SAC_UPD_THREADS;
-      e->upd_lds_b = e->upd_lds;
-      if (ut512 && !split) {
-        e->upd_ut_b = 512;
-        e->upd_lds_b = SAC_UPD_LDS_FOR(1);  // one slot (sac_phases.h, dw_adam_tile)
-      }
-    }
-    e->nrt = nrt;
-    // self-contained update tiles (phase B: critics + Polyak, phase D: policy)
-    const int esz2 = esz;
-    e->hostB.clear();
-    e->hostD.clear();
-    std::vector<TileDesc> halvesB, halvesD;
-    int ihalf = 0;
-    for (int ni = NET_PI; ni <= NET_Q2; ++ni) {
-      const NetDev& nd = h.net[ni];
-      const NetDev& tn = h.net[ni == NET_PI ? NET_PI : ni + 2];
-      for (int l = 0; l < nd.L; ++l) {
-        const LayerDev& ly = nd.l[l];
-        for (int nt = 0; nt < (ly.Np + TS - 1) / TS; ++nt)
-          for (int kt = 0; kt < (ly.Kp + TS - 1) / TS; ++kt) {
-            TileDesc t;
-            memset(&t, 0, sizeof(t));
-            const int bpl = (l == 0 && split) ? 2 * Bp : Bp;                     // X^T row stride
-            const int bpg = (l == 0 && split) ? (ni == NET_PI ? wc : 2) * Bp : Bp;  // dY^T row stride
-            t.GT = (const char*)ly.GT + (size_t)nt * TS * bpg * esz2;
-            t.XT = (const char*)ly.XT + (size_t)kt * TS * bpl * esz2;
-            t.W = nd.P + ly.w_off;
-            t.Wm = nd.M + ly.w_off;
-            t.Wv = nd.V + ly.w_off;
-            t.b = nd.P + ly.b_off;
-            t.bm = nd.M + ly.b_off;
-            t.bv = nd.V + ly.b_off;
-            t.Wc = ly.Wc;
-            t.WTc = ly.WTc;
-            if (ni != NET_PI) {
-              t.tW = tn.P + ly.w_off;
-              t.tb = tn.P + ly.b_off;
-              t.tWc = tn.l[l].Wc;
-            }
-            t.xt_par = ly.xt_par;
-            t.bp = (l == 0 && split) ? 2 * Bp : Bp;
-            t.K = ly.K;
-            t.N = ly.N;
-            t.Kp = ly.Kp;
-            t.Np = ly.Np;
-            t.n0 = nt * TS;
-            t.k0 = kt * TS;
-            t.opt = ni;
-            t.ld = t.bp;
-            t.ldx = t.bp;
-            t.kpart = 0;
-            t.nparts = 1;
-            t.gsum = 1;
-            t.goff = 0;
-            t.seed = nullptr;
-            if ((split || pairs) && ni != NET_PI) t.seed = h.seedq + (size_t)(ni - NET_Q1) * Bp;
-            if (l == 0 && split) {  // one block: dY parts [p Bp, (p+1) Bp) summed, X^T [0, Bp)
-              t.gsum = ni == NET_PI ? wc : 2;
-              t.goff = Bp;
-              t.bp = Bp;
-              t.ld = bpg;
-              t.ldx = 2 * Bp;
-            }
-            const int parts = tile_parts(ni, l);
-            if (parts > 1) {
-              // consumer part 1 (batch columns [0, bpp)) + producer parts 2..P ([(p-1) bpp, p bpp));
-              // split layer 0 (gsum): batch parts of the summed operands
-              const int total = Bp;
-              const int bpp = rup((Bp + parts - 1) / parts, 32);
-              if (!(l == 0 && split)) {
-                t.ld = Bp;
-                t.ldx = Bp;
-              }
-              t.bp = bpp;
-              t.kpart = 1;
-              t.nparts = parts;
-              t.part = (uint64_t*)(base + o_part) + (size_t)ihalf * part_stride;
-              ihalf += parts - 1;
-              for (int pp = 2; pp <= parts; ++pp) {
-                TileDesc pt = t;
-                const int off = (pp - 1) * bpp;
-                pt.kpart = pp;
-                pt.bp = std::min(bpp, total - off);
-                pt.GT = (const char*)t.GT + (size_t)off * esz2;
-                pt.XT = (const char*)t.XT + (size_t)off * esz2;
-                if (t.seed) pt.seed = t.seed + off;
-                (ni == NET_PI ? halvesD : halvesB).push_back(pt);
-              }
-            }
-            (ni == NET_PI ? e->hostD : e->hostB).push_back(t);
-          }
-      }
-    }
-    auto order = [&](std::vector<TileDesc>& cons, std::vector<TileDesc>& prod) {
-      xcd_order(cons);
-      // producer parts first: in-order dispatch starts every producer before its consumer
-      cons.insert(cons.begin(), prod.begin(), prod.end());
-    };
-    order(e->hostB, halvesB);
-    order(e->hostD, halvesD);
-    e->h.nBq[0] = e->h.nBq[1] = 0;
-    for (const TileDesc& t : e->hostB) ++e->h.nBq[t.opt - 1];
-    e->wl = wl;
-    e->wide = wl.on;
-    if (wl.on) build_wide(e, base);
-  }
-  return total + 256;
-}
-
-// Update-tile order for the XCDs (speed only; any order gives the same bits).
-// Blocks are dealt round-robin to the 8 XCDs (block b on XCD b % 8), and the
-// dW operands come from other XCDs' L2s (fetched through the Infinity Fabric
-// at ~11 B/cycle per CU). A layer's tile (nt, kt) reads dY^T rows nt and X^T
-// rows kt; tiles sharing them on one XCD fetch them once into that L2. So each
-// net's tiles are bucketed by XCD -- a 256x256 layer's 8x8 tiles as 2 nt x 4 kt
-// blocks per XCD (6 row groups fetched per XCD instead of 16), one-column /
-// one-row layers dealt across the XCDs -- and emitted so that position p holds
-// a tile of bucket p % 8.
-static void xcd_order(std::vector<TileDesc>& tiles) {
-  std::vector<TileDesc> out;
-  out.reserve(tiles.size());
-  size_t i = 0;
-  while (i < tiles.size()) {
-    size_t j = i;  // one net: consecutive tiles of the same optimizer
-    while (j < tiles.size() && tiles[j].opt == tiles[i].opt) ++j;
-    std::vector<TileDesc> bucket[8];
-    for (size_t t = i; t < j; ++t) {
-      const TileDesc& d = tiles[t];
-      const int NT = d.Np / 32, KT = d.Kp / 32, nt = d.n0 / 32, kt = d.k0 / 32;
-      int x;
-      if (KT == 1) x = nt % 8;
-      else if (NT == 1) x = kt % 8;
-      else if (NT >= 4 && KT >= 2) x = (nt * 4 / NT) * 2 + (kt * 2 / KT);
-      else x = (nt * KT + kt) % 8;
-      bucket[x].push_back(d);
-    }
-    size_t taken[8] = {0};
-    for (size_t left = j - i; left;) {
-      for (int x = 0; x < 8; ++x)
-        if (taken[x] < bucket[x].size()) {
-          out.push_back(bucket[x][taken[x]++]);
-          --left;
-        }
-    }
-    i = j;
-  }
-  tiles.swap(out);
 }
 
 template <typename T>
@@ -1217,45 +368,46 @@ __global__ void sac_spin_kernel(long long ticks) {
   while (__builtin_amdgcn_s_memrealtime() - t0 < ticks) __builtin_amdgcn_s_sleep(8);
 }
 
-// Launch kinds of a step: A B C D.
-enum LaunchKind { L_A = 0, L_B = 1, L_C = 2, L_D = 3 };
+// fn<T>(args) with T the engine's MFMA operand type: the one precision fork of
+// the step's launches.  (A macro, not a template over a generic lambda: the
+// kernels are instantiated in the order these forks name them, and the code
+// object lists them in that order.)
+#define BY_PRECISION(e, fn, ...) \
+  ((e)->cfg.precision == SAC_PREC_BF16 ? fn<bf16>(__VA_ARGS__) : fn<float>(__VA_ARGS__))
 
+// One phase launch of the row-tile / role / pair paths (and B, D of the stage
+// path): the kernel of the engine's path on the geometry plan_launches() made.
 template <typename T>
 static void launch_kind(sac_engine* e, int kind, const sac_replay* rb, const int32_t* idx, const float* eps,
                         hipStream_t s) {
-  const size_t lf = std::max(e->lds_bytes, e->upd_lds);
-  const int stg = e->h.stage ? e->nrt : 0;  // stager blocks of phase C
+  const PhaseLaunch& L = e->launch[kind];
   switch (kind) {
     case L_A:
-      if (e->h.split)
-        sac_target_critic_split<T><<<e->nrt * (10 + split_wpi((int)sizeof(T))), SAC_THREADS, lf, s>>>(e->d, *rb, idx,
-                                                                                                  eps);
-      else if (e->h.roles)
-        sac_target_critic<T, true><<<e->nrt * 6, SAC_THREADS, lf, s>>>(e->d, *rb, idx, eps);
-      else if (e->h.pairs)
-        sac_target_critic_pairs<T><<<2 * ((e->nrt + 1) / 2), SAC_THREADS, lf, s>>>(e->d, *rb, idx, eps);
-      else
-        sac_target_critic<T, false><<<e->nrt * e->h.xs, SAC_THREADS, lf, s>>>(e->d, *rb, idx, eps);
+      switch (e->path) {
+        case PATH_SPLIT: sac_target_critic_split<T><<<L.grid, L.threads, L.lds, s>>>(e->d, *rb, idx, eps); break;
+        case PATH_ROLES: sac_target_critic<T, true><<<L.grid, L.threads, L.lds, s>>>(e->d, *rb, idx, eps); break;
+        case PATH_PAIRS: sac_target_critic_pairs<T><<<L.grid, L.threads, L.lds, s>>>(e->d, *rb, idx, eps); break;
+        case PATH_ROWS: sac_target_critic<T, false><<<L.grid, L.threads, L.lds, s>>>(e->d, *rb, idx, eps); break;
+        case PATH_WIDE: break;  // its stages: launch_wide
+      }
       break;
     case L_B:
-      if (e->upd_ut_b == 512)
-        sac_critic_update<T, 512><<<e->nB, 512, e->upd_lds_b, s>>>(e->d, e->tilesB);
+      if (L.threads == 512)
+        sac_critic_update<T, 512><<<L.grid, 512, L.lds, s>>>(e->d, e->tilesB);
       else
-        sac_critic_update<T><<<e->nB, SAC_UPD_THREADS, e->upd_lds, s>>>(e->d, e->tilesB);
+        sac_critic_update<T><<<L.grid, L.threads, L.lds, s>>>(e->d, e->tilesB);
       break;
     case L_C:
-      if (e->h.split)
-        sac_actor_split<T><<<e->nrt * (2 * split_wcq((int)sizeof(T)) + split_wc((int)sizeof(T))) + stg, SAC_THREADS,
-                             lf, s>>>(e->d, *rb);
-      else if (e->h.roles)
-        sac_actor<T, true><<<e->nrt * 3 + stg, SAC_THREADS, lf, s>>>(e->d, *rb);
-      else if (e->h.pairs)
-        sac_actor_pairs<T><<<2 * ((e->nrt + 1) / 2) + stg, SAC_THREADS, lf, s>>>(e->d, *rb);
-      else
-        sac_actor<T, false><<<e->nrt * e->h.xs + stg, SAC_THREADS, lf, s>>>(e->d, *rb);
+      switch (e->path) {
+        case PATH_SPLIT: sac_actor_split<T><<<L.grid, L.threads, L.lds, s>>>(e->d, *rb); break;
+        case PATH_ROLES: sac_actor<T, true><<<L.grid, L.threads, L.lds, s>>>(e->d, *rb); break;
+        case PATH_PAIRS: sac_actor_pairs<T><<<L.grid, L.threads, L.lds, s>>>(e->d, *rb); break;
+        case PATH_ROWS: sac_actor<T, false><<<L.grid, L.threads, L.lds, s>>>(e->d, *rb); break;
+        case PATH_WIDE: break;
+      }
       break;
     case L_D:
-      sac_actor_update<T><<<e->nD + 1, SAC_UPD_THREADS, e->upd_lds, s>>>(e->d, e->tilesD, e->nD);
+      sac_actor_update<T><<<L.grid, L.threads, L.lds, s>>>(e->d, e->tilesD, e->nD);
       break;
   }
 }
@@ -1296,54 +448,44 @@ static void launch_wide_stage(sac_engine* e, const sac_engine::WStage& st, const
 }
 static void launch_wide(sac_engine* e, const sac_engine::WStage& st, const sac_replay* rb, const int32_t* idx,
                         const float* eps, hipStream_t s, bool stage_next = false, const int32_t* next_idx = nullptr) {
-  if (e->cfg.precision == SAC_PREC_BF16)
-    launch_wide_stage<bf16>(e, st, rb, idx, eps, s, stage_next, next_idx);
-  else
-    launch_wide_stage<float>(e, st, rb, idx, eps, s, stage_next, next_idx);
+  BY_PRECISION(e, launch_wide_stage, e, st, rb, idx, eps, s, stage_next, next_idx);
+}
+
+// What time_phases keeps of a launch: its phase and an event after it.
+static void after_launch(int phase, hipStream_t s, std::vector<int>* kinds, std::vector<hipEvent_t>* ev) {
+  if (kinds) kinds->push_back(phase);
+  if (ev) {
+    hipEvent_t x;
+    (void)hipEventCreate(&x);
+    (void)hipEventRecord(x, s);
+    ev->push_back(x);
+  }
 }
 
 // The launches of n consecutive steps (and, per launch, its kind in *kinds).
 static void launch_steps(sac_engine* e, const sac_replay* rb, int n, const int32_t* indices, const float* eps,
                          hipStream_t s, std::vector<int>* kinds = nullptr, std::vector<hipEvent_t>* ev = nullptr) {
   const size_t B = e->cfg.batch, A = e->cfg.act_dim;
-  auto go = [&](int kind, int step) {
-    const int32_t* ix = indices ? indices + (size_t)step * B : nullptr;
-    const float* ep = eps ? eps + (size_t)step * 2 * B * A : nullptr;
-    if (e->cfg.precision == SAC_PREC_BF16)
-      launch_kind<bf16>(e, kind, rb, ix, ep, s);
-    else
-      launch_kind<float>(e, kind, rb, ix, ep, s);
-    if (kinds) kinds->push_back(kind);
-    if (ev) {
-      hipEvent_t x;
-      (void)hipEventCreate(&x);
-      (void)hipEventRecord(x, s);
-      ev->push_back(x);
-    }
-  };
-  if (e->wide) {  // the stage sequence of sac_wide.h per step
-    for (int i = 0; i < n; ++i) {
-      const int32_t* ix = indices ? indices + (size_t)i * B : nullptr;
-      const float* ep = eps ? eps + (size_t)i * 2 * B * A : nullptr;
-      // step i > 0 of the call uses the batch step i - 1 gathered in its last phase-C stage
-      const bool next = i + 1 < n;
-      const int32_t* nix = indices && next ? indices + (size_t)(i + 1) * B : nullptr;
-      for (const sac_engine::WStage& st : e->wst) {
-        if (st.kind == 0 && i > 0) continue;
-        launch_wide(e, st, rb, ix, ep, s, next, nix);
-        if (kinds) kinds->push_back(st.phase);
-        if (ev) {
-          hipEvent_t x;
-          (void)hipEventCreate(&x);
-          (void)hipEventRecord(x, s);
-          ev->push_back(x);
-        }
+  for (int i = 0; i < n; ++i) {
+    const int32_t* ix = indices ? indices + (size_t)i * B : nullptr;
+    const float* ep = eps ? eps + (size_t)i * 2 * B * A : nullptr;
+    if (e->path != PATH_WIDE) {
+      for (int k = L_A; k <= L_D; ++k) {
+        BY_PRECISION(e, launch_kind, e, k, rb, ix, ep, s);
+        after_launch(k, s, kinds, ev);
       }
+      continue;
     }
-    return;
+    // the stage sequence of sac_wide.h: step i > 0 of the call uses the batch
+    // step i - 1 gathered in its last phase-C stage
+    const bool next = i + 1 < n;
+    const int32_t* nix = indices && next ? indices + (size_t)(i + 1) * B : nullptr;
+    for (const sac_engine::WStage& st : e->wst) {
+      if (st.kind == 0 && i > 0) continue;
+      launch_wide(e, st, rb, ix, ep, s, next, nix);
+      after_launch(st.phase, s, kinds, ev);
+    }
   }
-  for (int i = 0; i < n; ++i)
-    for (int k = L_A; k <= L_D; ++k) go(k, i);
 }
 
 static int check_replay(sac_engine* e, const sac_replay* rb) {
@@ -1373,6 +515,36 @@ static int check_envs(const sac_envs* ev, bool need_ring) {
   return SAC_OK;
 }
 
+// An explicit layout override the planner could not honour (choose_path).
+static int fail_refused(const char* refused) {
+  return fail(SAC_E_INVALID, std::string("layout override cannot be honoured: ") + refused);
+}
+
+// What sac_engine_create refuses of a finished plan, before its first HIP call.
+static int check_plan(const sac_engine* e) {
+  const sac_engine_config* c = &e->cfg;
+  if (std::max(e->lds_bytes, e->upd_lds) > 160 * 1024) {
+    const size_t lb = e->lds_bytes;
+    return fail(SAC_E_INVALID, "layer widths need " + std::to_string(lb) + " B of LDS per workgroup (max 163840)");
+  }
+  if (e->path == PATH_WIDE) {
+    // the stage launches' LDS, and the batch gather's [WGR][obs + act] rows + slots
+    size_t mx = (size_t)((WGR * (c->obs_dim + c->act_dim) + 1) & ~1) * 4 + WGR * 8;
+    for (const sac_engine::WStage& st : e->wst) mx = std::max(mx, st.lds);
+    if (e->hostW.size() > WIDE_MAX_JOBS || mx > 160 * 1024) {
+      const std::string m = "internal: stage path plans " + std::to_string(e->hostW.size()) + " jobs, " +
+                            std::to_string(mx) + " B of LDS";
+      return fail(SAC_E_INVALID, m);
+    }
+  }
+  if ((int)e->hostB.size() != e->nB || (int)e->hostD.size() != e->nD) {  // the grids launch nB / nD tiles
+    const std::string m = "internal: update tiles planned " + std::to_string(e->nB) + " / " + std::to_string(e->nD) +
+                          ", built " + std::to_string(e->hostB.size()) + " / " + std::to_string(e->hostD.size());
+    return fail(SAC_E_INVALID, m);
+  }
+  return SAC_OK;
+}
+
 extern "C" {
 
 const char* sac_last_error(void) { return g_err.c_str(); }
@@ -1380,7 +552,7 @@ const char* sac_version(void) { return SAC_VERSION; }
 
 size_t sac_engine_workspace_bytes(const sac_engine_config* cfg) {
   if (validate(cfg) != SAC_OK) return 0;
-  return plan(cfg, nullptr, nullptr);
+  return plan(cfg, nullptr, nullptr).bytes;  // also of a refused override: create reports that
 }
 
 const char* sac_phase_kernel_name(int32_t phase) {
@@ -1418,13 +590,15 @@ int sac_engine_create(const sac_engine_config* cfg, const sac_engine_buffers* bu
   *out = nullptr;
   int rc = validate(cfg);
   if (rc) return rc;
-  const size_t need = plan(cfg, nullptr, nullptr);
+  const PlanSize sized = plan(cfg, nullptr, nullptr);
+  const size_t need = sized.bytes;
   if (!buf->workspace || buf->workspace_bytes < need)
     return fail(SAC_E_INVALID, "workspace too small: need " + std::to_string(need) + " bytes");
   if (((uintptr_t)buf->workspace) & 255) return fail(SAC_E_INVALID, "workspace must be 256-byte aligned");
   if (!buf->pi || !buf->q1 || !buf->q2 || !buf->q1t || !buf->q2t || !buf->pi_m || !buf->pi_v || !buf->q1_m ||
       !buf->q1_v || !buf->q2_m || !buf->q2_v || !buf->alpha_state || !buf->opt_steps || !buf->rng_step || !buf->stats)
     return fail(SAC_E_INVALID, "null device buffer");
+  if (sized.refused) return fail_refused(sized.refused);
   sac_engine* e = new sac_engine();
   e->cfg = *cfg;
   e->buf = *buf;
@@ -1435,38 +609,10 @@ int sac_engine_create(const sac_engine_config* cfg, const sac_engine_buffers* bu
       e->ncu = n;
   }
   plan(cfg, e, (char*)buf->workspace);
-  {  // an explicit layout override runs the kernels it names or fails (as stage_path = -1 does)
-    const bool rows = !e->h.split && !e->h.roles && !e->h.pairs && !e->wide;
-    const char* miss = nullptr;
-    if (cfg->layout == SAC_LAYOUT_ROLES && !e->h.roles) miss = "roles (needs 6 * row tiles <= 256 co-resident workgroups)";
-    if (cfg->layout == SAC_LAYOUT_PAIRS && !e->h.pairs) miss = "pairs (the pair-tile LDS layout or record does not fit)";
-    if (cfg->layout == SAC_LAYOUT_ROWS && !rows) miss = "rows (the row-tile LDS layout does not fit: stage path)";
-    if (miss) {
-      delete e;
-      return fail(SAC_E_INVALID, std::string("layout override cannot be honoured: ") + miss);
-    }
-  }
-  if (std::max(e->lds_bytes, e->upd_lds) > 160 * 1024) {
-    const size_t lb = e->lds_bytes;
+  rc = check_plan(e);
+  if (rc) {
     delete e;
-    return fail(SAC_E_INVALID, "layer widths need " + std::to_string(lb) + " B of LDS per workgroup (max 163840)");
-  }
-  if (e->wide) {
-    // the stage launches' LDS, and the batch gather's [WGR][obs + act] rows + slots
-    size_t mx = (size_t)((WGR * (cfg->obs_dim + cfg->act_dim) + 1) & ~1) * 4 + WGR * 8;
-    for (const sac_engine::WStage& st : e->wst) mx = std::max(mx, st.lds);
-    if (e->hostW.size() > WIDE_MAX_JOBS || mx > 160 * 1024) {
-      const std::string m = "internal: stage path plans " + std::to_string(e->hostW.size()) + " jobs, " +
-                            std::to_string(mx) + " B of LDS";
-      delete e;
-      return fail(SAC_E_INVALID, m);
-    }
-  }
-  if ((int)e->hostB.size() != e->nB || (int)e->hostD.size() != e->nD) {  // the grids launch nB / nD tiles
-    const std::string m = "internal: update tiles planned " + std::to_string(e->nB) + " / " + std::to_string(e->nD) +
-                          ", built " + std::to_string(e->hostB.size()) + " / " + std::to_string(e->hostD.size());
-    delete e;
-    return fail(SAC_E_INVALID, m);
+    return rc;
   }
   if (cfg->precision == SAC_PREC_BF16)
     set_lds_attrs<bf16>(e->lds_bytes);
@@ -1477,8 +623,9 @@ int sac_engine_create(const sac_engine_config* cfg, const sac_engine_buffers* bu
   if (err == hipSuccess) err = hipMemcpyAsync(e->d, &e->h, sizeof(EngineDev), hipMemcpyHostToDevice, s);
   if (err == hipSuccess) err = hipMemcpyAsync(e->tilesB, e->hostB.data(), e->hostB.size() * sizeof(TileDesc), hipMemcpyHostToDevice, s);
   if (err == hipSuccess) err = hipMemcpyAsync(e->tilesD, e->hostD.data(), e->hostD.size() * sizeof(TileDesc), hipMemcpyHostToDevice, s);
-  if (err == hipSuccess && e->wide) err = hipMemcpyAsync(e->wdd, &e->wdh, sizeof(WideDev), hipMemcpyHostToDevice, s);
-  if (err == hipSuccess && e->wide)
+  const bool wide = e->path == PATH_WIDE;
+  if (err == hipSuccess && wide) err = hipMemcpyAsync(e->wdd, &e->wdh, sizeof(WideDev), hipMemcpyHostToDevice, s);
+  if (err == hipSuccess && wide)
     err = hipMemcpyAsync(e->wjobs, e->hostW.data(), e->hostW.size() * sizeof(WJob), hipMemcpyHostToDevice, s);
   if (err == hipSuccess) err = hipStreamSynchronize(s);
   if (err != hipSuccess) {
@@ -2030,18 +1177,86 @@ int sac_debug_eps_device(uint64_t seed, uint64_t step, int32_t batch, int32_t ac
   return SAC_OK;
 }
 
-int sac_engine_uses_roles(const sac_engine* e) { return e && e->h.roles ? 1 : 0; }
+// The plan of a config as JSON, with no HIP call (include/sac_engine_testing.h).
+int sac_debug_plan_host(const sac_engine_config* cfg, int32_t ncu, char* out, size_t cap) {
+  if (!out) return fail(SAC_E_INVALID, "null argument");
+  int rc = validate(cfg);
+  if (rc) return rc;
+  if (ncu < 1) return fail(SAC_E_INVALID, "ncu >= 1");
+  sac_engine e;
+  e.cfg = *cfg;
+  e.ncu = ncu;
+  // the fifteen parameter buffers are the struct's first fifteen pointers, in order
+  void* fake[15];
+  for (int i = 0; i < 15; ++i) fake[i] = (void*)(uintptr_t)(SAC_PLAN_FAKE_BUFFER0 + i * SAC_PLAN_FAKE_BUFFER_STEP);
+  static_assert(offsetof(sac_engine_buffers, workspace) == sizeof(fake), "fifteen pointers before the workspace");
+  memcpy(&e.buf, fake, sizeof(fake));
+  e.buf.workspace = (void*)(uintptr_t)SAC_PLAN_FAKE_WORKSPACE;
+  const PlanSize sized = plan(cfg, nullptr, nullptr);
+  if (sized.refused) return fail_refused(sized.refused);
+  e.buf.workspace_bytes = sized.bytes;
+  plan(cfg, &e, (char*)e.buf.workspace);
+  rc = check_plan(&e);
+  if (rc) return rc;
+  auto fnv = [](const void* p, size_t n) {  // FNV-1a 64
+    uint64_t hsh = 0xcbf29ce484222325ull;
+    for (size_t i = 0; i < n; ++i) hsh = (hsh ^ ((const unsigned char*)p)[i]) * 0x100000001b3ull;
+    char b[20];
+    snprintf(b, sizeof(b), "\"%016llx\"", (unsigned long long)hsh);
+    return std::string(b);
+  };
+  auto kv = [](const char* k, unsigned long long v) { return "\"" + std::string(k) + "\": " + std::to_string(v); };
+  const bool wide = e.path == PATH_WIDE;
+  const char* paths[] = {"split", "roles", "pairs", "rows", "wide"};  // by sac_path
+  const char* path = paths[e.path];
+  std::string j = "{\"path\": \"" + std::string(path) + "\", " + kv("workspace_bytes", e.buf.workspace_bytes) + ", " +
+                  kv("lds_bytes", e.lds_bytes) + ", " + kv("upd_lds", e.upd_lds) + ", " + kv("upd_lds_b", e.launch[L_B].lds) +
+                  ", " + kv("upd_threads_b", e.launch[L_B].threads) + ", " + kv("nB", e.nB) + ", " + kv("nD", e.nD) + ", " +
+                  kv("nrt", e.h.nrt) + ", " + kv("xs", e.h.xs) + ", " + kv("role_xcd", e.h.role_xcd) + ", " +
+                  kv("stage", e.h.stage) + ", " + kv("upd_slots", e.h.upd_slots) + ", \"launch\": {";
+  const char* names[4] = {"A", "B", "C", "D"};
+  bool first = true;
+  for (int k = L_A; k <= L_D; ++k) {
+    if (wide && (k == L_A || k == L_C)) continue;  // the stage list below
+    const PhaseLaunch& d = e.launch[k];
+    j += std::string(first ? "" : ", ") + "\"" + names[k] + "\": {" + kv("grid", d.grid) + ", " +
+         kv("threads", d.threads) + ", " + kv("lds", d.lds) + "}";
+    first = false;
+  }
+  if (wide) {
+    j += ", \"stages\": [";
+    for (size_t i = 0; i < e.wst.size(); ++i) {
+      const sac_engine::WStage& st = e.wst[i];
+      j += std::string(i ? ", {" : "{") + kv("kind", st.kind) + ", " + kv("j0", st.j0) + ", " + kv("j1", st.j1) + ", " +
+           kv("grid", st.grid) + ", " + kv("phase", st.phase) + ", " + kv("last", st.last) + ", " + kv("lds", st.lds) + "}";
+    }
+    j += "]";
+  }
+  EngineDev hd;
+  memcpy(&hd, &e.h, sizeof(hd));
+  j += "}, \"hash\": {\"engine_dev\": " + fnv(&hd, sizeof(hd)) +
+       ", \"tiles_b\": " + fnv(e.hostB.data(), e.hostB.size() * sizeof(TileDesc)) +
+       ", \"tiles_d\": " + fnv(e.hostD.data(), e.hostD.size() * sizeof(TileDesc)) +
+       ", \"wide_dev\": " + fnv(&e.wdh, wide ? sizeof(WideDev) : 0) +
+       ", \"wjobs\": " + fnv(e.hostW.data(), wide ? e.hostW.size() * sizeof(WJob) : 0) + "}}";
+  if (j.size() + 1 > cap) return fail(SAC_E_INVALID, "plan dump needs " + std::to_string(j.size() + 1) + " bytes");
+  memcpy(out, j.c_str(), j.size() + 1);
+  return SAC_OK;
+}
 
-int sac_engine_uses_split(const sac_engine* e) { return e && e->h.split ? 1 : 0; }
+// the hidden-split kernels are role kernels too
+int sac_engine_uses_roles(const sac_engine* e) { return e && (e->path == PATH_ROLES || e->path == PATH_SPLIT); }
 
-int sac_engine_uses_pairs(const sac_engine* e) { return e && e->h.pairs ? 1 : 0; }
+int sac_engine_uses_split(const sac_engine* e) { return e && e->path == PATH_SPLIT; }
 
-int sac_engine_uses_wide(const sac_engine* e) { return e && e->wide ? (int)e->wst.size() : 0; }
+int sac_engine_uses_pairs(const sac_engine* e) { return e && e->path == PATH_PAIRS; }
+
+int sac_engine_uses_wide(const sac_engine* e) { return e && e->path == PATH_WIDE ? (int)e->wst.size() : 0; }
 
 int sac_engine_phase_launches(const sac_engine* e, int32_t* out) {
   if (!e || !out) return fail(SAC_E_INVALID, "null argument");
   for (int k = 0; k < 4; ++k) out[k] = 1;
-  if (e->wide) {
+  if (e->path == PATH_WIDE) {
     for (int k = 0; k < 4; ++k) out[k] = 0;
     for (const sac_engine::WStage& st : e->wst)
       if (st.kind != 0 && st.phase >= 0 && st.phase < 4) ++out[st.phase];
@@ -2051,16 +1266,13 @@ int sac_engine_phase_launches(const sac_engine* e, int32_t* out) {
 
 int sac_engine_debug_launch(sac_engine* e, const sac_replay* rb, int32_t kind, void* stream) {
   if (!e || !rb || kind < L_A || kind > L_D) return fail(SAC_E_INVALID, "bad debug_launch arguments");
-  if (e->wide) {  // every launch of that phase
+  if (e->path == PATH_WIDE) {  // every launch of that phase
     for (const sac_engine::WStage& st : e->wst)
       if (st.phase == kind) launch_wide(e, st, rb, nullptr, nullptr, (hipStream_t)stream);
     HIPCHK(hipGetLastError());
     return SAC_OK;
   }
-  if (e->cfg.precision == SAC_PREC_BF16)
-    launch_kind<bf16>(e, kind, rb, nullptr, nullptr, (hipStream_t)stream);
-  else
-    launch_kind<float>(e, kind, rb, nullptr, nullptr, (hipStream_t)stream);
+  BY_PRECISION(e, launch_kind, e, kind, rb, nullptr, nullptr, (hipStream_t)stream);
   HIPCHK(hipGetLastError());
   return SAC_OK;
 }
@@ -2100,7 +1312,7 @@ int sac_engine_time_phases(sac_engine* e, const sac_replay* rb, int32_t n_steps,
     ++cnt[kinds[i]];
   }
   // per phase and step (the stage path has several launches per phase)
-  auto avg = [&](int k) { return cnt[k] ? (float)(sum[k] / (e->wide ? n_steps : cnt[k])) : 0.f; };
+  auto avg = [&](int k) { return cnt[k] ? (float)(sum[k] / (e->path == PATH_WIDE ? n_steps : cnt[k])) : 0.f; };
   for (int p = 0; p < 4; ++p) ms_host[p] = avg(p);
   // the same event pattern around empty launches: the per-launch gap
   {
