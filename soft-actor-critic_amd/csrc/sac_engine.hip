@@ -90,12 +90,7 @@ __global__ void replay_push_kernel(sac_replay rb, const float* __restrict__ rows
 // multiple of 4 floats), each lane taking its source row's slot from the
 // owner lane by a shuffle.  Loads are issued in batches of GATHER_GB before
 // their stores (memory-level parallelism: a batch's rows are independent).
-#ifndef GATHER_NT
-#define GATHER_NT 1  // nontemporal output stores: 2.41 -> 3.01 TB/s at B = 1,048,576 (records)
-#endif
-#ifndef GATHER_GB
 #define GATHER_GB 8
-#endif
 template <typename V>
 __device__ __forceinline__ void gather_field(const float* __restrict__ src, int W, int64_t stride,
                                              float* __restrict__ dst, int nrow, int64_t slot, int lane) {
@@ -195,11 +190,8 @@ __global__ void __launch_bounds__(256) replay_gather_records_kernel(
       if (row < nrow && piece < live) {
         const int b = b0 + row;
         if (dst) {
-#if GATHER_NT
+          // nontemporal output stores: 2.41 -> 3.01 TB/s at B = 1,048,576 (records)
           __builtin_nontemporal_store(v[u], (f32x4*)(dst + (size_t)b * dw + col));
-#else
-          *(f32x4*)(dst + (size_t)b * dw + col) = v[u];
-#endif
         } else if (f == 2 * O + A) {
           r[b] = v[u][0];
           d[b] = v[u][1];
@@ -1066,16 +1058,13 @@ int sac_replay_push(const sac_replay* rb, const float* rows, int64_t n, int64_t 
 
 // rows per wave of the records gather: 16 (4x the waves in flight of 64 rows per wave:
 // 65,536 rows 1.51 -> 2.42 TB/s, 1,048,576 rows 3.00 -> 3.17 TB/s)
-static int gather_rpw(int batch) {
-  (void)batch;
-  return 16;
-}
+static constexpr int GATHER_RPW = 16;
 
 int sac_replay_gather(const sac_replay* rb, const int32_t* logical_idx, int32_t batch, float* s, float* a, float* r,
                       float* s2, float* d, void* stream) {
   if (!rb || !logical_idx || batch < 1 || !s || !a || !r || !s2 || !d) return fail(SAC_E_INVALID, "bad gather arguments");
   const int blocks = (batch + 255) / 256;  // one wave per 64 rows
-  const int rpw = gather_rpw(batch);
+  const int rpw = GATHER_RPW;
   if (standard_records(rb))
     replay_gather_records_kernel<false><<<(batch + 4 * rpw - 1) / (4 * rpw), 256, 0, (hipStream_t)stream>>>(
         *rb, logical_idx, batch, FeistelKeys{}, nullptr, s, a, r, s2, d, rpw);
@@ -1090,7 +1079,7 @@ int sac_replay_sample_gather(const sac_replay* rb, int32_t batch, uint64_t seed,
                              float* s, float* a, float* r, float* s2, float* d, void* stream) {
   if (!rb || batch < 1 || !s || !a || !r || !s2 || !d) return fail(SAC_E_INVALID, "bad sample_gather arguments");
   const int blocks = (batch + 255) / 256;
-  const int rpw = gather_rpw(batch);
+  const int rpw = GATHER_RPW;
   if (standard_records(rb))
     replay_gather_records_kernel<true><<<(batch + 4 * rpw - 1) / (4 * rpw), 256, 0, (hipStream_t)stream>>>(
         *rb, nullptr, batch, feistel_keys(seed, step), idx_out, s, a, r, s2, d, rpw);

@@ -203,9 +203,7 @@ __device__ __forceinline__ void rollout_step_body(const EngineDev* __restrict__ 
     Xb[r * ld + k] = (k < O && r < nvalid) ? obs[(size_t)(r0 + r) * O + k] : 0.f;
   }
   __syncthreads();
-  Pf<T> pf;
-  pf.tag = nullptr;
-  mlp_forward<T, R>(pi, Xb, Yb, ld, outP, outB, ldo, E.o_P1, E.ldp1, lds, false, false, 0, 0, 0, pf, gw_none());
+  mlp_forward<T, R>(pi, Xb, Yb, ld, outP, outB, ldo, E.o_P1, E.ldp1, lds, false, false, 0, 0, 0);
   // every read of ev.obs above is behind mlp_forward's barriers: row owners may now overwrite their rows
   if (tid < nvalid) {
     const int i = r0 + tid;

@@ -127,7 +127,7 @@ __device__ __forceinline__ void unit_seed(const AS_C NetDev& q, const lf* outP, 
 template <typename T>
 __device__ __forceinline__ void pair_critic_forward(const AS_C EngineDev& E, const AS_C NetDev& q, lf* lds, lf* Xb,
                                                     lf* Yb, lf* outP, lf* outB, bool storeXT, bool store_x0, int r0,
-                                                    int nvalid, Pf<T>& pf) {
+                                                    int nvalid) {
   const int ld = E.ld, ldo = E.ldo, Bp = E.Bp;
   lf* X = Xb;
   lf* Y = Yb;
@@ -135,10 +135,9 @@ __device__ __forceinline__ void pair_critic_forward(const AS_C EngineDev& E, con
     const AS_C LayerDev& Ly = q.l[l];
     if (storeXT && (l > 0 || store_x0)) store_T<T, SAC_PR>(X, ld, Ly.Kp, Ly.K, Ly.XT, Bp, r0, nvalid, nullptr);
     if (l == q.L - 1)
-      layer_fwd<T, SAC_PR>(X, ld, Ly, q.P + Ly.b_off, q.out_act, outP, ldo, outB, ldo, nullptr, 0, pf, gw_bwd(Ly));
+      layer_fwd<T, SAC_PR>(X, ld, Ly, q.P + Ly.b_off, q.out_act, outP, ldo, outB, ldo, nullptr, 0);
     else
-      layer_fwd<T, SAC_PR>(X, ld, Ly, q.P + Ly.b_off, q.hid_act, lds + E.o_P1[l], E.ldp1[l], Y, ld, nullptr, 0, pf,
-                           gw_fwd(q.l[l + 1]));
+      layer_fwd<T, SAC_PR>(X, ld, Ly, q.P + Ly.b_off, q.hid_act, lds + E.o_P1[l], E.ldp1[l], Y, ld, nullptr, 0);
     __syncthreads();
     lf* t = X;
     X = Y;
@@ -186,8 +185,6 @@ __global__ void __launch_bounds__(SAC_THREADS) sac_target_critic_pairs(const Eng
   AS_L int64_t* slotB = (AS_L int64_t*)(lds + E.o_slot);
   AS_G float* stats = GP(float, E.stats);
   const AS_C NetDev& pi = E.net[NET_PI];
-  Pf<T> pf;
-  pf_issue<T>(pf, critics ? gw_fwd(E.net[NET_Q1].l[0]) : gw_fwd(pi.l[0]));
 
   const uint64_t step = *GPC(uint64_t, E.rng_step);
   const int par = (int)(step & 1);
@@ -239,7 +236,7 @@ __global__ void __launch_bounds__(SAC_THREADS) sac_target_critic_pairs(const Eng
         Xb[r * ld + k] = k < O ? sB[r * O + k] : (k < O + A ? aB[r * A + (k - O)] : 0.f);
       }
       __syncthreads();
-      pair_critic_forward<T>(E, q, lds, Xb, Yb, outP, outB, true, qi == 0, r0, nvalid, pf);
+      pair_critic_forward<T>(E, q, lds, Xb, Yb, outP, outB, true, qi == 0, r0, nvalid);
       // q to the target group (it computes y, the seeds and the loss partials)
       if (tid < PR && 2 * pt + (tid >> 4) < E.nrt)
         gran_put(gran_at(E, G_Q1T + qi, 2 * pt + (tid >> 4)) + (tid & 15), outB[tid * ldo], ep);
@@ -248,8 +245,7 @@ __global__ void __launch_bounds__(SAC_THREADS) sac_target_critic_pairs(const Eng
       __syncthreads();
       // every layer's unit-seed dY^T, stored as it is made: phase B scales batch
       // column b by the seed (TileDesc::seed = E.seedq)
-      mlp_backward<T, PR>(q, gqB, ldo, Xb, Yb, ld, E.o_P1, E.ldp1, lds, true, Bp, r0, nvalid, pf,
-                          qi ? gw_none() : gw_fwd(E.net[NET_Q2].l[0]));
+      mlp_backward<T, PR>(q, gqB, ldo, Xb, Yb, ld, E.o_P1, E.ldp1, lds, true, Bp, r0, nvalid);
       STAMP(11 + 2 * qi);
     }
     END_STAMP(60);
@@ -278,9 +274,8 @@ __global__ void __launch_bounds__(SAC_THREADS) sac_target_critic_pairs(const Eng
       // below from the activations), every other layer's pre-activations
       const bool bits = !out && pi.hid_act == ACT_RELU;
       float* stash = actor && !bits ? Ly.pstash + (size_t)r0 * Ly.Np : nullptr;
-      const GemmW nx = out ? gw_fwd(E.net[NET_Q1T].l[0]) : gw_fwd(pi.l[l + 1]);
       layer_fwd<T, PR>(X, ld, Ly, pi.P + Ly.b_off, out ? pi.out_act : pi.hid_act, out ? outP : nullptr,
-                       out ? ldo : ld, out ? outB : Y, out ? ldo : ld, stash, 0, pf, nx);
+                       out ? ldo : ld, out ? outB : Y, out ? ldo : ld, stash, 0);
       __syncthreads();
       if (actor && bits) {  // relu(p) > 0 <=> p > 0: one 32-unit word per (row, word) lane
         const int nw = Ly.Np >> 5;
@@ -358,8 +353,7 @@ __global__ void __launch_bounds__(SAC_THREADS) sac_target_critic_pairs(const Eng
       Xb[r * ld + k] = k < O ? s2B[r * O + k] : (k < O + A ? a2B[r * A + (k - O)] : 0.f);
     }
     __syncthreads();
-    mlp_forward<T, PR>(q, Xb, Yb, ld, outP, outB, ldo, E.o_P1, E.ldp1, lds, false, false, Bp, r0, nvalid, pf,
-                       t ? gw_fwd(pi.l[0]) : gw_fwd(E.net[NET_Q2T].l[0]));
+    mlp_forward<T, PR>(q, Xb, Yb, ld, outP, outB, ldo, E.o_P1, E.ldp1, lds, false, false, Bp, r0, nvalid);
     if (tid < PR) qtB[t * PR + tid] = outB[tid * ldo];
     __syncthreads();
     STAMP(7 + t);
@@ -433,8 +427,6 @@ __device__ __forceinline__ void actor_pairs_body(const AS_C EngineDev& E, int bi
   const float alpha32 = (float)*GPC(double, E.alpha_state + 1);
   const int qi = critic2 ? 1 : 0;
   const AS_C NetDev& q = E.net[NET_Q1 + qi];
-  Pf<T> pf;
-  pf_issue<T>(pf, gw_fwd(q.l[0]));
   for (int i = tid; i < PR * O; i += SAC_THREADS) sB[i] = r0 * O + i < E.Br * O ? GPC(float, E.s_st)[(size_t)r0 * O + i] : 0.f;
   for (int i = tid; i < PR * A; i += SAC_THREADS) aB[i] = r0 * A + i < E.Br * A ? GPC(float, E.a_st)[(size_t)r0 * A + i] : 0.f;
   if (!critic2) {
@@ -452,16 +444,15 @@ __device__ __forceinline__ void actor_pairs_body(const AS_C EngineDev& E, int bi
       Xb[r * ld + k] = k < O ? sB[r * O + k] : (k < O + A ? aB[r * A + (k - O)] : 0.f);
     }
     __syncthreads();
-    pair_critic_forward<T>(E, q, lds, Xb, Yb, outP, outB, false, false, r0, nvalid, pf);
+    pair_critic_forward<T>(E, q, lds, Xb, Yb, outP, outB, false, false, r0, nvalid);
     if (!critic2 && tid < PR) qtB[tid] = outB[tid * ldo];
     STAMP(36 + qi);
     unit_seed(q, outP, ldo, goutB, nvalid);
     __syncthreads();
     // d a~ through the critic: dX of layer 0, action columns (unit seed)
-    lf* G0 = mlp_backward<T, PR>(q, goutB, ldo, Xb, Yb, ld, E.o_P1, E.ldp1, lds, false, Bp, r0, nvalid, pf,
-                                 gw_bwd(q.l[0]));
+    lf* G0 = mlp_backward<T, PR>(q, goutB, ldo, Xb, Yb, ld, E.o_P1, E.ldp1, lds, false, Bp, r0, nvalid);
     lf* Gx = (G0 == Xb) ? Yb : Xb;
-    layer_bwd<T, PR>(G0, ld, q.l[0], nullptr, 0, -1, Gx, ld, pf, critic2 ? gw_none() : gw_bwd(pi.l[pi.L - 1]));
+    layer_bwd<T, PR>(G0, ld, q.l[0], nullptr, 0, -1, Gx, ld);
     __syncthreads();
     if (critic2) {  // (dQ2/da~, q2) to the actor group
       for (int i = tid; i < PR * A; i += SAC_THREADS) {
@@ -568,7 +559,7 @@ __device__ __forceinline__ void actor_pairs_body(const AS_C EngineDev& E, int bi
   }
   __syncthreads();
   // ---- pi backward (agent.py:255-257): every layer's dY^T for phase D
-  mlp_backward<T, PR>(pi, goutB, ldo, Xb, Yb, ld, E.o_P1, E.ldp1, lds, true, Bp, r0, nvalid, pf, gw_none());
+  mlp_backward<T, PR>(pi, goutB, ldo, Xb, Yb, ld, E.o_P1, E.ldp1, lds, true, Bp, r0, nvalid);
   STAMP(35);
 }
 

@@ -248,31 +248,31 @@ __device__ __forceinline__ void prefetch_engine(const void* p) {
   const uint64_t base = (uint64_t)(uintptr_t)p;  // kernel-argument pointer: already uniform (SGPRs)
   asm volatile("s_load_dword s95, %0, 0\n\t" "s_load_dword s95, %0, 64\n\t" "s_load_dword s95, %0, 128\n\t" "s_load_dword s95, %0, 192\n\t" "s_load_dword s95, %0, 256\n\t" "s_load_dword s95, %0, 320\n\t" "s_load_dword s95, %0, 384\n\t" "s_load_dword s95, %0, 448\n\t" "s_load_dword s95, %0, 512\n\t" "s_load_dword s95, %0, 576\n\t" "s_load_dword s95, %0, 640\n\t" "s_load_dword s95, %0, 704\n\t" "s_load_dword s95, %0, 768\n\t" "s_load_dword s95, %0, 832\n\t" "s_load_dword s95, %0, 896\n\t" "s_load_dword s95, %0, 960\n\t" "s_load_dword s95, %0, 1024\n\t" "s_load_dword s95, %0, 1088\n\t" "s_load_dword s95, %0, 1152\n\t" "s_load_dword s95, %0, 1216\n\t" "s_load_dword s95, %0, 1280\n\t" "s_load_dword s95, %0, 1344\n\t" "s_load_dword s95, %0, 1408\n\t" "s_load_dword s95, %0, 1472\n\t" "s_load_dword s95, %0, 1536\n\t" "s_load_dword s95, %0, 1600\n\t" "s_load_dword s95, %0, 1664\n\t" "s_load_dword s95, %0, 1728\n\t" "s_load_dword s95, %0, 1792\n\t" "s_load_dword s95, %0, 1856\n\t" "s_load_dword s95, %0, 1920\n\t" "s_load_dword s95, %0, 1984\n\t" "s_load_dword s95, %0, 2048\n\t" "s_load_dword s95, %0, 2112\n\t" "s_load_dword s95, %0, 2176\n\t" "s_load_dword s95, %0, 2240\n\t" "s_load_dword s95, %0, 2304\n\t" "s_load_dword s95, %0, 2368\n\t" "s_load_dword s95, %0, 2432\n\t" "s_load_dword s95, %0, 2496\n\t" "s_load_dword s95, %0, 2560\n\t" "s_load_dword s95, %0, 2624\n\t" "s_load_dword s95, %0, 2688\n\t" "s_load_dword s95, %0, 2752\n\t" "s_load_dword s95, %0, 2816\n\t" "s_load_dword s95, %0, 2880\n\t" "s_load_dword s95, %0, 2944\n\t" "s_load_dword s95, %0, 3008\n\t" "s_load_dword s95, %0, 3072\n\t" "s_load_dword s95, %0, 3136\n\t" "s_load_dword s95, %0, 3200\n\t" "s_load_dword s95, %0, 3264\n\t" "s_load_dword s95, %0, 3328\n\t" "s_load_dword s95, %0, 3392\n\t" "s_load_dword s95, %0, 3456\n\t" "s_load_dword s95, %0, 3520\n\t" "s_load_dword s95, %0, 3584\n\t" "s_load_dword s95, %0, 3648\n\t" "s_load_dword s95, %0, 3712\n\t" "s_load_dword s95, %0, 3776\n\t" "s_load_dword s95, %0, 3840\n\t" "s_load_dword s95, %0, 3904\n\t" "s_load_dword s95, %0, 3968\n\t" "s_load_dword s95, %0, 4032\n\t" "s_waitcnt lgkmcnt(0)" :: "s"(base) : "s95", "memory");
 }
-#ifdef SAC_NO_PREFETCH
-#define PREFETCH_ARG(ptr) ((void)0)
-#else
 #define PREFETCH_ARG(ptr) prefetch_engine(ptr)
-#endif
 
 // ============================================================================ MFMA layer steps
 // A GEMM step streams a fragment-packed B matrix (weights W for a forward step,
 // W^T for a dX step) against activations held in LDS.  Each wave owns output
-// tile pairs (nt, nt + SAC_NW).  The weight stream is software-pipelined across
-// steps: every wave keeps the first 8-chunk batch of its first tile pair of the
-// NEXT step in registers (Pf), issued right after the current step's first MFMAs,
-// so the load latency overlaps the epilogue, the barrier and whatever non-GEMM
-// work sits between the two steps.
+// tile pairs (nt, nt + SAC_NW).  A wave's B fragments are either streamed by
+// the step itself, in batches of 8 chunks whose loads are all issued before the
+// batch's first MFMA, or, for the first chunks of its first tile pair, held in
+// registers from before a wait by the caller (Held, below).
+// A cross-step register prefetch (the first chunks of the NEXT step's first tile
+// pair and its bias kept in flight over the epilogue and the barrier) was
+// measured and removed: on C2 1 chunk (8 VGPRs) gave 17.3K steps/s vs 17.8K
+// without, 8 chunks spilled at 8 waves; re-measured on the pair kernels it
+// spilled at their 252 VGPRs, C3 bf16 9.6K -> 8.5K (1 chunk) / 6.7K (4 chunks)
+// (profiles/r06_ab_cross_layer_prefetch.txt).
 struct GemmW {
   const void* p;      // packed B matrix (first element of the step's first tile and chunk)
   int cols;           // reduction length of the step (multiple of SAC_PAD)
   int NT;             // 16-row tiles of the packed matrix = output tiles of the step
-  const float* bias;  // forward steps: bias [N], prefetched with the weights
+  const float* bias;  // forward steps: bias [N] (held_issue holds the first pair's with the fragments)
   int N;
   int tcols;          // column count of the whole packed matrix: a 16-row tile is 16 * tcols elements
 };
 __device__ __forceinline__ GemmW gw_fwd(const AS_C LayerDev& L) { return GemmW{L.Wc, L.Kp, L.Np >> 4, L.bias, L.N, L.Kp}; }
 __device__ __forceinline__ GemmW gw_bwd(const AS_C LayerDev& L) { return GemmW{L.WTc, L.Np, L.Kp >> 4, nullptr, 0, L.Np}; }
-__device__ __forceinline__ GemmW gw_none() { return GemmW{nullptr, 0, 0, nullptr, 0, 0}; }
 // Sub-matrix view of a packed [rows][cols_full] operand: rows [row0, row0 + nrows)
 // (multiples of 16) and reduction columns [col0, col0 + ncols) (multiples of the
 // MFMA K chunk).  Tile t starts at t * 16 * cols_full elements and chunk ch of a
@@ -282,48 +282,6 @@ template <typename T>
 __device__ __forceinline__ GemmW gw_sub(const void* p, int cols_full, int row0, int nrows, int col0, int ncols,
                                         const float* bias, int N) {
   return GemmW{(const T*)p + (size_t)row0 * cols_full + (size_t)col0 * 16, ncols, nrows >> 4, bias, N, cols_full};
-}
-
-#ifndef SAC_PF
-// Cross-step register prefetch of the weight stream: chunks per tile of the
-// NEXT GEMM step each wave keeps in flight, plus its first bias values (see
-// gemm_step).  Measured on C2: 1 chunk (8 VGPRs) 17.3K steps/s vs 17.8K without;
-// 8 chunks spill at 8 waves.  Off by default.
-#define SAC_PF 0
-#endif
-template <typename T>
-struct Pf {
-#if SAC_PF
-  typename MM<T>::Frag f0[SAC_PF], f1[SAC_PF];
-  float b0, b1;  // bias of the lane's column in the first tile pair (forward steps)
-#endif
-  const void* tag;  // which B matrix the registers hold (wave-uniform)
-};
-
-// Issue batch 0 (chunks 0..7, clamped) of this wave's first tile pair of step w.
-template <typename T>
-__device__ __forceinline__ void pf_issue(Pf<T>& pf, const GemmW& w) {
-  pf.tag = w.p;
-#if SAC_PF
-  constexpr int KC = MM<T>::KC, FS = 64 * MM<T>::KL;
-  const int lane = threadIdx.x & 63, wave = wave_id();
-  if (!w.p || wave >= w.NT) return;
-  const int last = w.cols / KC - 1;
-  const int nt1 = wave + SAC_NW < w.NT ? wave + SAC_NW : wave;
-  const AS_G T* b0 = GPC(T, w.p) + packed_lane<T>(wave, w.tcols, lane);
-  const AS_G T* b1 = GPC(T, w.p) + packed_lane<T>(nt1, w.tcols, lane);
-  if (w.bias) {  // same columns as layer_fwd's first pair: n0 = 16 wave + c, n1 = n0 + 16 SAC_NW
-    const int n0 = wave * 16 + (lane & 15), n1 = n0 + 16 * SAC_NW;
-    pf.b0 = GPC(float, w.bias)[n0 < w.N ? n0 : w.N - 1];
-    pf.b1 = GPC(float, w.bias)[n1 < w.N ? n1 : w.N - 1];
-  }
-#pragma unroll
-  for (int u = 0; u < SAC_PF; ++u) {
-    const int cu = u < last ? u : last;
-    pf.f0[u] = MM<T>::ld(b0 + cu * FS);
-    pf.f1[u] = MM<T>::ld(b1 + cu * FS);
-  }
-#endif
 }
 
 // Held weights: a role that waits on a hand-off (or on its sample) loads the
@@ -500,18 +458,17 @@ __device__ __forceinline__ void gemm_pair_fixed(const lf* __restrict__ arow, int
 
 // One GEMM step over ROWS rows: out tile (r, col) for every col < 16*w.NT,
 // acc = sum_k A[r][k] B[col][k]; epi(h, col, acc[RT]) consumes each tile pair.
-// Batch 0 of the first pair comes from pf; the next step's batch 0 is issued
-// into pf right after those MFMAs.
+// The first HC chunks of the wave's first pair come from held when it holds
+// this step's B matrix; everything else is streamed.
 template <typename T, int ROWS, int HC, typename Epi>
-__device__ __forceinline__ void gemm_step(const lf* __restrict__ A, int lda, const GemmW& w, Pf<T>& pf,
-                                          const GemmW& next, Epi epi, const Held<T, HC ? HC : 1>* held) {
+__device__ __forceinline__ void gemm_step(const lf* __restrict__ A, int lda, const GemmW& w, Epi epi,
+                                          const Held<T, HC ? HC : 1>* held) {
   constexpr int RT = ROWS / 16;
   constexpr int KC = MM<T>::KC, KL = MM<T>::KL;
   const int lane = threadIdx.x & 63, wave = wave_id();
   const int c = lane & 15, g = lane >> 4;
   const int NT = w.NT, nch = w.cols / KC;
   const lf* arow = A + c * lda + g * KL;
-#if !SAC_PF
   if (w.NT == 2 * SAC_NW) {  // one pair per wave (uniform branches)
     if (nch == 8) {
       gemm_pair_fixed<T, RT, 8, false, HC>(arow, lda, w, lane, wave, c, epi, held);
@@ -522,8 +479,6 @@ __device__ __forceinline__ void gemm_step(const lf* __restrict__ A, int lda, con
       return;
     }
   }
-#endif
-  if (pf.tag != w.p) pf_issue<T>(pf, w);  // chain broken by the caller: reload (uniform)
   // weight stream: plain buffer loads through a uniform descriptor (coh_frag<T, false>)
   const __amdgpu_buffer_rsrc_t rs = coh_rsrc(w.p, 0xFFFFFFF0u);
   auto pair = [&](int nt0, bool first) __attribute__((always_inline)) {
@@ -534,28 +489,6 @@ __device__ __forceinline__ void gemm_step(const lf* __restrict__ A, int lda, con
     f32x4 acc0[RT], acc1[RT];
 #pragma unroll
     for (int rt = 0; rt < RT; ++rt) acc0[rt] = acc1[rt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#if SAC_PF
-    int ch0 = 0;
-    if (first) {
-      ch0 = nch < SAC_PF ? nch : SAC_PF;
-#pragma unroll
-      for (int u = 0; u < SAC_PF; ++u) {
-        if (u < ch0)
-#pragma unroll
-          for (int rt = 0; rt < RT; ++rt) {
-            const typename MM<T>::Frag a = MM<T>::from_lds(arow + rt * 16 * lda + u * KC);
-            MM<T>::mma(acc0[rt], a, pf.f0[u]);
-            if (has1) MM<T>::mma(acc1[rt], a, pf.f1[u]);
-          }
-        // bound how many A fragments the scheduler hoists (register pressure)
-        if (u & 1) __builtin_amdgcn_sched_barrier(0);
-      }
-      __builtin_amdgcn_sched_barrier(0);  // old fragments consumed before the registers are reloaded
-      pf_issue<T>(pf, next);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    mma_pair_from<T, RT, 8>(arow, lda, rs, o0, o1, has1, ch0, nch, acc0, acc1);
-#else
     if (HC > 0 && first && held && held->tag == w.p) {  // resident fragments (uniform branch)
       const int hn = nch < HC ? nch : HC;
       if (hn == HC) {
@@ -576,17 +509,12 @@ __device__ __forceinline__ void gemm_step(const lf* __restrict__ A, int lda, con
     } else {
       mma_pair_from<T, RT, 8>(arow, lda, rs, o0, o1, has1, 0, nch, acc0, acc1);
     }
-#endif
     epi(0, nt0 * 16 + c, acc0, first);
     if (has1) epi(1, nt1 * 16 + c, acc1, first);
   };
   // one instance of the pair code (runtime `first`) keeps the kernel's code small
   bool first = true;
-  for (int nt0 = wave;; nt0 += 2 * SAC_NW) {
-    if (nt0 >= NT) {
-      if (first) pf_issue<T>(pf, next);
-      break;
-    }
+  for (int nt0 = wave; nt0 < NT; nt0 += 2 * SAC_NW) {
     pair(nt0, first);
     first = false;
   }
@@ -628,27 +556,21 @@ __device__ __forceinline__ void act_pass_bwd(lf* G, int ldg, const lf* P, int ld
 // P (optional) keeps the pre-activation; Pg (optional) stashes rows >= pg_row0.
 template <typename T, int ROWS, int HC = 0>
 __device__ __forceinline__ void layer_fwd(const lf* X, int ldx, const AS_C LayerDev& L, const float* bias_, int act, lf* P,
-                                          int ldp, lf* Y, int ldy, float* Pg_, int pg_row0, Pf<T>& pf,
-                                          const GemmW& next, const Held<T, HC ? HC : 1>* held = nullptr) {
+                                          int ldp, lf* Y, int ldy, float* Pg_, int pg_row0,
+                                          const Held<T, HC ? HC : 1>* held = nullptr) {
   const AS_G float* bias = GPC(float, bias_);
   AS_G float* Pg = GP(float, Pg_);
   const int lane = threadIdx.x & 63, wave = wave_id();
   const int g = lane >> 4;
   const int N = L.N, Np = L.Np;
-  // The first pair's bias is loaded before the step: a load issued after the
-  // next step's prefetch would wait for all of it (vmcnt retires in order).
+  // The first pair's bias is loaded before the step, ahead of its weight stream.
   const int n0 = wave * 16 + (lane & 15), n1 = n0 + 16 * SAC_NW;
   const GemmW w = gw_fwd(L);
-#if SAC_PF
-  if (pf.tag != w.p) pf_issue<T>(pf, w);  // bias arrives with the prefetched weights
-  const float bpre0 = pf.b0, bpre1 = pf.b1;
-#else
   const bool hb = HC > 0 && held && held->tag == w.p;  // bias held with the fragments
   const float bpre0 = hb ? held->b0 : ldf<false>((const float*)bias + (n0 < N ? n0 : N - 1));
   const float bpre1 = hb ? held->b1 : ldf<false>((const float*)bias + (n1 < N ? n1 : N - 1));
-#endif
   // first: the wave's first tile pair, whose columns are n0 / n1 (bias preloaded)
-  gemm_step<T, ROWS, HC>(X, ldx, w, pf, next, [&](int h, int n, const f32x4* acc, bool first) {
+  gemm_step<T, ROWS, HC>(X, ldx, w, [&](int h, int n, const f32x4* acc, bool first) {
     const bool nv = n < N;
     const float bn = first ? (h ? bpre1 : bpre0) : ldf<false>((const float*)bias + (nv ? n : N - 1));
 #pragma unroll
@@ -668,11 +590,10 @@ __device__ __forceinline__ void layer_fwd(const lf* X, int ldx, const AS_C Layer
 // dX: Gout[r][k] = act'(Pprev[r][k]) * sum_n G[r][n] W[n][k]   (act_prev < 0: no act')
 template <typename T, int ROWS, int HC = 0>
 __device__ __forceinline__ void layer_bwd(const lf* G, int ldg, const AS_C LayerDev& L, const lf* Pprev, int ldp,
-                                          int act_prev, lf* Gout, int ldo, Pf<T>& pf, const GemmW& next,
-                                          const Held<T, HC ? HC : 1>* held = nullptr) {
+                                          int act_prev, lf* Gout, int ldo, const Held<T, HC ? HC : 1>* held = nullptr) {
   const int g = (threadIdx.x & 63) >> 4;
   const int K = L.K;
-  gemm_step<T, ROWS, HC>(G, ldg, gw_bwd(L), pf, next, [&](int, int k, const f32x4* acc, bool) {
+  gemm_step<T, ROWS, HC>(G, ldg, gw_bwd(L), [&](int, int k, const f32x4* acc, bool) {
     const bool kv = k < K;
 #pragma unroll
     for (int rt = 0; rt < ROWS / 16; ++rt)
@@ -744,19 +665,18 @@ __device__ __forceinline__ void store_T(const lf* __restrict__ src, int lds_ld, 
 // Full MLP forward over ROWS rows: hidden layers ping-pong Xb/Yb (stride ld), the
 // output layer writes (Pout, Yout) with stride ldo.  keepP: per-layer
 // pre-activations into lds[o_P[l]] (stride ldp[l]).  storeXT: each layer's input
-// transposed into L.XT (ROWS must be SAC_ROWS).  after: the GEMM step that follows.
+// transposed into L.XT (ROWS must be SAC_ROWS).
 // HELD: layers 0 and 1 start on fragments held in h0 / h1 (see Held).
 template <typename T, int ROWS, bool HELD = false>
 __device__ __forceinline__ void mlp_forward(const AS_C NetDev& net, lf* Xb, lf* Yb, int ld, lf* Pout, lf* Yout, int ldo,
                                             const AS_C int* o_P, const AS_C int* ldp, lf* lds, bool keepP, bool storeXT, int Bp,
-                                            int col0, int nvalid, Pf<T>& pf, const GemmW& after,
-                                            const Held<T, 1>* h0 = nullptr, const Held<T, 8>* h1 = nullptr) {
+                                            int col0, int nvalid, const Held<T, 1>* h0 = nullptr,
+                                            const Held<T, 8>* h1 = nullptr) {
   lf* X = Xb;
   lf* Y = Yb;
   for (int l = 0; l < net.L; ++l) {
     const AS_C LayerDev& Ly = net.l[l];
     const bool out = l == net.L - 1;
-    const GemmW next = out ? after : gw_fwd(net.l[l + 1]);
     if (storeXT) {
       if constexpr (ROWS == SAC_ROWS) store_T<T, ROWS>(X, ld, Ly.Kp, Ly.K, Ly.XT, Bp, col0, nvalid, nullptr);
     }
@@ -766,11 +686,11 @@ __device__ __forceinline__ void mlp_forward(const AS_C NetDev& net, lf* Xb, lf* 
     lf* Yl = out ? Yout : Y;
     const int ldyl = out ? ldo : ld;
     if (HELD && l == 0)
-      layer_fwd<T, ROWS, 1>(X, ld, Ly, net.P + Ly.b_off, act, Pl, ldpl, Yl, ldyl, nullptr, 0, pf, next, h0);
+      layer_fwd<T, ROWS, 1>(X, ld, Ly, net.P + Ly.b_off, act, Pl, ldpl, Yl, ldyl, nullptr, 0, h0);
     else if (HELD && l == 1)
-      layer_fwd<T, ROWS, 8>(X, ld, Ly, net.P + Ly.b_off, act, Pl, ldpl, Yl, ldyl, nullptr, 0, pf, next, h1);
+      layer_fwd<T, ROWS, 8>(X, ld, Ly, net.P + Ly.b_off, act, Pl, ldpl, Yl, ldyl, nullptr, 0, h1);
     else
-      layer_fwd<T, ROWS>(X, ld, Ly, net.P + Ly.b_off, act, Pl, ldpl, Yl, ldyl, nullptr, 0, pf, next);
+      layer_fwd<T, ROWS>(X, ld, Ly, net.P + Ly.b_off, act, Pl, ldpl, Yl, ldyl, nullptr, 0);
     __syncthreads();
     lf* t = X;
     X = Y;
@@ -786,13 +706,13 @@ __device__ __forceinline__ void mlp_forward(const AS_C NetDev& net, lf* Xb, lf* 
 template <typename T, int ROWS, bool HELD = false>
 __device__ __forceinline__ lf* mlp_backward(const AS_C NetDev& net, const lf* Gout, int ldo, lf* Xb, lf* Yb, int ld,
                                             const AS_C int* o_P, const AS_C int* ldp, lf* lds, bool storeGT, int Bp, int col0,
-                                            int nvalid, Pf<T>& pf, const GemmW& after,
-                                            const Held<T, 1>* h0 = nullptr, const Held<T, 8>* h1 = nullptr) {
+                                            int nvalid, const Held<T, 1>* h0 = nullptr,
+                                            const Held<T, 8>* h1 = nullptr) {
   const int Lh = net.L - 1;
   const AS_C LayerDev& Lo = net.l[Lh];
   if (storeGT) store_T<T, ROWS>(Gout, ldo, Lo.Np, Lo.N, Lo.GT, Bp, col0, nvalid, Lo.dbp);
-  layer_bwd<T, ROWS, HELD ? 1 : 0>(Gout, ldo, Lo, lds + o_P[Lh - 1], ldp[Lh - 1], net.hid_act, Yb, ld, pf,
-                                        Lh - 1 >= 1 ? gw_bwd(net.l[Lh - 1]) : after, (const Held<T, 1>*)h0);
+  layer_bwd<T, ROWS, HELD ? 1 : 0>(Gout, ldo, Lo, lds + o_P[Lh - 1], ldp[Lh - 1], net.hid_act, Yb, ld,
+                                   (const Held<T, 1>*)h0);
   __syncthreads();
   lf* G = Yb;
   lf* Gn = Xb;
@@ -801,11 +721,9 @@ __device__ __forceinline__ lf* mlp_backward(const AS_C NetDev& net, const lf* Go
     if (storeGT) store_T<T, ROWS>(G, ld, Ly.Np, Ly.N, Ly.GT, Bp, col0, nvalid, Ly.dbp);
     if (l == 0) break;
     if (HELD && l == Lh - 1)
-      layer_bwd<T, ROWS, 8>(G, ld, Ly, lds + o_P[l - 1], ldp[l - 1], net.hid_act, Gn, ld, pf,
-                                 l - 1 >= 1 ? gw_bwd(net.l[l - 1]) : after, h1);
+      layer_bwd<T, ROWS, 8>(G, ld, Ly, lds + o_P[l - 1], ldp[l - 1], net.hid_act, Gn, ld, h1);
     else
-      layer_bwd<T, ROWS>(G, ld, Ly, lds + o_P[l - 1], ldp[l - 1], net.hid_act, Gn, ld, pf,
-                       l - 1 >= 1 ? gw_bwd(net.l[l - 1]) : after);
+      layer_bwd<T, ROWS>(G, ld, Ly, lds + o_P[l - 1], ldp[l - 1], net.hid_act, Gn, ld);
     __syncthreads();
     lf* t = G;
     G = Gn;
@@ -826,14 +744,14 @@ __device__ __forceinline__ float fmin_nan(float a, float b) { return (a != a) ? 
 // the E.o_P1 buffers (critic forward with keepP).
 template <typename T, int ROWS>
 __device__ __forceinline__ void critic_unit_backward(const AS_C EngineDev& E, const AS_C NetDev& net, const lf* Gout, int ldo,
-                                                     lf* lds, Pf<T>& pf) {
+                                                     lf* lds) {
   const int Lh = net.L - 1;
   layer_bwd<T, ROWS>(Gout, ldo, net.l[Lh], lds + E.o_P1[Lh - 1], E.ldp1[Lh - 1], net.hid_act, lds + E.o_P2[Lh - 1],
-                     E.ldp2[Lh - 1], pf, Lh - 1 >= 1 ? gw_bwd(net.l[Lh - 1]) : gw_none());
+                     E.ldp2[Lh - 1]);
   __syncthreads();
   for (int l = Lh - 1; l >= 1; --l) {
     layer_bwd<T, ROWS>(lds + E.o_P2[l], E.ldp2[l], net.l[l], lds + E.o_P1[l - 1], E.ldp1[l - 1], net.hid_act,
-                       lds + E.o_P2[l - 1], E.ldp2[l - 1], pf, l - 1 >= 1 ? gw_bwd(net.l[l - 1]) : gw_none());
+                       lds + E.o_P2[l - 1], E.ldp2[l - 1]);
     __syncthreads();
   }
 }
@@ -866,9 +784,7 @@ __device__ __forceinline__ float adam_elem(float& p, float& m, float& v, float g
 //      from LDS as whole 16-B fragment pieces (plain stores: the reader is the
 //      next launch).
 // 16 waves (measured on C2: 256-thread tiles took B 8.7 / D 7.8 us vs 6.4 / 5.9)
-#ifndef SAC_UPD_THREADS
 #define SAC_UPD_THREADS 1024
-#endif
 #define SAC_UPD_BCH (512 / (int)sizeof(T))  // batch columns staged per chunk (512 B per row)
 // dynamic LDS of an update tile: upd_slots x stage 64 x 528 B | 2 x [32][33] f32 | [32][17] f32 |
 // upd_slots x [256] f32 seeds (>= the alpha block's 5 x 1024 floats)
@@ -1469,12 +1385,10 @@ __device__ __forceinline__ float gran_get(const AS_C EngineDev& E, const AS_G ui
 // one lane: N granules polled together (every load of a poll in flight at once:
 // one round trip once the producers have stored, not N in sequence)
 // Pipelined hand-off polls (gran_getn): the s_sleep between a consumer's two
-// polls in flight; 0 = one poll per round trip.  Same-box A/Bs, C2 fp32: 8 ->
-// +0.6% steps/s over 0 (both interleaved reps), 20 -> -1%; then 4 -> +0.5%
-// over 8, 12 mixed (profiles/r02_ab_poll2.txt, r02_ab_poll_spacing.txt).
-#ifndef SAC_POLL2
-#define SAC_POLL2 4
-#endif
+// polls in flight.  Same-box A/Bs, C2 fp32: 8 -> +0.6% steps/s over one poll
+// per round trip (both interleaved reps), 20 -> -1%; then 4 -> +0.5% over 8,
+// 12 mixed (profiles/r02_ab_poll2.txt, r02_ab_poll_spacing.txt).
+#define SAC_POLL_SLEEP 4
 template <int N>
 __device__ __forceinline__ bool gran_ok(const uint64_t (&x)[N], uint32_t ep) {
   bool all = true;
@@ -1512,14 +1426,13 @@ __device__ __forceinline__ void gran_getn1(const AS_C EngineDev& E, const AS_G u
 template <int N>
 __device__ __forceinline__ void gran_getn(const AS_C EngineDev& E, const AS_G uint64_t* const (&g)[N], uint32_t ep,
                                           float (&out)[N]) {
-#if SAC_POLL2
   // Two polls in flight, half a round trip apart: a failed check re-issues its
   // poll at once while the other one is still on its way, so a granule that
   // lands is seen ~RTT/4 after (on average) instead of ~RTT/2.  The check of
   // one poll waits only for its own loads (the other's were issued later).
   uint64_t x[N], y[N];
   gran_issue<N>(g, x);
-  __builtin_amdgcn_s_sleep(SAC_POLL2);
+  __builtin_amdgcn_s_sleep(SAC_POLL_SLEEP);
   gran_issue<N>(g, y);
   for (int it = 0;; it += 2) {
     if (gran_ok<N>(x, ep)) {
@@ -1542,9 +1455,6 @@ __device__ __forceinline__ void gran_getn(const AS_C EngineDev& E, const AS_G ui
     }
     gran_issue<N>(g, y);
   }
-#else
-  gran_getn1<N>(E, g, ep, out);
-#endif
 }
 
 // ============================================================================ sample + gather
@@ -1689,9 +1599,6 @@ __device__ __forceinline__ void target_critic_body(const EngineDev* __restrict__
   lf* gqB = lds + E.o_gout;
   AS_L int64_t* slotB = (AS_L int64_t*)(lds + E.o_slot);
   const AS_C NetDev& pi = E.net[NET_PI];
-  Pf<T> pf;  // this role's first GEMM streams in under the sample / gather
-  pf_issue<T>(pf, !ROLES || do_pi ? gw_fwd(pi.l[0])
-                  : gw_fwd(E.net[role <= 2 ? NET_Q1T + role - 1 : NET_Q1 + role - 3].l[0]));
   // pi(s') (the critical path): layers 0 and 1 held under the sample / gather
   Held<T, 1> ph0;
   Held<T, 8> ph1;
@@ -1840,7 +1747,6 @@ __device__ __forceinline__ void target_critic_body(const EngineDev* __restrict__
       lf* Pl = out ? outP : nullptr;
       lf* Yl = out ? outB : Y;
       const int ldl = out ? ldo : ld;
-      const GemmW nx = out ? gw_fwd(E.net[NET_Q1T].l[0]) : gw_fwd(pi.l[l + 1]);
       // held fragments exist only under the role split (ROWS = R); the fused
       // [s'; s] pass (ROWS = 2R) streams every layer.  (With the held variants
       // instantiated here -- their tags null, the held branch never taken -- the
@@ -1850,13 +1756,13 @@ __device__ __forceinline__ void target_critic_body(const EngineDev* __restrict__
       // test_bf16_one_step_from_the_engine_state; profiles/r06_bf16_rows_fault.txt.)
       if constexpr (ROLES) {
         if (l == 0)
-          layer_fwd<T, ROWS, 1>(X, ld, Ly, pi.P + Ly.b_off, act_l, Pl, ldl, Yl, ldl, stash, a0, pf, nx, &ph0);
+          layer_fwd<T, ROWS, 1>(X, ld, Ly, pi.P + Ly.b_off, act_l, Pl, ldl, Yl, ldl, stash, a0, &ph0);
         else if (l == 1)
-          layer_fwd<T, ROWS, 8>(X, ld, Ly, pi.P + Ly.b_off, act_l, Pl, ldl, Yl, ldl, stash, a0, pf, nx, &ph1);
+          layer_fwd<T, ROWS, 8>(X, ld, Ly, pi.P + Ly.b_off, act_l, Pl, ldl, Yl, ldl, stash, a0, &ph1);
         else
-          layer_fwd<T, ROWS>(X, ld, Ly, pi.P + Ly.b_off, act_l, Pl, ldl, Yl, ldl, stash, a0, pf, nx);
+          layer_fwd<T, ROWS>(X, ld, Ly, pi.P + Ly.b_off, act_l, Pl, ldl, Yl, ldl, stash, a0);
       } else {
-        layer_fwd<T, ROWS>(X, ld, Ly, pi.P + Ly.b_off, act_l, Pl, ldl, Yl, ldl, stash, a0, pf, nx);
+        layer_fwd<T, ROWS>(X, ld, Ly, pi.P + Ly.b_off, act_l, Pl, ldl, Yl, ldl, stash, a0);
       }
       __syncthreads();
       STAMP(2 + l);
@@ -1947,7 +1853,7 @@ __device__ __forceinline__ void target_critic_body(const EngineDev* __restrict__
       }
       __syncthreads();
       mlp_forward<T, R, ROLES>(q, Xb, Yb, ld, outP, outB, ldo, E.o_P1, E.ldp1, lds, false, false, Bp, r0,
-                                      nvalid, pf, gw_fwd(E.net[t ? NET_Q1 : NET_Q2T].l[0]), &qh0, &qh1);
+                               nvalid, &qh0, &qh1);
       if (tid < R) {
         qtB[t * R + tid] = outB[tid * ldo];
         if (ROLES) gran_put(gran_at(E, t ? G_Q2T : G_Q1T, rbi) + tid, outB[tid * ldo], ep);
@@ -1986,10 +1892,9 @@ __device__ __forceinline__ void target_critic_body(const EngineDev* __restrict__
         const AS_C LayerDev& Ly = q.l[l];
         if (l > 0) store_T<T, R>(X, ld, Ly.Kp, Ly.K, Ly.XT, Bp, r0, nvalid, nullptr);
         if (l == q.L - 1)
-          layer_fwd<T, R>(X, ld, Ly, q.P + Ly.b_off, q.out_act, outP, ldo, outB, ldo, nullptr, 0, pf, gw_bwd(Ly));
+          layer_fwd<T, R>(X, ld, Ly, q.P + Ly.b_off, q.out_act, outP, ldo, outB, ldo, nullptr, 0);
         else
-          layer_fwd<T, R>(X, ld, Ly, q.P + Ly.b_off, q.hid_act, lds + E.o_P1[l], E.ldp1[l], Y, ld, nullptr, 0, pf,
-                          gw_fwd(q.l[l + 1]));
+          layer_fwd<T, R>(X, ld, Ly, q.P + Ly.b_off, q.hid_act, lds + E.o_P1[l], E.ldp1[l], Y, ld, nullptr, 0);
         __syncthreads();
         lf* t = X;
         X = Y;
@@ -2006,7 +1911,7 @@ __device__ __forceinline__ void target_critic_body(const EngineDev* __restrict__
         for (int n = 0; n < 32; ++n) gqB[tid * ldo + n] = n == 0 ? u : 0.f;
       }
       __syncthreads();
-      critic_unit_backward<T, R>(E, q, gqB, ldo, lds, pf);
+      critic_unit_backward<T, R>(E, q, gqB, ldo, lds);
       STAMP(16);
       // y needs both target critics and log pi' (granules: each lane polls its row's three)
       STAMP(14);
@@ -2111,9 +2016,6 @@ __device__ __forceinline__ void actor_body(const EngineDev* __restrict__ Ep, int
   lf* outP2 = lds + E.o_outp2;
   const AS_C NetDev& pi = E.net[NET_PI];
   const float alpha32 = (float)*GPC(double, E.alpha_state + 1);
-  Pf<T> pf;  // this role's first GEMM streams in under the loads / the wait
-  pf_issue<T>(pf, !ROLES ? gw_fwd(E.net[NET_Q1].l[0])
-                  : role == 0 ? gw_bwd(pi.l[pi.L - 1]) : gw_fwd(E.net[NET_Q1 + role - 1].l[0]));
 
   if (!ROLES || role >= 1) {
     for (int i = tid; i < R * O; i += SAC_THREADS) sB[i] = GPC(float, E.s_st)[(size_t)r0 * O + i];
@@ -2143,11 +2045,8 @@ __device__ __forceinline__ void actor_body(const EngineDev* __restrict__ Ep, int
         Xb[r * ld + k] = k < O ? sB[r * O + k] : (k < O + A ? aB[r * A + (k - O)] : 0.f);
       }
       __syncthreads();
-      mlp_forward<T, R, ROLES>(q, Xb, Yb, ld, qi ? outP2 : outP1, qi ? out2 : out1, ldo,
-                                       qi ? E.o_P2 : E.o_P1, qi ? E.ldp2 : E.ldp1, lds, true, false, Bp, r0, nvalid, pf,
-                                       ROLES ? gw_bwd(q.l[q.L - 1])
-                                       : qi ? gw_bwd(E.net[NET_Q1].l[E.net[NET_Q1].L - 1]) : gw_fwd(E.net[NET_Q2].l[0]),
-                                       &ch0, &ch1);
+      mlp_forward<T, R, ROLES>(q, Xb, Yb, ld, qi ? outP2 : outP1, qi ? out2 : out1, ldo, qi ? E.o_P2 : E.o_P1,
+                               qi ? E.ldp2 : E.ldp1, lds, true, false, Bp, r0, nvalid, &ch0, &ch1);
       STAMP(36 + qi);
     }
     // ---- backward seeds.  L_pi = mean(alpha logpi - min Q) (agent.py:251-252); min
@@ -2187,10 +2086,9 @@ __device__ __forceinline__ void actor_body(const EngineDev* __restrict__ Ep, int
     for (int qi = q_lo; qi < q_hi; ++qi) {
       const AS_C NetDev& q = E.net[NET_Q1 + qi];
       lf* G0 = mlp_backward<T, R>(q, qi ? g2B : g1B, ldo, Xb, Yb, ld, qi ? E.o_P2 : E.o_P1, qi ? E.ldp2 : E.ldp1,
-                                  lds, false, Bp, r0, nvalid, pf, gw_bwd(q.l[0]));
+                                  lds, false, Bp, r0, nvalid);
       lf* Gx = (G0 == Xb) ? Yb : Xb;
-      layer_bwd<T, R>(G0, ld, q.l[0], nullptr, 0, -1, Gx, ld, pf,
-                      qi ? gw_bwd(pi.l[pi.L - 1]) : gw_bwd(E.net[NET_Q2].l[E.net[NET_Q2].L - 1]));
+      layer_bwd<T, R>(G0, ld, q.l[0], nullptr, 0, -1, Gx, ld);
       __syncthreads();
       if (ROLES) {
         AS_G uint64_t* g = gran_at(E, G_C1 + qi, rbi);
@@ -2287,8 +2185,7 @@ __device__ __forceinline__ void actor_body(const EngineDev* __restrict__ Ep, int
   }
   __syncthreads();
   // held fragments only under the role split (bh0 / bh1 are issued only there)
-  mlp_backward<T, R, ROLES>(pi, goutB, ldo, Xb, Yb, ld, E.o_P1, E.ldp1, lds, true, Bp, r0, nvalid, pf, gw_none(),
-                                   &bh0, &bh1);
+  mlp_backward<T, R, ROLES>(pi, goutB, ldo, Xb, Yb, ld, E.o_P1, E.ldp1, lds, true, Bp, r0, nvalid, &bh0, &bh1);
   STAMP(35);
 }
 
@@ -2378,9 +2275,7 @@ __global__ void __launch_bounds__(SAC_THREADS) sac_policy_act_kernel(const Engin
     Xb[r * ld + k] = (k < O && r < nvalid) ? obs[(size_t)(r0 + r) * O + k] : 0.f;
   }
   __syncthreads();
-  Pf<T> pf;
-  pf.tag = nullptr;
-  mlp_forward<T, R>(pi, Xb, Yb, ld, outP, outB, ldo, E.o_P1, E.ldp1, lds, false, false, 0, 0, 0, pf, gw_none());
+  mlp_forward<T, R>(pi, Xb, Yb, ld, outP, outB, ldo, E.o_P1, E.ldp1, lds, false, false, 0, 0, 0);
   if (tid < nvalid) {
     const int b = r0 + tid;
     const lf* o = outB + tid * ldo;
@@ -2468,8 +2363,6 @@ __global__ void __launch_bounds__(SAC_THREADS) sac_q_values_kernel(const EngineD
     Xb[r * ld + k] = v;
   }
   __syncthreads();
-  Pf<T> pf;
-  pf.tag = nullptr;
-  mlp_forward<T, R>(q, Xb, Yb, ld, outP, outB, ldo, E.o_P1, E.ldp1, lds, false, false, 0, 0, 0, pf, gw_none());
+  mlp_forward<T, R>(q, Xb, Yb, ld, outP, outB, ldo, E.o_P1, E.ldp1, lds, false, false, 0, 0, 0);
   if (tid < nvalid) qo[(size_t)(r0 + tid) * 2 + c] = outB[tid * ldo];
 }

@@ -189,24 +189,15 @@ __device__ __forceinline__ void gemm_hs(const lf* __restrict__ A, int lda, const
 // A wave's slice of a k-split step held in registers: a step that follows a
 // hand-off (the target critics' and pi(s')'s layer 2) issues its fragment
 // before the poll instead of one more memory round trip after it.  Held when
-// the slice is at most SAC_KS_MAXC32 chunks in fp32 / one chunk in bf16 (a
-// 128-deep reduction over 8 waves).  Same-box A/Bs at C2
+// the slice is at most one chunk in either precision (in bf16 a 128-deep
+// reduction over 8 waves).  Same-box A/Bs at C2
 // (profiles/r02_ab_*.txt): bf16 +2.7% steps/s; fp32 phase A with 2- or 4-chunk
 // slices held (issued under layer 1 / before the poll): no change, so fp32
-// streams (MAXC32 = 1).  Phase C critics' two k-split steps held (SAC_KS_C):
+// streams longer slices.  Phase C critics' two k-split steps held:
 // with both issued at launch start the fp32 kernel spilled 28 VGPRs (C 18.4 ->
 // 19.8 us); with W0^T's 8 fp32 chunks issued once layer 1's held part is dead,
 // no spill and C 18.6 -> 18.1 us, +0.8% steps/s fp32, +1.3% bf16.
-#ifndef SAC_KS_HELD
-#define SAC_KS_HELD 1
-#endif
-#ifndef SAC_KS_MAXC32
-#define SAC_KS_MAXC32 1
-#endif
-#ifndef SAC_KS_C
-#define SAC_KS_C 1
-#endif
-template <typename T, int MC = (sizeof(T) == 4 ? SAC_KS_MAXC32 : 1)>
+template <typename T, int MC = 1>
 struct KsHeld {
   static constexpr int MAXC = MC;
   typename MM<T>::Frag f[MAXC];
@@ -230,7 +221,7 @@ __device__ __forceinline__ void ks_issue(KsHeld<T, MC>& kh, const GemmW& w) {
   int t, c0, c1, wpt;
   ks_slice<T>(w, t, c0, c1, wpt);
   const int nch = w.cols / MM<T>::KC, per = (nch + wpt - 1) / wpt;
-  kh.ok = SAC_KS_HELD && per <= MC;  // uniform
+  kh.ok = per <= MC;  // uniform
   if (!kh.ok) return;
   const __amdgpu_buffer_rsrc_t rs = coh_rsrc(w.p, 0xFFFFFFF0u);
   const uint32_t o = (uint32_t)(((size_t)t * 16 * w.tcols + (threadIdx.x & 63) * MM<T>::KL) * sizeof(T));
@@ -293,7 +284,7 @@ __device__ __forceinline__ void gemm_ksplit(const lf* __restrict__ A, int lda, c
 // Phase C's critic layer 2 in fp32 (N = 1: one W2 row).  As a k-split GEMM it
 // costs an LDS write of its input, a barrier, MFMAs on a tile that is 15/16
 // padding, an LDS write of the per-wave partials, a barrier and an LDS
-// reduction.  Fused (SAC_NARROW_FUSED), the dot product is formed in layer 1's
+// reduction.  Fused, the dot product is formed in layer 1's
 // epilogue: the lane multiplies its column's four row values by the column's
 // W2 element from the fp32 master, rows16_sum adds the 16 lanes of a column
 // group in a fixed order, one value per (wave, row) goes to LDS, and after the
@@ -306,16 +297,10 @@ __device__ __forceinline__ void gemm_ksplit(const lf* __restrict__ A, int lda, c
 // layer 1's dX epilogue (-3%; A scattered master loads per dY0 column and 4 A
 // accumulators per lane), pi(s')'s head writing a~' straight into X (neutral):
 // profiles/ab_narrow_items.txt.
-// SAC_NARROW_SMALL: phase C changes that move no float operation -- the critic
-// roles' s / a~ go global -> register -> X with one barrier (+1.0%), and pi
-// computes every head-backward term that does not need the critics' da before
-// it polls for them (+1.0%).  =0 for both: the earlier path.
-#ifndef SAC_NARROW_FUSED
-#define SAC_NARROW_FUSED 1
-#endif
-#ifndef SAC_NARROW_SMALL
-#define SAC_NARROW_SMALL 1
-#endif
+// Two phase C changes that moved no float operation -- the critic roles'
+// s / a~ go global -> register -> X with one barrier (+1.0%), and pi computes
+// every head-backward term that does not need the critics' da before it polls
+// for them (+1.0%).
 
 // p[i]: the lane's value for its row i (i < 4) -- a gemm_hs epilogue's lane
 // (c = lane & 15, g = lane >> 4) holds rows 4 g + i of column c.  Returns the
@@ -405,10 +390,7 @@ __device__ __forceinline__ void target_critic_split_body(const EngineDev* __rest
 
   const uint64_t step = sc.step;
   const int par = sc.par;
-#ifndef SAC_ADAM_LAST
-#define SAC_ADAM_LAST 1
-#endif
-  const bool adam_blk = (SAC_ADAM_LAST ? (role == 5 && rbi == E.nrt - 1 && h == 1) : (role == 0 && rbi == 0 && h == 0));
+  const bool adam_blk = role == 5 && rbi == E.nrt - 1 && h == 1;
   if (adam_blk && tid < 4 && (tid < 3 || (E.auto_entropy && E.alpha_update))) {
     // optimizer step counters and this step's Adam bias corrections (torch adam.py), read
     // by phases B and D only: done by the last pi(s) workgroup, off the y chain (a load
@@ -965,7 +947,7 @@ __device__ __forceinline__ void actor_split_body(const EngineDev* __restrict__ E
     // the two k-split steps of the critic's chain (layer 2's partial q, then
     // layer 0's dX for the action columns) read weights phase B has just
     // written: held (issued behind the inputs), not a cold round trip each
-    // after layer 1 / after dY0 (SAC_KS_C=0: streamed)
+    // after layer 1 / after dY0
     GemmW w2 = gw_sub<T>(L2.Wc, L2.Kp, 0, L2.Np, h * HQ, HQ, nullptr, 0);
     w2.NT = (L2.N + 15) >> 4;
     const int k0 = (O >> 4) << 4, k1 = (O + A + 15) >> 4 << 4;
@@ -980,11 +962,11 @@ __device__ __forceinline__ void actor_split_body(const EngineDev* __restrict__ E
     const int Kp0 = L0.Kp;
     // fp32, N = 1: layer 2 (the partial q) fused into layer 1's epilogue, see rows16_sum
     const bool relu_id = act == ACT_RELU || act == ACT_ID;
-    const bool fuse2 = SAC_NARROW_FUSED && sizeof(T) == 4 && L2.N == 1 && relu_id;
+    const bool fuse2 = sizeof(T) == 4 && L2.N == 1 && relu_id;
     const int lane = tid & 63, wv = wave_id();
     float w2l = 0.f;
     // one thread per element of X when it fits: s / a~ go global -> register -> X, one barrier
-    const bool x_direct = SAC_NARROW_SMALL && R * Kp0 <= SAC_THREADS;
+    const bool x_direct = R * Kp0 <= SAC_THREADS;
     float xv = 0.f;
     if (x_direct) {
       const int r = tid / Kp0, k = tid % Kp0;
@@ -996,10 +978,8 @@ __device__ __forceinline__ void actor_split_body(const EngineDev* __restrict__ E
     }
     // behind the inputs: waiting for s / a~ must not wait for these (loads retire in order)
     if (fuse2) w2l = GPC(float, net.P + L2.w_off)[h * HQ + (wv < w1.NT ? wv : 0) * 16 + (lane & 15)];
-    if (SAC_KS_C) {
-      if (!fuse2) ks_issue<T, decltype(kc2)::MAXC>(kc2, w2);
-      if (sizeof(T) == 2) ks_issue<T, decltype(kc0)::MAXC>(kc0, wt0);  // fp32: after layer 1 (its held W1 part is dead then; from here it spilled)
-    }
+    if (!fuse2) ks_issue<T, decltype(kc2)::MAXC>(kc2, w2);
+    if (sizeof(T) == 2) ks_issue<T, decltype(kc0)::MAXC>(kc0, wt0);  // fp32: after layer 1 (its held W1 part is dead then; from here it spilled)
     if (x_direct) {
       if (tid < R * Kp0) Xb[(tid / Kp0) * ld + tid % Kp0] = xv;
     } else {
@@ -1041,7 +1021,7 @@ __device__ __forceinline__ void actor_split_body(const EngineDev* __restrict__ E
         if ((lane & 3) == 0) red[wv * R + ((lane >> 4) << 2) + ((lane & 15) >> 2)] = s2;
       }
     });
-    if (SAC_KS_C && sizeof(T) == 4) ks_issue<T, decltype(kc0)::MAXC>(kc0, wt0);
+    if (sizeof(T) == 4) ks_issue<T, decltype(kc0)::MAXC>(kc0, wt0);
     if (act != ACT_RELU && act != ACT_ID) act_pass_fwd<R>(H1, ldh1, HQ >> 4, act);
     __syncthreads();
     if (fuse2) {  // the waves' partials, in wave order; outB[r][0] is read by thread r only
@@ -1132,29 +1112,27 @@ __device__ __forceinline__ void actor_split_body(const EngineDev* __restrict__ E
   // da, computed while the role waits for them: the same operations in the
   // same order, only earlier.  hb_*: this thread's (row, action dim).
   float hb_omt = 0.f, hb_sp = 0.f, hb_gstd = 0.f, hb_gdiff = 0.f, hb_sd = 0.f;
-  if (SAC_NARROW_SMALL) {
-    if (tid < R * A) {
-      const bool v = tid / A < nvalid;
-      const float gl = v ? alpha32 * (1.0f / (float)B) : 0.f;
-      const float lo = E.ls_min, hi = E.ls_max;
-      const float mu = hsv[0], lsr = hsv[1], z = hsv[2];
-      const float ls = lsr < lo ? lo : (lsr > hi ? hi : lsr);
-      const float sd = expf(ls);
-      const float t = tanhf(z);
-      const float diff = z - mu, var = sd * sd;
-      hb_omt = 1.f - t * t;
-      hb_sp = (-gl) * 2.f * (-1.f + 2.f * softplus20_grad(-2.f * z));
-      const float two_var = 2.f * var;
-      const float g_sq = -gl / two_var;
-      const float g_twovar = gl * (diff * diff) / (two_var * two_var);
-      const float g_var = 2.f * g_twovar;
-      hb_gstd = 2.f * sd * g_var - gl / sd;
-      hb_gdiff = 2.f * diff * g_sq;
-      hb_sd = sd;
-    }
-    const int NOp = L2.Np, pad = NOp - 2 * A;
-    for (int i = tid; i < R * pad; i += SAC_THREADS) goutB[(i / pad) * ldo + 2 * A + i % pad] = 0.f;
+  if (tid < R * A) {
+    const bool v = tid / A < nvalid;
+    const float gl = v ? alpha32 * (1.0f / (float)B) : 0.f;
+    const float lo = E.ls_min, hi = E.ls_max;
+    const float mu = hsv[0], lsr = hsv[1], z = hsv[2];
+    const float ls = lsr < lo ? lo : (lsr > hi ? hi : lsr);
+    const float sd = expf(ls);
+    const float t = tanhf(z);
+    const float diff = z - mu, var = sd * sd;
+    hb_omt = 1.f - t * t;
+    hb_sp = (-gl) * 2.f * (-1.f + 2.f * softplus20_grad(-2.f * z));
+    const float two_var = 2.f * var;
+    const float g_sq = -gl / two_var;
+    const float g_twovar = gl * (diff * diff) / (two_var * two_var);
+    const float g_var = 2.f * g_twovar;
+    hb_gstd = 2.f * sd * g_var - gl / sd;
+    hb_gdiff = 2.f * diff * g_sq;
+    hb_sd = sd;
   }
+  const int pad = L2.Np - 2 * A;  // dOut's padding columns
+  for (int i = tid; i < R * pad; i += SAC_THREADS) goutB[(i / pad) * ldo + 2 * A + i % pad] = 0.f;
   __syncthreads();
   STAMP(34);
   // combine the critics' unit-seed partials with the min-Q weights (L_pi = mean(alpha logpi - min Q))
@@ -1284,52 +1262,20 @@ __device__ __forceinline__ void actor_split_body(const EngineDev* __restrict__ E
   STAMP(39);
   // squashed-Gaussian head backward (models.py:79-87), one lane per (row, action dim)
   static_assert(SAC_ROWS * 32 <= SAC_THREADS, "one (row, action dim) per thread");
-  if (SAC_NARROW_SMALL) {
-    if (tid < R * A) {  // only the terms that need the critics' da are left (hb_*: before the poll)
-      const int r = tid / A, j = tid % A;
-      const bool v = r < nvalid;
-      const float lo = E.ls_min, hi = E.ls_max, scale = E.scale;
-      const float lsr = hsv[1], e = hsv[3];
-      float g_z = (gaB[r * A + j] * scale) * hb_omt;
-      g_z = g_z + hb_sp;
-      g_z = g_z + hb_gdiff;
-      const float g_mu = -hb_gdiff + g_z;
-      const float g_std = hb_gstd + g_z * e;
-      const float g_ls = g_std * hb_sd;
-      const bool in_range = (lsr >= lo) && (lsr <= hi);
-      goutB[r * ldo + j] = v ? g_mu : 0.f;
-      goutB[r * ldo + A + j] = (v && in_range) ? g_ls : 0.f;
-    }
-  } else if (tid < R * A) {
-    const int i = tid;
-    const int r = i / A, j = i % A;
+  if (tid < R * A) {  // only the terms that need the critics' da are left (hb_*: before the poll)
+    const int r = tid / A, j = tid % A;
     const bool v = r < nvalid;
-    const float gl = v ? alpha32 * (1.0f / (float)B) : 0.f;
     const float lo = E.ls_min, hi = E.ls_max, scale = E.scale;
-    const float mu = hsv[0], lsr = hsv[1], z = hsv[2], e = hsv[3];
-    const float ls = lsr < lo ? lo : (lsr > hi ? hi : lsr);
-    const float sd = expf(ls);
-    const float t = tanhf(z);
-    const float diff = z - mu, var = sd * sd;
-    float g_z = (gaB[r * A + j] * scale) * (1.f - t * t);
-    g_z = g_z + (-gl) * 2.f * (-1.f + 2.f * softplus20_grad(-2.f * z));
-    const float two_var = 2.f * var;
-    const float g_sq = -gl / two_var;
-    const float g_twovar = gl * (diff * diff) / (two_var * two_var);
-    const float g_var = 2.f * g_twovar;
-    float g_std = 2.f * sd * g_var - gl / sd;
-    const float g_diff = 2.f * diff * g_sq;
-    g_z = g_z + g_diff;
-    const float g_mu = -g_diff + g_z;
-    g_std = g_std + g_z * e;
-    const float g_ls = g_std * sd;
+    const float lsr = hsv[1], e = hsv[3];
+    float g_z = (gaB[r * A + j] * scale) * hb_omt;
+    g_z = g_z + hb_sp;
+    g_z = g_z + hb_gdiff;
+    const float g_mu = -hb_gdiff + g_z;
+    const float g_std = hb_gstd + g_z * e;
+    const float g_ls = g_std * hb_sd;
     const bool in_range = (lsr >= lo) && (lsr <= hi);
     goutB[r * ldo + j] = v ? g_mu : 0.f;
     goutB[r * ldo + A + j] = (v && in_range) ? g_ls : 0.f;
-  }
-  if (!SAC_NARROW_SMALL) {
-    const int NOp = L2.Np, pad = NOp - 2 * A;
-    for (int i = tid; i < R * pad; i += SAC_THREADS) goutB[(i / pad) * ldo + 2 * A + i % pad] = 0.f;
   }
   __syncthreads();
   // layer 2 dY^T (= dOut) + bias partials: half 0

@@ -30,8 +30,6 @@ __global__ void __launch_bounds__(SAC_THREADS) k(long long* out, float* sink) {
   lf* Y = X + 16 * 260;
   for (int i = threadIdx.x; i < 16 * 260; i += SAC_THREADS) X[i] = 0.01f * (i % 7);
   __syncthreads();
-  Pf<bf16> pf;
-  pf.tag = nullptr;
   long long t[NT];
   Held<bf16, 8> h, h1, h2;
   t[0] = __builtin_amdgcn_s_memtime();
@@ -39,26 +37,26 @@ __global__ void __launch_bounds__(SAC_THREADS) k(long long* out, float* sink) {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   t[1] = __builtin_amdgcn_s_memtime();  // [0] issue -> landed (cold)
-  layer_fwd<bf16, 16, false, 8>(X, 260, L0, L0.bias, ACT_RELU, nullptr, 0, Y, 260, nullptr, 0, pf, gw_none(), &h);
+  layer_fwd<bf16, 16, 8>(X, 260, L0, L0.bias, ACT_RELU, nullptr, 0, Y, 260, nullptr, 0, &h);
   __syncthreads();
   t[2] = __builtin_amdgcn_s_memtime();  // [1] held layer, first run of its code
   held_issue<bf16, 8>(h1, gw_fwd(L1));
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   t[3] = __builtin_amdgcn_s_memtime();  // [2] issue -> landed (second set)
-  layer_fwd<bf16, 16, false, 8>(Y, 260, L1, L1.bias, ACT_RELU, nullptr, 0, X, 260, nullptr, 0, pf, gw_none(), &h1);
+  layer_fwd<bf16, 16, 8>(Y, 260, L1, L1.bias, ACT_RELU, nullptr, 0, X, 260, nullptr, 0, &h1);
   __syncthreads();
   t[4] = __builtin_amdgcn_s_memtime();  // [3] held layer, same code again
-  layer_fwd<bf16, 16>(X, 260, L0, L0.bias, ACT_RELU, nullptr, 0, Y, 260, nullptr, 0, pf, gw_none());
+  layer_fwd<bf16, 16>(X, 260, L0, L0.bias, ACT_RELU, nullptr, 0, Y, 260, nullptr, 0);
   __syncthreads();
   t[5] = __builtin_amdgcn_s_memtime();  // [4] streamed, L2-warm
   held_issue<bf16, 8>(h2, gw_fwd(L1));
-  layer_fwd<bf16, 16, false, 8>(Y, 260, L1, L1.bias, ACT_RELU, nullptr, 0, X, 260, nullptr, 0, pf, gw_none(), &h2);
+  layer_fwd<bf16, 16, 8>(Y, 260, L1, L1.bias, ACT_RELU, nullptr, 0, X, 260, nullptr, 0, &h2);
   __syncthreads();
   t[6] = __builtin_amdgcn_s_memtime();  // [5] held issued at use (warm)
   long long r0 = __builtin_amdgcn_s_memrealtime();
   for (int i = 0; i < 4; ++i) {
-    layer_fwd<bf16, 16>(X, 260, L0, L0.bias, ACT_RELU, nullptr, 0, Y, 260, nullptr, 0, pf, gw_none());
+    layer_fwd<bf16, 16>(X, 260, L0, L0.bias, ACT_RELU, nullptr, 0, Y, 260, nullptr, 0);
     __syncthreads();
     lf* tt = X; X = Y; Y = tt;
   }
