@@ -90,7 +90,12 @@ typedef struct sac_engine_config {
    * same step (fp32 summation order aside).  The library reads no environment. */
   int32_t layout;        /* enum sac_layout */
   int32_t stage_path;    /* 0: only where the phase kernels' LDS layout does not fit;
-                            1: force the layer-synchronous stage path; -1: refuse it (create fails) */
+                            1: force the layer-synchronous stage path; -1: refuse it (create fails).
+                            1 is honoured only where the stage path applies: the hidden split was not
+                            chosen, both nets have at least two hidden layers and act_dim <= 8.  Anywhere
+                            else it is ignored without an error and the shape runs the kernels it would
+                            run at 0.  A shape past the LDS layout with act_dim > 8 has no path: create
+                            fails with the LDS figure. */
   int32_t stage_batch;   /* 0: phase C gathers the next step's batch; -1: phase A gathers its own */
   int32_t upd_parts;     /* 0: cost model; 1..4: batch parts of the large-batch (B > 1024) update tiles */
   int32_t upd_threads;   /* 0: auto; 512 / 1024: workgroup size of phase B's large-batch update tiles */

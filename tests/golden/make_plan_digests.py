@@ -58,6 +58,11 @@ EDGES = {
     "b4096_parts3": (_edge(batch=4096), {"upd_parts": 3}, NCU),
     "act16": (_edge(act=16), {}, NCU),  # the hidden split's 2 * act <= 32
     "act17": (_edge(act=17), {}, NCU),
+    # the API's widest action on each forced layout, and the stage path's 2 * act <= 16 (padded small nets, B = 40)
+    "act32_roles": (_edge(batch=40, obs=5, act=32, q_hidden=[72, 40], pi_hidden=[40, 72]), {"layout": 1}, NCU),
+    "act32_rows": (_edge(batch=40, obs=5, act=32, q_hidden=[72, 40], pi_hidden=[40, 72]), {"layout": 2}, NCU),
+    "act32_pairs": (_edge(batch=40, obs=5, act=32, q_hidden=[72, 40], pi_hidden=[40, 72]), {"layout": 3}, NCU),
+    "act8_stage": (_edge(batch=40, obs=5, act=8, q_hidden=[72, 40], pi_hidden=[40, 72]), {"stage_path": 1}, NCU),
     "obs216": (_edge(obs=216), {}, NCU),
     "pi_256_128": (_edge(pi_hidden=[256, 128]), {}, NCU),  # pi's own widths: the split refused by width
     "deep_64": (_edge(hidden=(64, 64, 64)), {}, NCU),  # 4-layer nets

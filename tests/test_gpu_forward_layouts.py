@@ -25,7 +25,10 @@ profiles/forward_layouts_gputest.txt.  Placement (tile, slot, ragged tiles) is
 compared with the kernel's own output on the same rows, bit for bit.
 
 act17: create accepts act 17 (the header's limit is act <= 32), so the 34 output
-columns cross the 32-column pad as asked; no smaller stand-in is used.
+columns cross the 32-column pad as asked; no smaller stand-in is used.  It runs
+the role kernels only: act17_rows and act17_pairs put the same 34 columns on the
+row and pair tiles' 2R-row buffers, act32_roles is the widest head (64 columns)
+and act8_stage the stage path's (2 act = 16).
 
 Head saturation: the issue's bias cycles have five entries and the engines it
 names have at most three action dimensions, so at a fixed start the +-20 means
@@ -66,6 +69,12 @@ ENGINES = {
     # the rollout kernel's action width; 2 act = 34 output columns across the 32-column pad
     "act1": (dict(obs=5, act=1, hidden=[64, 64], batch=17, capacity=64), None, "roles"),
     "act17": (dict(obs=3, act=17, hidden=[64, 64], batch=32, capacity=64), None, "roles"),
+    # wide actions on the other LDS layouts: the row and pair tiles' 2R-row buffers at 34 output columns, 64
+    # output columns (the API's maximum) and the stage path's widest head (2 act = 16)
+    "act17_rows": (dict(PAD, act=17), {"layout": "rows"}, "rows"),
+    "act17_pairs": (dict(PAD, act=17), {"layout": "pairs"}, "pairs"),
+    "act32_roles": (dict(PAD, act=32), {"layout": "roles"}, "roles"),
+    "act8_stage": (dict(PAD, act=8), {"stage_path": 1}, "stage"),
 }
 ACTS = {"relu": dict(),
         "tanh": dict(pi_act="tanh", pi_out_act="tanh", log_std_min=-0.5, log_std_max=0.5, action_scale=2.5)}

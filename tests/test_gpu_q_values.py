@@ -45,6 +45,16 @@ SHAPES = {
     "stage_obs300": (dict(obs=300, act=6, hidden=[256, 256], batch=64, capacity=128), None, "stage"),
     "stage_512": (dict(obs=24, act=4, hidden=[512, 512], batch=64, capacity=128), None, "stage"),
     "stage_400_300": (dict(obs=17, act=6, hidden=[400, 300], batch=64, capacity=128), None, "stage"),
+    # wide actions (the action columns of the critics' input: 17, 32 and 8 of obs + act = 22, 37 and 13), on
+    # the engines of test_gpu_forward_layouts.py
+    "act17_rows": (dict(obs=5, act=17, q_hidden=[72, 40], pi_hidden=[40, 72], batch=40, capacity=64),
+                   {"layout": "rows"}, "rows"),
+    "act17_pairs": (dict(obs=5, act=17, q_hidden=[72, 40], pi_hidden=[40, 72], batch=40, capacity=64),
+                    {"layout": "pairs"}, "pairs"),
+    "act32_roles": (dict(obs=5, act=32, q_hidden=[72, 40], pi_hidden=[40, 72], batch=40, capacity=64),
+                    {"layout": "roles"}, "roles"),
+    "act8_stage": (dict(obs=5, act=8, q_hidden=[72, 40], pi_hidden=[40, 72], batch=40, capacity=64),
+                   {"stage_path": 1}, "stage"),
 }
 ACTS = {"relu": dict(), "gelu_tanh": dict(q_act="gelu", q_out_act="tanh")}
 ROWS = (1, 16, 17, 33)  # one row, a full tile, a ragged tile, three tiles

@@ -224,6 +224,71 @@ def test_bad_layout_override_is_refused(field, value):
     assert rc == SAC_E_INVALID and "layout override" in lib.sac_last_error().decode()
 
 
+def _plan(c, precision, **overrides):
+    """(rc, the plan's "path" or the error message) of a config dict through
+    the host-only planner export (sac_debug_plan_host, include/
+    sac_engine_testing.h: no HIP call, with or without a GPU)."""
+    import json
+
+    lib = E.load_library()
+    lib.sac_debug_plan_host.restype = ctypes.c_int
+    lib.sac_debug_plan_host.argtypes = [ctypes.POINTER(E.EngineConfig), ctypes.c_int32, ctypes.c_char_p,
+                                        ctypes.c_size_t]
+    cfg = _cfg_of(c, precision)
+    for k, v in overrides.items():
+        setattr(cfg, k, v)
+    buf = ctypes.create_string_buffer(1 << 16)
+    rc = lib.sac_debug_plan_host(ctypes.byref(cfg), 256, buf, len(buf))
+    return rc, json.loads(buf.value)["path"] if rc == 0 else lib.sac_last_error().decode()
+
+
+PADH = dict(obs=5, q_hidden=[72, 40], pi_hidden=[40, 72], batch=40)  # tests/test_gpu_action_width.py's small shape
+
+
+@pytest.mark.parametrize("precision", ["fp32", "bf16"])
+def test_the_hidden_split_takes_two_act_up_to_32(precision):
+    """[256, 256] nets at obs 24: 2 act = 32 output columns still run the
+    hidden-split kernels, 34 the role kernels without the split."""
+    c = dict(obs=24, hidden=[256, 256], batch=64)
+    assert _plan(dict(c, act=16), precision) == (0, "split")
+    assert _plan(dict(c, act=17), precision) == (0, "roles")
+
+
+@pytest.mark.parametrize("precision", ["fp32", "bf16"])
+def test_stage_path_override_is_ignored_past_act_8(precision):
+    """stage_path = 1 forces the stage path up to 2 act = 16 (its head's
+    column limit); at act 9 the same shape is created all the same and runs
+    the role kernels: the override is ignored, not refused."""
+    assert _plan(dict(PADH, act=8), precision, stage_path=1) == (0, "wide")
+    assert _plan(dict(PADH, act=9), precision, stage_path=1) == (0, "roles")
+    assert _plan(dict(PADH, act=9), precision) == (0, "roles")
+
+
+@pytest.mark.parametrize("precision", ["fp32", "bf16"])
+@pytest.mark.parametrize("layout,path", [(1, "roles"), (2, "rows"), (3, "pairs")])
+def test_act_32_is_planned_on_every_forced_layout(layout, path, precision):
+    assert _plan(dict(PADH, act=32), precision, layout=layout) == (0, path)
+
+
+def test_act_33_is_refused():
+    rc, msg = _plan(dict(PADH, act=33), "fp32")
+    assert rc == SAC_E_INVALID and "act_dim <= 32" in msg, (rc, msg)
+
+
+@pytest.mark.parametrize("precision", ["fp32", "bf16"])
+@pytest.mark.parametrize("shape", [dict(obs=24, hidden=[512, 512], batch=64, act=9),
+                                   dict(obs=376, hidden=[256, 256], batch=64, act=17)], ids=["w512_act9", "humanoid"])
+def test_shapes_past_the_lds_layout_need_act_up_to_8(shape, precision):
+    """Past the phase kernels' LDS layout only the stage path is left, and it
+    takes 2 act <= 16: [512, 512] runs it at act 8 and is refused at act 9, as
+    is obs 376 / act 17 with [256, 256] nets (Humanoid's shape), with
+    SAC_E_INVALID and the LDS byte count."""
+    if shape["hidden"] == [512, 512]:
+        assert _plan(dict(shape, act=8), precision) == (0, "wide")
+    rc, msg = _plan(shape, precision)
+    assert rc == SAC_E_INVALID and "B of LDS per workgroup (max 163840)" in msg, (rc, msg)
+
+
 def test_engine_library_reads_no_environment():
     """the product library takes every layout choice from
     sac_engine_config; no getenv / secure_getenv import in its dynamic symbols
