@@ -269,12 +269,26 @@ const char *sac_phase_kernel_name(int32_t phase);
  * which = 3 the observation a SAC_ENV_RANDOM_OBS environment steps to at t,
  * which = 4 its reset observation at t (key = the environment seed; four
  * draws per block, u = (word >> 8) * 2^-24, obs = 2u - 1).  The initial reset
- * is t = 0; the k-th step (k = 0, 1, ...) is t = k + 1. */
+ * is t = 0; the k-th step (k = 0, 1, ...) is t = k + 1.
+ *
+ * SAC_ENV_PENDULUM is the one kind that is a control task, not a probe: the
+ * classic pendulum swing-up (sac/control_envs.py PendulumEnv; g = 10, m = l =
+ * 1, speed limit 8).  State (th, thdot) in float64 (sac_envs.pos / .vel), one
+ * torque component clipped to [action_low, action_high], observation
+ * (cos th, sin th, thdot) in fp32 (obs_dim = 3).  With u the clipped action and
+ * an = ((th + pi) mod 2 pi) - pi, a step gives reward -(an^2 + 0.1 thdot^2 +
+ * 0.001 u^2) of the PRE-step state, thdot' = clip(thdot + (15 sin th + 3 u) dt,
+ * -8, 8), th' = th + thdot' dt; never terminated, truncated at max_steps.
+ * RNG: which = 4, block 0 at vector step t gives the reset state an episode
+ * truncated at t restarts from (t = 0: the initial reset; key = the environment
+ * seed): th = pi (2 u0 - 1), thdot = 2 u1 - 1 in double, u0 / u1 the block's
+ * first two uniforms.  Codes 4..7 are not assigned. */
 enum sac_env_kind {
   SAC_ENV_CONSTANT_REWARD = 0,  /* envs.py ConstantRewardEnv: r = reward, terminated at max_steps */
   SAC_ENV_QUADRATIC_ACTION = 1, /* QuadraticActionRewardEnv: r = -(clip(a) - target)^2 in fp32 */
   SAC_ENV_RANDOM_OBS = 2,       /* RandomObsBinaryRewardEnv: uniform obs, r = +1 iff |a| <= threshold */
-  SAC_ENV_POINT_MASS = 3        /* OneDPointMassReachEnv: pos += clip(a) * dt, reach goal_pos */
+  SAC_ENV_POINT_MASS = 3,       /* OneDPointMassReachEnv: pos += clip(a) * dt, reach goal_pos */
+  SAC_ENV_PENDULUM = 8          /* control_envs.py PendulumEnv: swing-up, obs (cos th, sin th, thdot) */
 };
 
 /* The constructor arguments of the sac/envs.py class of `kind` (the others are
@@ -282,14 +296,16 @@ enum sac_env_kind {
 typedef struct sac_env_config {
   int32_t kind;                 /* enum sac_env_kind */
   int32_t num_envs;
-  int32_t obs_dim;              /* 1, except SAC_ENV_RANDOM_OBS (its obs_dim argument) */
+  int32_t obs_dim;              /* 1, except SAC_ENV_RANDOM_OBS (its obs_dim argument) and SAC_ENV_PENDULUM (3) */
   int32_t max_steps;
   double reward;                              /* SAC_ENV_CONSTANT_REWARD */
   double target;                              /* SAC_ENV_QUADRATIC_ACTION */
-  double action_low, action_high;             /* SAC_ENV_QUADRATIC_ACTION, SAC_ENV_POINT_MASS */
+  double action_low, action_high;             /* SAC_ENV_QUADRATIC_ACTION, SAC_ENV_POINT_MASS, SAC_ENV_PENDULUM
+                                                 (-max_torque, max_torque) */
   double threshold;                           /* SAC_ENV_RANDOM_OBS */
-  double start_pos, goal_pos, dt, step_penalty, goal_reward, goal_tolerance;  /* SAC_ENV_POINT_MASS */
-  uint64_t seed;                /* observation draws of SAC_ENV_RANDOM_OBS */
+  double start_pos, goal_pos, dt, step_penalty, goal_reward, goal_tolerance;  /* SAC_ENV_POINT_MASS; dt also
+                                                                                 SAC_ENV_PENDULUM */
+  uint64_t seed;                /* observation draws of SAC_ENV_RANDOM_OBS, reset draws of SAC_ENV_PENDULUM */
 } sac_env_config;
 
 /* One cell of the episode record: written by every environment on every step. */
@@ -305,15 +321,17 @@ typedef struct sac_envs {
   float *obs;                   /* [num_envs][obs_dim] current observations */
   int32_t *step;                /* [num_envs] step in the episode (envs.py current_step) */
   int32_t *ep_length;           /* [num_envs] length of the running episode */
-  double *pos;                  /* [num_envs] SAC_ENV_POINT_MASS position */
+  double *pos;                  /* [num_envs] SAC_ENV_POINT_MASS position; SAC_ENV_PENDULUM angle th */
   double *ep_return;            /* [num_envs] return of the running episode */
   sac_env_episode *episodes;    /* [ring_steps][num_envs] dense ring indexed by t % ring_steps and env row;
                                    NULL: no record (sac_envs_step only) */
   int64_t ring_steps;
+  double *vel;                  /* [num_envs] SAC_ENV_PENDULUM angular velocity thdot; may be NULL for the probes */
 } sac_envs;
 
 /* Reset every environment: step and episode counters to 0, the initial
- * observation (draws of SAC_ENV_RANDOM_OBS: which = 4, t = 0, key `seed`).
+ * observation (draws of SAC_ENV_RANDOM_OBS and SAC_ENV_PENDULUM: which = 4, t = 0,
+ * key `seed`).
  * Replaces: SyncVectorEnv.reset (sac/vector_env.py:39-46). */
 int sac_envs_reset(const sac_envs *envs, uint64_t seed, void *stream);
 

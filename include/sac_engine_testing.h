@@ -63,6 +63,20 @@ int sac_debug_rollout_eps_host(uint64_t seed, uint64_t t, int32_t n, int32_t act
  * t).  Counter (t, i, which << 16 | k / 4), key seed (the environments');
  * output word k % 4: u = (word >> 8) * 2^-24, obs = 2u - 1 in [-1, 1). */
 int sac_debug_env_obs_host(uint64_t seed, uint64_t t, int32_t which, int32_t n, int32_t obs_dim, float *out);
+/* One step of SAC_ENV_PENDULUM on the host: the inline dynamics the device
+ * kernels call (csrc/sac_envs.h pendulum_dynamics), compiled for the host, so
+ * sin / cos are the host libm's.  cfg supplies action_low, action_high, dt and
+ * max_steps (kind must be SAC_ENV_PENDULUM); state = (th, thdot) is advanced in
+ * place; `step` is the step in the episode before this one.  Outputs: the
+ * observation stepped to, the reward of the pre-step state, truncated = step +
+ * 1 >= max_steps.  No autoreset: the caller applies the reset draw below. */
+int sac_debug_env_step_host(const sac_env_config *cfg, double state[2], int32_t step, float action,
+                            float obs_out[3], double *reward, int32_t *truncated);
+/* The reset state (th, thdot) of SAC_ENV_PENDULUM row `row` at vector step t
+ * (t = 0: the initial reset) for environment seed `seed`: the same inline code
+ * as the device's, state_out = {pi (2 u0 - 1), 2 u1 - 1} with u0, u1 the first
+ * two uniforms of sac_debug_env_obs_host's which = 4 block 0. */
+int sac_debug_env_reset_host(uint64_t seed, uint64_t t, int32_t row, double state_out[2]);
 /* A host-only engine: the validated config and no device state (no HIP call is
  * made).  For the argument checks of the forward-only entry points --
  * sac_q_values, sac_q_values_replay, sac_policy_act and sac_rollout_step -- on

@@ -330,8 +330,12 @@ static void set_lds_attrs(size_t bytes) {
   (void)hipFuncSetAttribute((const void*)sac_actor<T, false>, hipFuncAttributeMaxDynamicSharedMemorySize, b);
   (void)hipFuncSetAttribute((const void*)sac_actor<T, true>, hipFuncAttributeMaxDynamicSharedMemorySize, b);
   (void)hipFuncSetAttribute((const void*)sac_policy_act_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, b);
-  (void)hipFuncSetAttribute((const void*)sac_rollout_step_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, b);
-  (void)hipFuncSetAttribute((const void*)sac_rollout_step_dev_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, b);
+  (void)hipFuncSetAttribute((const void*)sac_rollout_step_kernel<T, false>, hipFuncAttributeMaxDynamicSharedMemorySize, b);
+  (void)hipFuncSetAttribute((const void*)sac_rollout_step_kernel<T, true>, hipFuncAttributeMaxDynamicSharedMemorySize, b);
+  (void)hipFuncSetAttribute((const void*)sac_rollout_step_dev_kernel<T, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            b);
+  (void)hipFuncSetAttribute((const void*)sac_rollout_step_dev_kernel<T, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            b);
   (void)hipFuncSetAttribute((const void*)sac_q_values_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, b);
   (void)hipFuncSetAttribute((const void*)sac_target_critic_split<T>, hipFuncAttributeMaxDynamicSharedMemorySize, b);
   (void)hipFuncSetAttribute((const void*)sac_target_critic_pairs<T>, hipFuncAttributeMaxDynamicSharedMemorySize, b);
@@ -494,13 +498,16 @@ static int check_replay(sac_engine* e, const sac_replay* rb) {
 static int check_envs(const sac_envs* ev, bool need_ring) {
   if (!ev) return fail(SAC_E_INVALID, "null environments");
   const sac_env_config& c = ev->cfg;
-  if (c.kind < SAC_ENV_CONSTANT_REWARD || c.kind > SAC_ENV_POINT_MASS)
+  const bool pendulum = c.kind == SAC_ENV_PENDULUM;
+  if ((c.kind < SAC_ENV_CONSTANT_REWARD || c.kind > SAC_ENV_POINT_MASS) && !pendulum)
     return fail(SAC_E_INVALID, "unknown environment kind " + std::to_string(c.kind));
   if (c.num_envs < 1) return fail(SAC_E_INVALID, "num_envs >= 1");
   if (c.max_steps < 1) return fail(SAC_E_INVALID, "max_steps >= 1");
-  if (c.kind == SAC_ENV_RANDOM_OBS ? (c.obs_dim < 1 || c.obs_dim > 4 * 65536) : c.obs_dim != 1)
+  if (pendulum && c.obs_dim != SAC_PENDULUM_OBS_DIM)
+    return fail(SAC_E_INVALID, "obs_dim must be 3 for SAC_ENV_PENDULUM");
+  if (!pendulum && (c.kind == SAC_ENV_RANDOM_OBS ? (c.obs_dim < 1 || c.obs_dim > 4 * 65536) : c.obs_dim != 1))
     return fail(SAC_E_INVALID, "obs_dim must be 1 (SAC_ENV_RANDOM_OBS: 1..262144)");
-  if (!ev->obs || !ev->step || !ev->ep_length || !ev->pos || !ev->ep_return)
+  if (!ev->obs || !ev->step || !ev->ep_length || !ev->pos || !ev->ep_return || (pendulum && !ev->vel))
     return fail(SAC_E_INVALID, "null environment state");
   if (need_ring ? (!ev->episodes || ev->ring_steps < 1) : (ev->episodes && ev->ring_steps < 1))
     return fail(SAC_E_INVALID, "episode ring needs episodes != NULL and ring_steps >= 1");
@@ -912,12 +919,11 @@ int sac_rollout_step(sac_engine* e, const sac_envs* envs, const sac_replay* rb, 
   const int64_t new_pos = (pos_host + n) % cap;
   const int blocks = (int)((n + SAC_ROWS - 1) / SAC_ROWS);
   hipStream_t s = (hipStream_t)stream;
-  if (e->cfg.precision == SAC_PREC_BF16)
-    sac_rollout_step_kernel<bf16><<<blocks, SAC_THREADS, e->lds_bytes, s>>>(e->d, *envs, *rb, pos_host, new_size, new_pos,
-                                                                           t, deterministic ? 1 : 0, store ? 1 : 0);
-  else
-    sac_rollout_step_kernel<float><<<blocks, SAC_THREADS, e->lds_bytes, s>>>(e->d, *envs, *rb, pos_host, new_size, new_pos,
-                                                                            t, deterministic ? 1 : 0, store ? 1 : 0);
+  const bool bf = e->cfg.precision == SAC_PREC_BF16, pendulum = envs->cfg.kind == SAC_ENV_PENDULUM;
+  auto kernel = bf ? (pendulum ? sac_rollout_step_kernel<bf16, true> : sac_rollout_step_kernel<bf16, false>)
+                   : (pendulum ? sac_rollout_step_kernel<float, true> : sac_rollout_step_kernel<float, false>);
+  kernel<<<blocks, SAC_THREADS, e->lds_bytes, s>>>(e->d, *envs, *rb, pos_host, new_size, new_pos, t, deterministic ? 1 : 0,
+                                                   store ? 1 : 0);
   HIPCHK(hipGetLastError());
   return SAC_OK;
 }
@@ -928,12 +934,10 @@ static int launch_rollout_dev(sac_engine* e, const sac_envs* envs, const sac_rep
   const int blocks = (envs->cfg.num_envs + SAC_ROWS - 1) / SAC_ROWS;
   const int64_t* cur = cursor + 4 * parity;
   int64_t* nxt = cursor + 4 * (parity ^ 1);
-  if (e->cfg.precision == SAC_PREC_BF16)
-    sac_rollout_step_dev_kernel<bf16><<<blocks, SAC_THREADS, e->lds_bytes, s>>>(e->d, *envs, *rb, cur, nxt, deterministic,
-                                                                               store);
-  else
-    sac_rollout_step_dev_kernel<float><<<blocks, SAC_THREADS, e->lds_bytes, s>>>(e->d, *envs, *rb, cur, nxt, deterministic,
-                                                                                store);
+  const bool bf = e->cfg.precision == SAC_PREC_BF16, pendulum = envs->cfg.kind == SAC_ENV_PENDULUM;
+  auto kernel = bf ? (pendulum ? sac_rollout_step_dev_kernel<bf16, true> : sac_rollout_step_dev_kernel<bf16, false>)
+                   : (pendulum ? sac_rollout_step_dev_kernel<float, true> : sac_rollout_step_dev_kernel<float, false>);
+  kernel<<<blocks, SAC_THREADS, e->lds_bytes, s>>>(e->d, *envs, *rb, cur, nxt, deterministic, store);
   HIPCHK(hipGetLastError());
   return SAC_OK;
 }
@@ -1038,6 +1042,23 @@ int sac_debug_env_obs_host(uint64_t seed, uint64_t t, int32_t which, int32_t n, 
       philox_uniform4(seed, t, (uint32_t)i, (uint32_t)which, (uint32_t)b, u);
       for (int k = 0; k < 4 && 4 * b + k < obs_dim; ++k) out[(size_t)i * obs_dim + 4 * b + k] = env_uniform_obs(u[k]);
     }
+  return SAC_OK;
+}
+
+int sac_debug_env_step_host(const sac_env_config* cfg, double state[2], int32_t step, float action, float obs_out[3],
+                            double* reward, int32_t* truncated) {
+  if (!cfg || !state || !obs_out || !reward || !truncated)
+    return fail(SAC_E_INVALID, "need cfg, state, obs_out, reward and truncated != NULL");
+  if (cfg->kind != SAC_ENV_PENDULUM) return fail(SAC_E_INVALID, "env_step_host: kind must be SAC_ENV_PENDULUM");
+  if (cfg->max_steps < 1 || step < 0) return fail(SAC_E_INVALID, "env_step_host: max_steps >= 1 and step >= 0");
+  *reward = pendulum_dynamics(state[0], state[1], action, cfg->action_low, cfg->action_high, cfg->dt, obs_out);
+  *truncated = step + 1 >= cfg->max_steps ? 1 : 0;
+  return SAC_OK;
+}
+
+int sac_debug_env_reset_host(uint64_t seed, uint64_t t, int32_t row, double state_out[2]) {
+  if (!state_out || row < 0) return fail(SAC_E_INVALID, "need row >= 0 and state_out != NULL");
+  pendulum_reset_draw(seed, t, (uint32_t)row, state_out[0], state_out[1]);
   return SAC_OK;
 }
 

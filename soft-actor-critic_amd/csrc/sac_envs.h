@@ -1,19 +1,22 @@
-// sac_envs.h — the probe environments of sac/envs.py on the device, and the
-// fused rollout step (act -> step -> store in one launch).
+// sac_envs.h — the probe environments of sac/envs.py and the Pendulum swing-up
+// of sac/control_envs.py on the device, and the fused rollout step (act -> step
+// -> store in one launch).
 //
-//   * env_step: ONE statement of the four probes' dynamics, with the semantics
+//   * pendulum_dynamics: one step of the swing-up in float64, host-callable;
+//   * env_step: ONE statement of the environments' dynamics, with the semantics
 //     sac.vector_env.SyncVectorEnv gives the host classes (same-step autoreset;
 //     the transition is (obs, action, reward, final_obs, terminated | truncated)).
 //     Whatever sac/envs.py keeps as a Python float is a double here, so the
 //     fp32-rounded observations and rewards are the host's bit for bit;
 //   * sac_envs_step_kernel: N environments stepped with the caller's actions;
-//   * sac_rollout_step_kernel<T>: sibling of sac_policy_act_kernel<T> (same
-//     workgroup shape, LDS layout and mlp_forward call); the thread that owns
-//     environment row i samples its action, steps the environment and writes
-//     the transition into the replay ring;
-//   * sac_rollout_step_dev_kernel<T>: the same body with (size, pos, t) read
-//     from a two-slot cursor in device memory, so whole loop iterations replay
-//     from one hipGraph (sac_engine_loop_graph).
+//   * sac_rollout_step_kernel<T, PENDULUM>: sibling of sac_policy_act_kernel<T>
+//     (same workgroup shape, LDS layout and mlp_forward call); the thread that
+//     owns environment row i samples its action, steps the environment and
+//     writes the transition into the replay ring.  Compiled once for the probes
+//     and once for the pendulum; the host picks by the environments' kind;
+//   * sac_rollout_step_dev_kernel<T, PENDULUM>: the same body with (size, pos,
+//     t) read from a two-slot cursor in device memory, so whole loop iterations
+//     replay from one hipGraph (sac_engine_loop_graph).
 //
 // State is caller-owned global memory (include/sac_engine.h sac_envs).  Every
 // environment row is read and written by exactly one thread of one launch, and
@@ -46,16 +49,97 @@ __host__ __device__ inline float env_uniform_obs(float u) { return 2.0f * u - 1.
 // np.clip on float32: min(max(x, lo), hi) with NaN passed through
 __host__ __device__ inline float clip_f32(float x, float lo, float hi) { return x < lo ? lo : (x > hi ? hi : x); }
 
+// ---- Pendulum swing-up (sac/control_envs.py PendulumEnv) --------------------
+// State (th, thdot) in float64; g = 10, m = l = 1, so 3 g / (2 l) = 15 and
+// 3 / (m l^2) = 3 exactly.  Every operation below is the host class's, in its
+// order (the library is built with -ffp-contract=off: no fused multiply-adds).
+#define SAC_PENDULUM_OBS_DIM 3
+#define SAC_PENDULUM_MAX_SPEED 8.0
+#define SAC_PI 3.141592653589793
+
+// Python's ((th + pi) % (2 pi)) - pi: the angle in [-pi, pi)
+__host__ __device__ inline double pendulum_angle(double th) {
+  double an = fmod(th + SAC_PI, 2.0 * SAC_PI);
+  if (an < 0.0) an += 2.0 * SAC_PI;
+  return an - SAC_PI;
+}
+
+// The observation of a state, in fp32
+__host__ __device__ inline void pendulum_obs(double th, double thdot, float obs[SAC_PENDULUM_OBS_DIM]) {
+  obs[0] = (float)cos(th);
+  obs[1] = (float)sin(th);
+  obs[2] = (float)thdot;
+}
+
+// One step from (th, thdot) with action a: the reward of the PRE-step state,
+// the new state in place and its observation (cos th', sin th', thdot') in fp32.
+__host__ __device__ inline double pendulum_dynamics(double& th, double& thdot, float a, double action_low,
+                                                    double action_high, double dt, float obs[SAC_PENDULUM_OBS_DIM]) {
+  const double u = (double)clip_f32(a, (float)action_low, (float)action_high);
+  const double an = pendulum_angle(th);
+  const double reward = -(an * an + 0.1 * thdot * thdot + 0.001 * u * u);
+  double v = thdot + (15.0 * sin(th) + 3.0 * u) * dt;
+  v = v < -SAC_PENDULUM_MAX_SPEED ? -SAC_PENDULUM_MAX_SPEED : (v > SAC_PENDULUM_MAX_SPEED ? SAC_PENDULUM_MAX_SPEED : v);
+  th = th + v * dt;
+  thdot = v;
+  pendulum_obs(th, thdot, obs);
+  return reward;
+}
+
+// The reset draw of env row `row` at vector step t: th ~ U[-pi, pi), thdot ~
+// U[-1, 1) from the first two uniforms of the row's ENV_WHICH_RESET block 0.
+__host__ __device__ inline void pendulum_reset_draw(uint64_t seed, uint64_t t, uint32_t row, double& th,
+                                                    double& thdot) {
+  float u[4];
+  philox_uniform4(seed, t, row, ENV_WHICH_RESET, 0, u);
+  th = SAC_PI * (2.0 * (double)u[0] - 1.0);
+  thdot = 2.0 * (double)u[1] - 1.0;
+}
+
 struct EnvOut {
   double reward;  // as the host class returns it (probe 1's fp32 reward widened, as float(r) does)
   bool terminated, truncated;
 };
 
+// The pendulum's step of env_step: state (th, thdot) in ev.pos / ev.vel, three
+// observation components, no termination, truncation at max_steps; a truncated
+// row takes its reset draw of this t as its current state and observation.
+// Inlined: a noinline call costs the rollout kernels 192 B of scratch per lane
+// (profiles/pendulum_rollout_resources.txt).
+__device__ __forceinline__ EnvOut env_step_pendulum(const sac_envs& ev, int i, uint64_t t, float action,
+                                                    float* final_obs) {
+  const sac_env_config& c = ev.cfg;
+  const int step = ev.step[i] + 1;
+  float* cur = ev.obs + (size_t)i * SAC_PENDULUM_OBS_DIM;
+  double th = ev.pos[i], thdot = ev.vel[i];
+  float fo[SAC_PENDULUM_OBS_DIM];
+  EnvOut o;
+  o.reward = pendulum_dynamics(th, thdot, action, c.action_low, c.action_high, c.dt, fo);
+  o.terminated = false;
+  o.truncated = step >= c.max_steps;
+  if (final_obs)
+    for (int k = 0; k < SAC_PENDULUM_OBS_DIM; ++k) final_obs[k] = fo[k];
+  if (o.truncated) {
+    pendulum_reset_draw(c.seed, t, (uint32_t)i, th, thdot);
+    pendulum_obs(th, thdot, fo);
+  }
+  for (int k = 0; k < SAC_PENDULUM_OBS_DIM; ++k) cur[k] = fo[k];
+  ev.step[i] = o.truncated ? 0 : step;
+  ev.pos[i] = th;
+  ev.vel[i] = thdot;
+  return o;
+}
+
 // One step of environment row i at vector step t with the action's first
 // component.  Writes the observation stepped to into final_obs[obs_dim] (unless
 // NULL), the environment's new current observation (the reset observation where
 // the episode ended) into ev.obs, and its step counter / position.
+// PENDULUM is the kind, decided by the launch: the rollout kernels are compiled
+// once per side, so the probes' kernels hold none of the pendulum's code (behind
+// a run-time branch it cost them 16 more spilled SGPRs and 1-2 % per launch).
+template <bool PENDULUM>
 __device__ __forceinline__ EnvOut env_step(const sac_envs& ev, int i, uint64_t t, float action, float* final_obs) {
+  if (PENDULUM) return env_step_pendulum(ev, i, t, action, final_obs);
   const sac_env_config& c = ev.cfg;
   const int O = c.obs_dim;
   const int step = ev.step[i] + 1;
@@ -149,12 +233,20 @@ __global__ void sac_envs_reset_kernel(sac_envs ev, uint64_t seed) {
       for (int k = 0; k < 4; ++k)
         if (4 * b + k < O) cur[4 * b + k] = env_uniform_obs(u[k]);
     }
-  } else {
+  } else if (c.kind != SAC_ENV_PENDULUM) {
     cur[0] = c.kind == SAC_ENV_POINT_MASS ? (float)c.start_pos : 0.f;
   }
   ev.step[i] = 0;
   ev.ep_length[i] = 0;
-  ev.pos[i] = c.kind == SAC_ENV_POINT_MASS ? c.start_pos : 0.0;
+  if (c.kind == SAC_ENV_PENDULUM) {
+    double th, thdot;
+    pendulum_reset_draw(seed, 0, (uint32_t)i, th, thdot);
+    pendulum_obs(th, thdot, cur);
+    ev.pos[i] = th;
+    ev.vel[i] = thdot;
+  } else {
+    ev.pos[i] = c.kind == SAC_ENV_POINT_MASS ? c.start_pos : 0.0;
+  }
   ev.ep_return[i] = 0.0;
 }
 
@@ -165,7 +257,9 @@ __global__ void sac_envs_step_kernel(sac_envs ev, const float* __restrict__ acti
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= ev.cfg.num_envs) return;
   const int O = ev.cfg.obs_dim;
-  const EnvOut o = env_step(ev, i, t, actions[(size_t)i * SAC_ENV_ACT_DIM], final_obs + (size_t)i * O);
+  const float a = actions[(size_t)i * SAC_ENV_ACT_DIM];
+  const EnvOut o = ev.cfg.kind == SAC_ENV_PENDULUM ? env_step<true>(ev, i, t, a, final_obs + (size_t)i * O)
+                                                   : env_step<false>(ev, i, t, a, final_obs + (size_t)i * O);
   env_account(ev, i, t, o);
   for (int k = 0; k < O; ++k) obs[(size_t)i * O + k] = ev.obs[(size_t)i * O + k];
   reward[i] = (float)o.reward;
@@ -178,7 +272,7 @@ __global__ void sac_envs_step_kernel(sac_envs ev, const float* __restrict__ acti
 // replay's (size, write slot) after this step, as sac_replay_push computes
 // them.  Both kernels below are this body; they differ in where (pos, t) come
 // from.
-template <typename T>
+template <typename T, bool PENDULUM>
 __device__ __forceinline__ void rollout_step_body(const EngineDev* __restrict__ Ep, const sac_envs& ev,
                                                   const sac_replay& rb, int64_t pos, int64_t new_size, int64_t new_pos,
                                                   uint64_t t, int deterministic, int store) {
@@ -235,7 +329,7 @@ __device__ __forceinline__ void rollout_step_body(const EngineDev* __restrict__ 
         if (store) rb.act[slot * rs.act + j] = a;
       }
     }
-    const EnvOut eo = env_step(ev, i, t, a0, store ? rb.next_obs + slot * rs.obs : nullptr);
+    const EnvOut eo = env_step<PENDULUM>(ev, i, t, a0, store ? rb.next_obs + slot * rs.obs : nullptr);
     env_account(ev, i, t, eo);
     if (store) {
       rb.rew[slot * rs.one] = (float)eo.reward;
@@ -250,13 +344,14 @@ __device__ __forceinline__ void rollout_step_body(const EngineDev* __restrict__ 
 }
 
 // One workgroup per SAC_ROWS environments; (size, pos, t) are host arguments,
-// new_size / new_pos computed by the host as sac_replay_push does.
-template <typename T>
+// new_size / new_pos computed by the host as sac_replay_push does.  PENDULUM:
+// ev.cfg.kind == SAC_ENV_PENDULUM (the host picks the instantiation).
+template <typename T, bool PENDULUM>
 __global__ void __launch_bounds__(SAC_THREADS) sac_rollout_step_kernel(const EngineDev* __restrict__ Ep, sac_envs ev,
                                                                       sac_replay rb, int64_t pos, int64_t new_size,
                                                                       int64_t new_pos, uint64_t t, int deterministic,
                                                                       int store) {
-  rollout_step_body<T>(Ep, ev, rb, pos, new_size, new_pos, t, deterministic, store);
+  rollout_step_body<T, PENDULUM>(Ep, ev, rb, pos, new_size, new_pos, t, deterministic, store);
 }
 
 // The same step with the loop cursor on the device (include/sac_engine.h
@@ -267,7 +362,7 @@ __global__ void __launch_bounds__(SAC_THREADS) sac_rollout_step_kernel(const Eng
 // written), so nothing depends on the order workgroups run in and the launch
 // can be replayed from a hipGraph with the slots alternating.  A cursor outside
 // the ring (never seeded) stores nothing and does not advance.
-template <typename T>
+template <typename T, bool PENDULUM>
 __global__ void __launch_bounds__(SAC_THREADS) sac_rollout_step_dev_kernel(const EngineDev* __restrict__ Ep, sac_envs ev,
                                                                           sac_replay rb,
                                                                           const int64_t* __restrict__ cur,
@@ -278,7 +373,7 @@ __global__ void __launch_bounds__(SAC_THREADS) sac_rollout_step_dev_kernel(const
   if (size < 0 || size > cap || pos < 0 || pos >= cap) return;
   const int64_t new_size = store ? (size + n < cap ? size + n : cap) : size;
   const int64_t new_pos = store ? (pos + n) % cap : pos;
-  rollout_step_body<T>(Ep, ev, rb, pos, new_size, new_pos, t, deterministic, store);
+  rollout_step_body<T, PENDULUM>(Ep, ev, rb, pos, new_size, new_pos, t, deterministic, store);
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     nxt[0] = new_size;
     nxt[1] = new_pos;

@@ -76,7 +76,7 @@ class ReplayDesc(ctypes.Structure):
 
 
 # sac_env_kind (include/sac_engine.h) by the names sac/train_replicas.py uses
-ENV_KINDS = {"constant_reward": 0, "quadratic_action": 1, "random_obs_binary": 2, "point_mass": 3}
+ENV_KINDS = {"constant_reward": 0, "quadratic_action": 1, "random_obs_binary": 2, "point_mass": 3, "pendulum": 8}
 # the double parameters of sac_env_config, in struct order
 ENV_PARAMS = ("reward", "target", "action_low", "action_high", "threshold", "start_pos", "goal_pos", "dt",
               "step_penalty", "goal_reward", "goal_tolerance")
@@ -95,7 +95,7 @@ class EnvEpisode(ctypes.Structure):
 class EnvsDesc(ctypes.Structure):
     _fields_ = [("cfg", EnvConfig), ("obs", ctypes.c_void_p), ("step", ctypes.c_void_p),
                 ("ep_length", ctypes.c_void_p), ("pos", ctypes.c_void_p), ("ep_return", ctypes.c_void_p),
-                ("episodes", ctypes.c_void_p), ("ring_steps", ctypes.c_int64)]
+                ("episodes", ctypes.c_void_p), ("ring_steps", ctypes.c_int64), ("vel", ctypes.c_void_p)]
 
 
 # name -> (restype, argtypes): every symbol include/sac_engine.h declares

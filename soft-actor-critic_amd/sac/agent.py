@@ -764,8 +764,9 @@ class SAC:
 
         env = vec_env if vec_env is not None else self.env
         if not isinstance(env, DeviceVectorEnv):
-            raise TypeError(f"{what} needs a sac.device_envs.DeviceVectorEnv (a probe environment of sac.envs "
-                            "resident on the device); other environments run through run_vectorized_training_loop")
+            raise TypeError(f"{what} needs a sac.device_envs.DeviceVectorEnv (a probe environment of sac.envs or "
+                            "the pendulum of sac.control_envs resident on the device); other environments run "
+                            "through run_vectorized_training_loop")
         return env
 
     def run_device_training_loop(self, total_env_steps: int, vec_env: Any = None, logger=None,

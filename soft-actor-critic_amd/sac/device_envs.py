@@ -1,6 +1,7 @@
-"""The probe environments of ``sac.envs`` resident on the device.
+"""The probe environments of ``sac.envs`` and the pendulum swing-up of
+``sac.control_envs`` resident on the device.
 
-``DeviceVectorEnv`` holds N copies of one probe environment as device state
+``DeviceVectorEnv`` holds N copies of one environment as device state
 (``include/sac_engine.h`` ``sac_envs``) and steps them in HIP kernels with the
 semantics ``sac.vector_env.SyncVectorEnv`` gives the host classes: same-step
 autoreset, ``infos["final_obs"]`` holding the true next state of every env.
@@ -15,10 +16,14 @@ Two ways to step:
   launch (the policy forward, the squashed-Gaussian sample, the env step and
   the write into the replay ring), the step of ``SAC.run_device_training_loop``.
 
-The only randomness is ``RandomObsBinaryRewardEnv``'s observations: Philox
-draws keyed by the seed given to ``reset`` with counter (vector step, env row),
-so a run is reproducible whatever order the workgroups run in (the host class
-draws from numpy's generator instead: same distribution, other numbers).
+The only randomness is ``RandomObsBinaryRewardEnv``'s observations and
+``PendulumEnv``'s reset states: Philox draws keyed by the seed given to
+``reset`` with counter (vector step, env row), so a run is reproducible
+whatever order the workgroups run in (the host classes draw from numpy's
+generator instead: same distribution, other numbers).  The pendulum's float64
+arithmetic is the host class's in the same order; its ``sin`` / ``cos`` are the
+device library's, so its fp32 observations and rewards may differ from the
+host's in the last bit.
 
 Episode statistics: every step writes each env's running (return, length,
 ended) into a dense ring ``[ring_steps][N]`` indexed by ``t % ring_steps``;
@@ -37,6 +42,7 @@ import numpy as np
 import torch
 
 from . import _engine as E
+from . import control_envs
 from . import envs as host_envs
 
 # kind name -> (sac_env_kind, host class); the names of sac/train_replicas.py
@@ -45,6 +51,7 @@ KINDS = {
     "quadratic_action": (1, host_envs.QuadraticActionRewardEnv),
     "random_obs_binary": (2, host_envs.RandomObsBinaryRewardEnv),
     "point_mass": (3, host_envs.OneDPointMassReachEnv),
+    "pendulum": (8, control_envs.PendulumEnv),
 }
 _BY_CLASS = {cls.__name__: name for name, (_, cls) in KINDS.items()}
 _BY_CODE = {code: name for name, (code, _) in KINDS.items()}
@@ -56,6 +63,7 @@ _PARAM_ATTRS = {
     "random_obs_binary": {"threshold": "threshold"},
     "point_mass": {"start_pos": "start_pos", "goal_pos": "goal_pos", "dt": "dt", "step_penalty": "step_penalty",
                    "goal_reward": "goal_reward", "goal_tolerance": "goal_tolerance"},
+    "pendulum": {"dt": "dt"},  # the torque bound is the action space's, as for every kind
 }
 
 
@@ -68,7 +76,7 @@ def kind_name(kind_or_name) -> str:
     else:
         name = _BY_CODE.get(int(kind_or_name))
     if name not in KINDS:
-        raise ValueError(f"unknown probe environment {kind_or_name!r} (one of {sorted(KINDS)})")
+        raise ValueError(f"unknown device environment {kind_or_name!r} (one of {sorted(KINDS)})")
     return name
 
 
@@ -82,7 +90,8 @@ class DeviceVectorEnv:
 
     @classmethod
     def from_env(cls, host_env, num_envs: int, device=None, ring_steps: Optional[int] = None) -> "DeviceVectorEnv":
-        """N device copies of ``host_env`` (an instance of a ``sac.envs`` class), with its parameters."""
+        """N device copies of ``host_env`` (an instance of a ``sac.envs`` class or of
+        ``sac.control_envs.PendulumEnv``), with its parameters."""
         kind_name(type(host_env))
         self = cls.__new__(cls)
         self._setup(host_env, num_envs, device, ring_steps)
@@ -119,7 +128,8 @@ class DeviceVectorEnv:
             raise ValueError("ring_steps must be >= 1")
         self.obs = torch.zeros(N, self.obs_dim, dtype=torch.float32, device=dev)
         self.counters = torch.zeros(2, N, dtype=torch.int32, device=dev)   # step in episode, episode length
-        self.dstate = torch.zeros(2, N, dtype=torch.float64, device=dev)   # position, episode return
+        # position (the pendulum: angle), episode return; the pendulum adds its angular velocity
+        self.dstate = torch.zeros(3 if self.kind == "pendulum" else 2, N, dtype=torch.float64, device=dev)
         self.ring = torch.zeros(self.ring_steps, N, 2, dtype=torch.float64, device=dev)
         self.seed = 0
         self.t = 0  # vector steps taken since the last reset; step k (0-based) is RNG step t = k + 1

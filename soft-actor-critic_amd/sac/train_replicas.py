@@ -17,10 +17,14 @@ aggregate as one JSON line.
         --env point_mass --num-envs 16 --env-steps 200000
 
 Without torchrun it runs one replica in-process.  ``--env`` names one of the
-probe envs of ``sac.envs`` or, when gymnasium is importable, any registered
-gymnasium id (the reference's own envs).
+probe envs of ``sac.envs``, ``pendulum`` (the swing-up of
+``sac.control_envs``) or, when gymnasium is importable, any registered
+gymnasium id (the reference's own envs).  The policy's output range is the
+config's ``policy_net.action_scale``, not the environment's: for ``pendulum``
+set it to 2.0 (its torque bound); at 1.0 the policy can use only half the
+torque.
 
-``--device-envs`` (probe envs only) keeps the environments on the device
+``--device-envs`` (the built-in envs only) keeps the environments on the device
 (``sac.device_envs.DeviceVectorEnv``) and trains through
 ``SAC.run_device_training_loop``: act -> step -> store is one launch per
 vector step, with no per-step host<->device traffic.  A config with
@@ -47,22 +51,25 @@ if __package__ in (None, ""):  # run as a script: make `sac` importable
 
 from sac.replicas import ReplicaAggregator, replica_seed  # noqa: E402
 
+# name -> (module of the sac package, class, constructor arguments): the environments with a device form
 PROBE_ENVS = {
-    "point_mass": ("OneDPointMassReachEnv", {}),
-    "constant_reward": ("ConstantRewardEnv", {}),
-    "quadratic_action": ("QuadraticActionRewardEnv", {}),
-    "random_obs_binary": ("RandomObsBinaryRewardEnv", {}),
+    "point_mass": ("envs", "OneDPointMassReachEnv", {}),
+    "constant_reward": ("envs", "ConstantRewardEnv", {}),
+    "quadratic_action": ("envs", "QuadraticActionRewardEnv", {}),
+    "random_obs_binary": ("envs", "RandomObsBinaryRewardEnv", {}),
+    "pendulum": ("control_envs", "PendulumEnv", {}),
 }
 
 
 def env_factory(name: str) -> Callable[[], object]:
-    """A zero-argument env constructor for ``name``: a probe env of sac.envs,
-    else a gymnasium id (gymnasium must be importable)."""
+    """A zero-argument env constructor for ``name``: a probe env of sac.envs or
+    the pendulum of sac.control_envs, else a gymnasium id (gymnasium must be
+    importable)."""
     if name in PROBE_ENVS:
-        from sac import envs
+        import importlib
 
-        cls, kw = PROBE_ENVS[name]
-        return lambda: getattr(envs, cls)(**kw)
+        mod, cls, kw = PROBE_ENVS[name]
+        return lambda: getattr(importlib.import_module("sac." + mod), cls)(**kw)
     try:
         import gymnasium as gym
     except ImportError as e:  # the probe envs need nothing
@@ -83,7 +90,7 @@ def train_replica(config: dict, make_env: Callable[[], object], num_envs: int, e
     "aggregate": the all-reduced METRICS summary}.  ``agent_cls`` /
     ``vec_env_cls`` default to sac.agent.SAC / sac.vector_env.SyncVectorEnv
     (tests pass host stubs).  ``device_envs``: ``make_env`` must build a probe
-    env of sac.envs; num_envs device copies of it (DeviceVectorEnv.from_env)
+    env of sac.envs or sac.control_envs.PendulumEnv; num_envs device copies of it (DeviceVectorEnv.from_env)
     train through ``run_device_training_loop`` (``graph_steps``: its argument)."""
     if agent_cls is None:
         from sac.agent import SAC as agent_cls  # noqa: N813
@@ -122,7 +129,8 @@ def train_replica(config: dict, make_env: Callable[[], object], num_envs: int, e
     return {"metrics": metrics, "aggregate": agg.finish()}
 
 
-def main(argv=None) -> int:
+def parse_args(argv=None) -> argparse.Namespace:
+    """The command line, with the combinations the device loop cannot run refused (SystemExit)."""
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--config", required=True, help="YAML config in the reference's format")
     ap.add_argument("--env", default="point_mass")
@@ -130,7 +138,8 @@ def main(argv=None) -> int:
     ap.add_argument("--env-steps", type=int, default=100_000)
     ap.add_argument("--aggregate-every", type=int, default=1000, help="gradient steps between all-reduces")
     ap.add_argument("--device-envs", action="store_true",
-                    help="keep the (probe) environments on the device: one fused act/step/store launch per vector step")
+                    help="keep the (built-in) environments on the device: one fused act/step/store launch per vector "
+                         "step")
     ap.add_argument("--graph-steps", type=int, default=0,
                     help="with --device-envs: vector steps per hipGraph replay of the loop (even, >= 2; 0 = stepwise)")
     a = ap.parse_args(argv)
@@ -138,6 +147,11 @@ def main(argv=None) -> int:
         raise SystemExit(f"--device-envs: {a.env!r} is not a probe env ({sorted(PROBE_ENVS)})")
     if a.graph_steps and not a.device_envs:
         raise SystemExit("--graph-steps needs --device-envs (the loop graph holds the device-resident loop)")
+    return a
+
+
+def main(argv=None) -> int:
+    a = parse_args(argv)
     import yaml
 
     with open(a.config) as f:

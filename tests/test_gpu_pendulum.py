@@ -1,0 +1,351 @@
+"""The device-resident pendulum swing-up on the MI355X: the step kernel against
+sac.control_envs.PendulumEnv, the fused rollout step against the step kernel
+and sac_policy_act, the loop graph against the stepwise loop, and -- the one
+test only a control task makes possible -- a training run whose evaluation
+return has to improve.
+
+Equality rules.  The device's float64 arithmetic is the host class's in the
+same order; only sin / cos come from another library.  Both are accurate to a
+few float64 ulps and the host instances take the device's state after every
+reset, so the error carried between resets stays near 1e-13: every fp32
+observation and fp32-rounded reward is within ONE fp32 ulp of the host's, at
+least 99 % of them identical; flags, counters and episode lengths are exact,
+episode returns within 1e-9.  Device against device (fused step against step
+kernel, graph against stepwise) is bit for bit."""
+import ctypes
+import math
+
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+DEV = "cuda"
+u64, i32, vp = ctypes.c_uint64, ctypes.c_int32, ctypes.c_void_p
+
+
+def _cfg(hidden=(40, 72), precision="fp32", capacity=1000, batch=32, warming=64, seed=3, action_scale=2.0,
+         log_episodes=False):
+    hidden = list(hidden)
+    return {
+        "sac": {"gamma": 0.99, "tau": 0.005, "alpha": 0.2, "auto_entropy_tuning": True, "actor_lr": 3e-4,
+                "critic_lr": 3e-4, "alpha_lr": 3e-4},
+        "q_net": {"hidden_sizes": hidden, "hidden_layers_act": "relu", "output_activation": "identity"},
+        "policy_net": {"hidden_sizes": hidden, "hidden_layers_act": "relu", "output_activation": "identity",
+                       "log_std_min": -20, "log_std_max": 2, "action_scale": action_scale},
+        "buffer": {"capacity": capacity},
+        "train": {"gradient_steps_per_update": 1, "update_frequency": 1, "seed": seed, "batch_size": batch,
+                  "warming_steps": warming, "device": "cuda", "precision": precision, "graph_chunk": 4},
+        "logger": {"enabled": False, "env_name": "pendulum", "agent_name": "SAC", "log_episode_stats": log_episodes,
+                   "log_q_values": False, "save_model": {"enabled": False, "path": None}},
+    }
+
+
+def bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def raw(t):
+    return t.detach().contiguous().view(torch.uint8).cpu()
+
+
+def within_one_ulp(dev, host, what):
+    """dev fp32 within one fp32 ulp of host fp32, elementwise; returns the number of non-identical elements."""
+    dev, host = np.asarray(dev, np.float32), np.asarray(host, np.float32)
+    err = np.abs(dev.astype(np.float64) - host.astype(np.float64))
+    ok = err <= np.spacing(np.abs(host)).astype(np.float64)
+    n_diff = int(np.sum(bits(dev) != bits(host)))
+    print(f"{what}: {n_diff} of {dev.size} not identical, max |err| {err.max():.3e}, beyond 1 ulp {int(np.sum(~ok))}")
+    assert np.all(ok), f"{what}: {int(np.sum(~ok))} of {dev.size} beyond 1 ulp (max |err| {err.max():.3e})"
+    return n_diff
+
+
+# ---------------------------------------------------------------- 6. step against the host class
+@pytest.mark.parametrize("N", [1, 17, 33])
+@pytest.mark.parametrize("max_steps,T", [(5, 12), (200, 205)])
+def test_step_matches_host_class(N, max_steps, T):
+    from sac.control_envs import PendulumEnv
+    from sac.device_envs import DeviceVectorEnv
+
+    seed = 11
+    dv = DeviceVectorEnv.from_env(PendulumEnv(max_steps=max_steps), N, device=DEV)
+    assert dv.obs_dim == 3 and dv.act_dim == 1 and tuple(dv.dstate.shape) == (3, N) and dv.kind_code == 8
+    hosts = [PendulumEnv(max_steps=max_steps) for _ in range(N)]
+    obs0, info = dv.reset(seed=seed)
+    assert info == {} and obs0.is_cuda and tuple(obs0.shape) == (N, 3)
+
+    def adopt(rows):  # the host instances take the device's reset draws (their own differ by design)
+        st = dv.dstate.cpu().numpy()
+        for i in rows:
+            hosts[i].reset()
+            hosts[i].state = [float(st[0, i]), float(st[2, i])]
+        return st
+
+    st = adopt(range(N))
+    assert np.all(st[0] >= -math.pi) and np.all(st[0] < math.pi) and np.all(np.abs(st[2]) <= 1.0)
+    if N > 1:
+        assert len(np.unique(st[0])) == N
+    cur = np.stack([h._obs() for h in hosts])
+    n_diff = within_one_ulp(obs0.cpu().numpy(), cur, "reset obs")
+    n_all = cur.size
+    rng = np.random.default_rng(100 + N + max_steps)
+    actions = rng.uniform(-3.0, 3.0, size=(T, N, 1)).astype(np.float32)  # a third of them beyond the torque bound
+    assert (np.abs(actions) > 2.0).any() and (np.abs(actions) < 2.0).any()
+    acts = torch.from_numpy(actions).to(DEV)
+    ep_ret, ep_len, cells = np.zeros(N), np.zeros(N, np.int64), []
+    for t in range(T):
+        o, r, te, tr, inf = dv.step(acts[t])
+        assert all(x.is_cuda for x in (o, r, te, tr, inf["final_obs"])) and te.dtype == torch.bool
+        o, r, te, tr, fin = (x.cpu().numpy() for x in (o, r, te, tr, inf["final_obs"]))
+        want = [h.step(actions[t, i]) for i, h in enumerate(hosts)]
+        w_fin = np.stack([w[0] for w in want])
+        w_rew = np.array([w[1] for w in want], np.float64)
+        w_trunc = np.array([w[3] for w in want], bool)
+        assert not te.any() and np.array_equal(tr, w_trunc), t
+        assert np.array_equal(tr, np.full(N, (t + 1) % max_steps == 0)), t
+        n_diff += within_one_ulp(fin, w_fin, f"step {t + 1} final_obs")
+        n_diff += within_one_ulp(r, w_rew.astype(np.float32), f"step {t + 1} reward")
+        n_all += fin.size + r.size
+        ep_ret += w_rew
+        ep_len += 1
+        cells.append((ep_ret.copy(), ep_len.copy(), w_trunc.copy()))
+        ep_ret[w_trunc], ep_len[w_trunc] = 0.0, 0
+        if w_trunc.any():
+            adopt(np.nonzero(w_trunc)[0])
+            w_cur = np.stack([h._obs() for h in hosts])
+            assert not np.array_equal(o, fin)  # a fresh draw, not the state stepped to
+        else:
+            w_cur = w_fin
+        n_diff += within_one_ulp(o, w_cur, f"step {t + 1} obs after autoreset")
+        n_all += o.size
+        counters = dv.counters.cpu().numpy()
+        assert np.array_equal(counters[0], [h.current_step for h in hosts]), t
+        assert np.array_equal(counters[1], ep_len), t
+    assert n_diff <= 0.01 * n_all, f"{n_diff} of {n_all} elements not identical to the host's"
+    # the episode ring: lengths and ended flags exact, returns within 1e-9
+    ring = dv.ring.cpu()
+    ints = ring[..., 1].contiguous().view(torch.int32).reshape(ring.shape[0], N, 2).numpy()
+    rets = ring[..., 0].numpy()
+    for t, (w_ret, w_len, w_end) in enumerate(cells, start=1):
+        c = t % dv.ring_steps
+        assert np.array_equal(ints[c, :, 0], w_len) and np.array_equal(ints[c, :, 1], w_end.astype(np.int32)), t
+        assert np.abs(rets[c] - w_ret).max() <= 1e-9, (t, np.abs(rets[c] - w_ret).max())
+    assert sum(int(c[2].sum()) for c in cells) == N * (T // max_steps) > 0
+
+
+# ---------------------------------------------------------------- 7. the fused rollout step
+@pytest.fixture(scope="module")
+def lib():
+    from sac import _engine as E
+
+    lb = E.load_library()
+    lb.sac_debug_rollout_eps_host.argtypes = [u64, u64, i32, i32, vp]
+    return lb
+
+
+def make_agent(N, max_steps=5, precision="fp32", layout="records", **cfg_kw):
+    from sac.agent import SAC
+    from sac.control_envs import PendulumEnv
+    from sac.device_envs import DeviceVectorEnv
+    from sac.replay_buffer import ReplayBuffer
+
+    cfg = _cfg(precision=precision, **cfg_kw)
+    dv = DeviceVectorEnv.from_env(PendulumEnv(max_steps=max_steps), N, device=DEV)
+    agent = SAC(dv, cfg)  # _set_seed resets the envs with train.seed
+    if layout != "records":
+        agent.replay_buffer = ReplayBuffer(cfg["buffer"]["capacity"], device=agent.device, layout=layout)
+    return agent, dv
+
+
+def twin_of(dv):
+    """Another DeviceVectorEnv in dv's state: stepping it with the stored actions is the step kernel's answer."""
+    from sac.device_envs import DeviceVectorEnv
+    from sac.control_envs import PendulumEnv
+
+    tw = DeviceVectorEnv.from_env(PendulumEnv(max_steps=dv.max_steps), dv.num_envs, device=DEV)
+    tw.seed, tw.t, tw._reset_done = dv.seed, dv.t, True
+    for name in ("obs", "counters", "dstate", "ring"):
+        getattr(tw, name).copy_(getattr(dv, name))
+    return tw
+
+
+@pytest.mark.parametrize("precision", ["fp32", "bf16"])
+@pytest.mark.parametrize("layout", ["records", "soa"])
+def test_fused_rollout_matches_step_kernel_and_policy_act(lib, layout, precision):
+    N, T, cap = 17, 7, 40  # the ring wraps on the third step, at a capacity that is no multiple of N
+    agent, dv = make_agent(N, max_steps=5, precision=precision, layout=layout, capacity=cap, batch=16)
+    eng, rb = agent.engine, agent.replay_buffer
+    assert float(eng.cfg.action_scale) == 2.0
+    rb._alloc(dv.obs_dim, dv.act_dim)
+    assert rb.layout == layout
+    torch.cuda.synchronize()
+    gen0 = int(rb.state.cpu()[2])
+    seed = int(eng.cfg.seed)
+    dones, all_acts = [], []
+    for t in range(1, T + 1):
+        tw = twin_of(dv)
+        before = dv.obs.clone()
+        slots = (torch.arange(N, device=DEV) + rb._pos) % cap
+        eng.rollout_step(dv, rb)
+        got = {k: getattr(rb, k)[slots].clone() for k in ("obs", "act", "rew", "next_obs", "done")}
+        # the stored action: policy_act on the observations the step saw with the step's Philox noise
+        eps = np.zeros((N, 1), np.float32)
+        assert lib.sac_debug_rollout_eps_host(seed, t, N, 1, eps.ctypes.data) == 0
+        want_act = eng.policy_act(before, torch.from_numpy(eps))
+        err = float((got["act"] - want_act).abs().max())
+        assert err <= 1e-6, (t, err)
+        # the stored transition: the step kernel's from the same state with those actions, bit for bit
+        o, r, te, tr, inf = tw.step(got["act"])
+        assert torch.equal(raw(got["obs"]), raw(before)), t
+        assert torch.equal(raw(got["next_obs"]), raw(inf["final_obs"])), t
+        assert torch.equal(raw(got["rew"]), raw(r)), t
+        assert torch.equal(got["done"], (te | tr).to(torch.float32)), t
+        for name in ("obs", "counters", "dstate", "ring"):
+            assert torch.equal(raw(getattr(dv, name)), raw(getattr(tw, name))), (t, name)
+        assert torch.equal(raw(o), raw(dv.obs))
+        dones.append(got["done"].cpu().numpy())
+        all_acts.append(got["act"].cpu().numpy())
+    dones = np.stack(dones)
+    assert np.array_equal(dones, np.repeat((np.arange(1, T + 1) % 5 == 0)[:, None], N, 1).astype(np.float32))
+    acts = np.stack(all_acts)
+    assert len(np.unique(acts)) > N and np.abs(acts).max() > 1.0 and np.abs(acts).max() <= 2.0  # action_scale 2
+    obs = rb.obs.cpu().numpy()
+    assert np.allclose(obs[:, 0] ** 2 + obs[:, 1] ** 2, 1.0, atol=1e-6) and np.abs(obs[:, 2]).max() <= 8.0
+    assert rb.state.cpu().tolist() == [cap, (T * N) % cap, gen0 + T] and (rb._size, rb._pos) == (cap, (T * N) % cap)
+
+    # store = 0 (evaluation): the environments step, the replay and its generation stay
+    storage0, state0 = raw(rb.storage), rb.state.cpu().tolist()
+    tw = twin_of(dv)
+    before = dv.obs.clone()
+    eng.rollout_step(dv, rb, deterministic=True, store=False)
+    torch.cuda.synchronize()
+    assert torch.equal(storage0, raw(rb.storage)) and rb.state.cpu().tolist() == state0
+    assert (rb._size, rb._pos) == (cap, (T * N) % cap)
+    tw.step(eng.policy_act(before))
+    for name in ("obs", "counters", "dstate"):
+        assert torch.equal(raw(getattr(dv, name)), raw(getattr(tw, name))), name
+    assert dv.t == T + 1
+
+
+# ---------------------------------------------------------------- 8. device cursor and graph
+class Logger:
+    def __init__(self):
+        self.episodes, self.hparams = [], []
+
+    def log_episode_metrics(self, episode_idx, reward, length):
+        self.episodes.append((episode_idx, reward, length))
+
+    def log_hparams(self, cfg, metrics):
+        self.hparams.append(dict(metrics))
+
+
+def test_training_loop_with_graph_steps_matches_stepwise():
+    N, warming = 17, 64
+    total = 4 * N + 40 * N + 5  # the warm-up ends with the fourth vector step; 40 whole steps and a ragged one follow
+    runs = []
+    for graph_steps in (0, 4):
+        agent, dv = make_agent(N, max_steps=5, capacity=300, batch=32, warming=warming, log_episodes=True)
+        logger = Logger()
+        calls = []
+        orig = agent.engine.loop_graph
+        agent.engine.loop_graph = lambda *a, **k: (calls.append(1), orig(*a, **k))[1]
+        m = agent.run_device_training_loop(total, logger=logger, graph_steps=graph_steps, drain_every=8)
+        torch.cuda.synchronize()
+        agent.engine.check()
+        state = dict(agent.engine.state_tensors(), storage=agent.replay_buffer.storage,
+                     replay_state=agent.replay_buffer.state, env_obs=dv.obs, env_counters=dv.counters,
+                     env_dstate=dv.dstate, env_ring=dv.ring)
+        runs.append(dict(metrics=m, episodes=logger.episodes, state={k: raw(v) for k, v in state.items()},
+                         graphs=len(calls)))
+    a, b = runs
+    assert a["graphs"] == 0 and b["graphs"] >= 8  # resets (every fifth step) fall inside blocks of four
+    assert a["metrics"] == b["metrics"] and a["metrics"]["total_env_steps"] == 45 * N
+    assert a["metrics"]["gradient_steps"] == 45 * N - (warming - 1) and a["metrics"]["total_episodes"] == 9 * N
+    assert a["episodes"] == b["episodes"] and len(a["episodes"]) == 9 * N
+    assert all(length == 5 and -5 * 16.27 <= ret < 0.0 for _, ret, length in a["episodes"])
+    bad = [k for k in a["state"] if not torch.equal(a["state"][k], b["state"][k])]
+    assert not bad, f"graph_steps = 4 against stepwise: {bad} differ"
+    assert a["state"].keys() >= {"param/pi", "param/q1", "storage", "env_dstate"}
+
+
+# ---------------------------------------------------------------- 9. learning
+# 16 environments, one gradient step per environment step, 20,000 gradient steps after a warm-up of 1,000
+# transitions, blocks of 8 vector steps from the loop graph; evaluation: 16 deterministic episodes of 200 steps.
+LEARNING = dict(num_envs=16, hidden=[256, 256], precision="fp32", action_scale=2.0, batch=256, capacity=100_000,
+                warming=1000, gradient_steps=20_000, graph_steps=8, eval_episodes=16)
+
+
+def learning_run(seed, curve=False):
+    import time
+
+    from sac.agent import SAC
+    from sac.device_envs import DeviceVectorEnv
+
+    c = LEARNING
+    t0 = time.perf_counter()
+    dv = DeviceVectorEnv("pendulum", c["num_envs"], device=DEV)
+    agent = SAC(dv, _cfg(hidden=c["hidden"], precision=c["precision"], capacity=c["capacity"], batch=c["batch"],
+                         warming=c["warming"], seed=seed, action_scale=c["action_scale"]))
+    untrained = agent.evaluate_device(c["eval_episodes"], dv)
+    points = []
+    cb = (lambda m: points.append((m["env_steps"], round(m["avg_return"], 1)))) if curve else None
+    t1 = time.perf_counter()
+    # whole vector steps; the first update is at the warming-th transition: at most c["gradient_steps"] of them
+    vec_steps = (c["gradient_steps"] + c["warming"] - 1) // c["num_envs"]
+    m = agent.run_device_training_loop(vec_steps * c["num_envs"], seed=seed, graph_steps=c["graph_steps"], callback=cb)
+    assert 0.99 * c["gradient_steps"] <= m["gradient_steps"] <= c["gradient_steps"]
+    torch.cuda.synchronize()
+    t2 = time.perf_counter()
+    trained = agent.evaluate_device(c["eval_episodes"], dv)
+    agent.engine.close()
+    return dict(untrained=untrained, trained=trained, gradient_steps=m["gradient_steps"],
+                env_steps=m["total_env_steps"], episodes=m["total_episodes"], train_s=t2 - t1,
+                total_s=time.perf_counter() - t0, curve=points[::16])
+
+
+# profiles/pendulum_learning.txt: seeds 0, 1, 2 of this configuration, measured once: untrained -1256.60,
+# -1560.17, -1301.10; trained -133.27, -143.84, -148.92 (a return lies in [-3255, 0]).  The bar is halfway
+# between the best untrained (-1256.60) and the worst trained (-148.92) of them, which lie 1107.68 apart.
+LEARNING_BAR = -702.76
+
+
+def test_training_improves_the_evaluation_return():
+    """The engine learns, end to end: about 20,000 gradient steps of the device loop on the pendulum (a second
+    of GPU time) lift the deterministic policy's mean return over 16 episodes from the untrained side of the
+    bar to the trained side.  Drift between packed and master weights, a wrong Polyak or temperature update
+    or a stale staged batch leave every few-step parity test passing and this one failing."""
+    r = learning_run(seed=0)
+    print(f"untrained {r['untrained']:.2f} trained {r['trained']:.2f} bar {LEARNING_BAR} "
+          f"gradient_steps {r['gradient_steps']} train_wall_s {r['train_s']:.2f}")
+    assert r["episodes"] == 6 * LEARNING["num_envs"] and r["env_steps"] == 1312 * LEARNING["num_envs"]
+    assert -3255.0 <= r["untrained"] < LEARNING_BAR, r
+    assert LEARNING_BAR < r["trained"] <= 0.0, r
+
+
+# ---------------------------------------------------------------- 10. replica training
+@pytest.mark.parametrize("device_envs,graph_steps", [(True, 0), (True, 4), (False, 0)])
+def test_train_replica_on_pendulum(device_envs, graph_steps):
+    """sac/train_replicas.py --env pendulum, with and without --device-envs: one rank over RCCL."""
+    import socket
+
+    import torch.distributed as dist
+
+    from sac.train_replicas import env_factory, train_replica
+
+    with socket.socket() as s:
+        s.bind(("127.0.0.1", 0))
+        port = s.getsockname()[1]
+    cfg = _cfg(hidden=(32, 32), batch=16, warming=24, capacity=4096, seed=5)
+    torch.cuda.set_device(0)
+    dist.init_process_group("nccl", init_method=f"tcp://127.0.0.1:{port}", rank=0, world_size=1)
+    try:
+        out = train_replica(cfg, env_factory("pendulum"), num_envs=4, env_steps=1000, every=64, rank=0,
+                            device="cuda:0", device_envs=device_envs, graph_steps=graph_steps)
+    finally:
+        dist.destroy_process_group()
+    m, agg = out["metrics"], out["aggregate"]
+    # 250 vector steps of 4 environments with episodes of 200 steps: one finished per environment
+    assert m["total_env_steps"] == 1000 and m["total_episodes"] == 4
+    assert m["gradient_steps"] == 1000 - 23 and -3255.0 <= m["final_avg_return"] < 0.0
+    assert agg["world"] == 1 and agg["aggregations"] >= 1
