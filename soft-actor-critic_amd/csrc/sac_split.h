@@ -231,9 +231,14 @@ __device__ __forceinline__ void ks_issue(KsHeld<T, MC>& kh, const GemmW& w) {
   });
 }
 
-template <typename T, bool COH = false, int MC = 1>
-__device__ __forceinline__ void gemm_ksplit(const lf* __restrict__ A, int lda, const GemmW& w, lf* red, lf* out,
-                                            int ldo, const KsHeld<T, MC>* kh = nullptr) {
+// Epilogue form: after the ONE barrier behind the per-wave partials, the thread
+// that sums element (r, col) hands the sum to epi(r, col, s) -- a publish from
+// the reducer instead of an LDS write, a second barrier and a re-read.  No
+// barrier follows: the caller adds one before anything reads what epi wrote to
+// LDS, and before red is written again.
+template <typename T, bool COH = false, int MC = 1, typename Epi>
+__device__ __forceinline__ void gemm_ksplit_epi(const lf* __restrict__ A, int lda, const GemmW& w, lf* red,
+                                                const KsHeld<T, MC>* kh, Epi&& epi) {
   typedef typename MM<T>::Frag F;
   constexpr int KC = MM<T>::KC, KL = MM<T>::KL;
   constexpr uint32_t FSB = 64 * KL * sizeof(T);
@@ -275,8 +280,13 @@ __device__ __forceinline__ void gemm_ksplit(const lf* __restrict__ A, int lda, c
     const int tt = i / 256, e = i % 256, r = e / 16, cc = e % 16;
     float s = 0.f;
     for (int q = 0; q < wpt; ++q) s += red[(q * NT + tt) * 256 + e];
-    out[r * ldo + tt * 16 + cc] = s;
+    epi(r, tt * 16 + cc, s);
   }
+}
+template <typename T, bool COH = false, int MC = 1>
+__device__ __forceinline__ void gemm_ksplit(const lf* __restrict__ A, int lda, const GemmW& w, lf* red, lf* out,
+                                            int ldo, const KsHeld<T, MC>* kh = nullptr) {
+  gemm_ksplit_epi<T, COH, MC>(A, lda, w, red, kh, [&](int r, int col, float s) { out[r * ldo + col] = s; });
   __syncthreads();
 }
 
@@ -301,6 +311,16 @@ __device__ __forceinline__ void gemm_ksplit(const lf* __restrict__ A, int lda, c
 // s / a~ go global -> register -> X with one barrier (+1.0%), and pi computes
 // every head-backward term that does not need the critics' da before it polls
 // for them (+1.0%).
+// Chain trims (profiles/ab_chain_trims_items.txt; none moves a float
+// operation, the bits are the parent's).  Kept on their own A/B: the critics'
+// unit seed U1 = act'(P1) W2 written by layer 1's epilogue in phase A (+1.0%)
+// and phase C (+0.5%) for ReLU / identity (the loop over P1 and its barrier
+// go; other activations keep the loop).  Kept as a group (+0.35..0.7% together,
+// each alone within noise): phase A's staged record -> registers -> X for
+// every role; k-split steps that publish from the threads that sum the
+// partials (gemm_ksplit_epi: pi(s')'s layer 2, every partial q of phase A,
+// phase C's dX0 of the action columns); pi's d(-min Q)/d a~ kept in its lane
+// (R A <= 64); pi's layer-2 dX over the chunks of dOut that hold data.
 
 // p[i]: the lane's value for its row i (i < 4) -- a gemm_hs epilogue's lane
 // (c = lane & 15, g = lane >> 4) holds rows 4 g + i of column c.  Returns the
@@ -410,11 +430,17 @@ __device__ __forceinline__ void target_critic_split_body(const EngineDev* __rest
   const int64_t rb_size = GPC(int64_t, rb.state)[0], rb_pos = GPC(int64_t, rb.state)[1];
   bool staged = false;
   bool h1_issued = false;
+  // x_direct: the staged record's registers were written straight into Xb (and
+  // the record turned out to be this step's); sreg: the thread's elements of s
+  constexpr int NS = (R * 32 + SAC_THREADS - 1) / SAC_THREADS;
+  bool x_direct = false;
+  float sreg[NS];
+#pragma unroll
+  for (int u = 0; u < NS; ++u) sreg[u] = 0.f;
   if (E.stage && !inj_idx) {
     const AS_G float* rec = GPC(float, E.stg) + stage_rec(E, step, rbi);
     const AS_C uint64_t* hdr = (const AS_C uint64_t*)rec;
     const AS_G float* p = rec + 16;
-    constexpr int NS = (R * 32 + SAC_THREADS - 1) / SAC_THREADS;
     if (O <= 32) {  // uniform: record -> registers, layer-1 weights issued behind it, -> LDS
       float rs[2][NS], ra[NS], rr = 0.f, rd = 0.f;
 #pragma unroll
@@ -430,14 +456,31 @@ __device__ __forceinline__ void target_critic_split_body(const EngineDev* __rest
       }
       ht_issue<T, 1, NCH_H>(h1, w1);
       h1_issued = true;
+      if (L0.Kp <= 64) {  // uniform: the record goes straight into layer 0's input
+        // X = [s' | 0] for pi(s') and the target critics (a~' comes after the head),
+        // [s | a] for the critics, [s | 0] for pi(s); pad columns zeroed by the
+        // same loop's spare iterations.  Nothing else reads s / s' / a from LDS.
+        const bool crit = role == 3 || role == 4;
+        const int used = crit ? O + A : O, npad = L0.Kp - used;
 #pragma unroll
-      for (int u = 0; u < NS; ++u) {
-        const int i = tid + u * SAC_THREADS;
-        if (i < R * O) {
-          sB[i] = rs[0][u];
-          s2B[i] = rs[1][u];
+        for (int u = 0; u < NS; ++u) {
+          const int i = tid + u * SAC_THREADS;
+          if (i < R * O) Xb[(i / O) * ld + i % O] = role >= 3 ? rs[0][u] : rs[1][u];
+          if (crit && i < R * A) Xb[(i / A) * ld + O + i % A] = ra[u];
+          sreg[u] = rs[0][u];
         }
-        if (i < R * A) aB[i] = ra[u];
+        for (int i = tid; i < R * npad; i += SAC_THREADS) Xb[(i / npad) * ld + used + i % npad] = 0.f;
+        x_direct = true;
+      } else {
+#pragma unroll
+        for (int u = 0; u < NS; ++u) {
+          const int i = tid + u * SAC_THREADS;
+          if (i < R * O) {
+            sB[i] = rs[0][u];
+            s2B[i] = rs[1][u];
+          }
+          if (i < R * A) aB[i] = ra[u];
+        }
       }
       if (tid < R) {
         rB[tid] = rr;
@@ -458,6 +501,7 @@ __device__ __forceinline__ void target_critic_split_body(const EngineDev* __rest
     staged = hdr[0] == step && hdr[1] == (uint64_t)rb_size && hdr[2] == (uint64_t)rb_pos &&
              hdr[3] == (uint64_t)(uintptr_t)rb.obs && hdr[4] == (uint64_t)GPC(int64_t, rb.state)[2];
   }
+  x_direct = x_direct && staged;  // a stale record: the gather and build_x below overwrite Xb
   if (!h1_issued) ht_issue<T, 1, NCH_H>(h1, w1);
   // layer 2's k-split slice (layer 2 runs after the hand-off for the target
   // critics, and at the end of pi(s')'s chain): held from here
@@ -573,6 +617,16 @@ __device__ __forceinline__ void target_critic_split_body(const EngineDev* __rest
 
   // ---- layer 0 (full) and layer 1 (this half) forward: H0, H1 in LDS; P0 / P1 kept
   auto no_hook = [] {};
+  // layer 2's reduction epilogue (gemm_ksplit_epi).  l2_pub 0: the partial goes
+  // to outB; 1: pi(s')'s R x 2A partial is published by the threads that sum it;
+  // 2: the partial q (column 0) is published the same way, and kept in outB
+  // only where someone reads it (l2_keep).  mk_u1: the critics' unit seed U1 is
+  // written by layer 1's epilogue (w2l: W2's element of the lane's column).
+  int l2_pub = 0;
+  bool l2_keep = false;
+  AS_G uint64_t* l2_g = nullptr;
+  bool mk_u1 = false;
+  float w2l = 0.f;
   auto forward01 = [&](bool keepP, bool stXT, bool pi_actor, auto&& after_l1, bool l0_done = false) {
     // layer 0: X [R][Kp0] -> P0 / H0 [R][H] (l0_done: the caller computed H0)
     const int act = net.hid_act;
@@ -608,7 +662,10 @@ __device__ __forceinline__ void target_critic_split_body(const EngineDev* __rest
       for (int i = 0; i < 4; ++i) {
         const int r = (((threadIdx.x & 63) >> 4) << 2) + i;
         const float p = acc[i] + bn;
-        if (keepP) P1[r * ldp1 + col] = p;
+        if (mk_u1)
+          U1[r * ldu1 + col] = act == ACT_RELU ? (p > 0.f ? w2l : 0.f) : w2l;
+        else if (keepP)
+          P1[r * ldp1 + col] = p;
         H1[r * ldh1 + col] = act == ACT_RELU ? (p > 0.f ? p : 0.f) : p;
       }
     });
@@ -624,7 +681,17 @@ __device__ __forceinline__ void target_critic_split_body(const EngineDev* __rest
                        nvalid, nullptr);
     STAMP(3);
     // layer 2, this half's partial sum: outB [R][Np2]
-    gemm_ksplit<T, false, decltype(kh2)::MAXC>(H1, ldh1, w2n, red, outB, ldo, &kh2);
+    gemm_ksplit_epi<T, false, decltype(kh2)::MAXC>(H1, ldh1, w2n, red, &kh2, [&](int r, int col, float s) {
+      if (l2_pub == 0) {
+        outB[r * ldo + col] = s;
+      } else if (l2_pub == 1) {
+        if (col < 2 * A) gran_put(l2_g + r * 2 * A + col, s, ep);
+      } else if (col == 0) {
+        gran_put(l2_g + r, s, ep);
+        if (l2_keep) outB[r * ldo] = s;
+      }
+    });
+    if (l2_pub == 0 || l2_keep) __syncthreads();  // uniform
     STAMP(4);
   };
 
@@ -642,16 +709,23 @@ __device__ __forceinline__ void target_critic_split_body(const EngineDev* __rest
   const float alpha32 = (float)*GPC(double, E.alpha_state + 1);
   if (role == 0) {
     // ---- pi(s'): the critical path's head
-    build_x(s2B, aB, 0);
+    if (!x_direct) build_x(s2B, aB, 0);
+    l2_pub = 1;
+    l2_g = gs_at(E, GS_PI, rbi, h);
     forward01(false, false, false, no_hook);
-    AS_G uint64_t* g = gs_at(E, GS_PI, rbi, h);
-    for (int i = tid; i < R * 2 * A; i += SAC_THREADS) gran_put(g + i, outB[(i / (2 * A)) * ldo + i % (2 * A)], ep);
     STAMP(6);
   } else if (role == 5) {
     // ---- pi(s): the actor sample for phase C (stashes), X^T of pi's layers
-    if (h == 0)
-      for (int i = tid; i < R * O; i += SAC_THREADS) st_f<false>(E.s_st + (size_t)r0 * O + i, sB[i]);
-    build_x(sB, aB, 0);
+    if (h == 0) {
+      if (x_direct) {
+#pragma unroll
+        for (int u = 0; u < NS; ++u)
+          if (tid + u * SAC_THREADS < R * O) st_f<false>(E.s_st + (size_t)r0 * O + tid + u * SAC_THREADS, sreg[u]);
+      } else {
+        for (int i = tid; i < R * O; i += SAC_THREADS) st_f<false>(E.s_st + (size_t)r0 * O + i, sB[i]);
+      }
+    }
+    if (!x_direct) build_x(sB, aB, 0);
     // layer-0 input X^T: both halves store it (columns h Bp + r0: the partial dW layout)
     store_T<T, R>(Xb, ld, L0.Kp, L0.K, (T*)L0.XT + par * L0.xt_par, 2 * Bp, h * Bp + r0, nvalid, nullptr);
     forward01(true, true, true, no_hook);
@@ -667,6 +741,9 @@ __device__ __forceinline__ void target_critic_split_body(const EngineDev* __rest
   } else if (role == 1 || role == 2) {
     // ---- target critic t (agent.py:195-211): a~', log pi' from pi(s')'s two partials
     const int t = role - 1;
+    l2_pub = 2;
+    l2_keep = t == 0 && h == 0;  // this half reads its own partial for y
+    l2_g = gs_at(E, t ? GS_QT2 : GS_QT1, rbi, h);
     if (sizeof(T) == 4) ks_issue<T, KsHeld<T>::MAXC, false>(kh2, w2n);
     // Layer 0 over the s' columns runs BEFORE the pi(s') hand-off (round 5,
     // VERDICT r04 item 2c): only the chunks holding a~' columns are left for
@@ -678,7 +755,7 @@ __device__ __forceinline__ void target_critic_split_body(const EngineDev* __rest
     const int Kp0 = L0.Kp, nch0 = Kp0 / KC;
     const bool early0 = nch0 <= HC0;  // every layer-0 chunk held (C2, C4): else the plain path
     if (early0) {
-      build_x(s2B, a2B, 0);  // [s', 0]
+      if (!x_direct) build_x(s2B, a2B, 0);  // [s', 0]
       const int cs = O / KC, cb = (O + KC - 1) / KC;  // s'-only chunks; chunks with any s' column
       const int lane = tid & 63, wave = wave_id(), c = lane & 15, g = lane >> 4;
       const lf* arow = Xb + c * ld + g * MM<T>::KL;
@@ -735,7 +812,6 @@ __device__ __forceinline__ void target_critic_split_body(const EngineDev* __rest
       build_x(s2B, a2B, A);
       forward01(false, false, false, no_hook);
     }
-    if (tid < R) gran_put(gs_at(E, t ? GS_QT2 : GS_QT1, rbi, h) + tid, outB[tid * ldo], ep);
     STAMP(9);
     if (t == 0 && h == 0 && tid < 64) {
       // this half (Qt1, half 0) computes the row tile's targets y and both
@@ -791,22 +867,29 @@ __device__ __forceinline__ void target_critic_split_body(const EngineDev* __rest
     // W2's element for this thread's column n = tid % HH
     if constexpr (sizeof(T) == 2) ht_issue<T, 2, NCH_HH, false>(ht1, wt1);
     static_assert(SAC_THREADS % SPLIT_HH == 0, "one W2 column per thread in the unit-seed loop");
-    const float w2n = ldf<false>(net.P + L2.w_off + h * HH + tid % HH);  // W2 [1][H] fp32 master
-    build_x(sB, aB, A);
+    const bool relu_id = net.hid_act == ACT_RELU || net.hid_act == ACT_ID;
+    mk_u1 = relu_id;
+    // W2 [1][H] fp32 master: the element of layer 1's epilogue column, or of the loop's
+    const float w2n = mk_u1 ? 0.f : ldf<false>(net.P + L2.w_off + h * HH + tid % HH);
+    if (mk_u1) w2l = ldf<false>(net.P + L2.w_off + h * HH + wave_id() * 16 + (tid & 15));
+    l2_pub = 2;
+    l2_g = gs_at(E, qi ? GS_QA2 : GS_QA1, rbi, h);
+    if (!x_direct) build_x(sB, aB, A);
     // layer-0 input X^T is shared by Q1 and Q2: Q1's halves store it (columns h Bp + r0)
     if (qi == 0) store_T<T, R>(Xb, ld, L0.Kp, L0.K, L0.XT, 2 * Bp, h * Bp + r0, nvalid, nullptr);
     forward01(true, true, false, [&] {
       if constexpr (sizeof(T) == 4) ht_issue<T, 2, NCH_HH, false>(ht1, wt1);
     });
-    if (tid < R) gran_put(gs_at(E, qi ? GS_QA2 : GS_QA1, rbi, h) + tid, outB[tid * ldo], ep);
     // unit-seed backward (every layer's dY is linear in the row's seed 2(q - y)/B):
     // U1[r][n] = act'(P1[r][n]) * W2[0][h HH + n];  U0p = act'(P0) * (U1 W1[half])
     {
-      for (int i = tid; i < R * HH; i += SAC_THREADS) {
-        const int r = i / HH, n = i % HH;  // n == tid % HH
-        U1[r * ldu1 + n] = act_bwd(net.hid_act, P1[r * ldp1 + n], w2n);
+      if (!mk_u1) {  // uniform
+        for (int i = tid; i < R * HH; i += SAC_THREADS) {
+          const int r = i / HH, n = i % HH;  // n == tid % HH
+          U1[r * ldu1 + n] = act_bwd(net.hid_act, P1[r * ldp1 + n], w2n);
+        }
+        __syncthreads();
       }
-      __syncthreads();
       gemm_hs<T, 2, NCH_HH, false>(U1, ldu1, wt1, &ht1, [&](int j, int col, const f32x4& acc) {
         const bool kv = col < L1.K;
 #pragma unroll
@@ -957,12 +1040,14 @@ __device__ __forceinline__ void actor_split_body(const EngineDev* __restrict__ E
     kc2.ok = kc0.ok = false;
     // the W2 (fp32 master) element of this thread's column n = tid % HQ of the unit-seed backward
     static_assert(SAC_THREADS % HQ == 0, "one W2 column per thread in the unit-seed loop");
-    const float w2n = GPC(float, net.P + L2.w_off)[h * HQ + tid % HQ];
     const int act = net.hid_act;
     const int Kp0 = L0.Kp;
     // fp32, N = 1: layer 2 (the partial q) fused into layer 1's epilogue, see rows16_sum
     const bool relu_id = act == ACT_RELU || act == ACT_ID;
     const bool fuse2 = sizeof(T) == 4 && L2.N == 1 && relu_id;
+    // ReLU / identity: the unit seed U1 = act'(P1) * W2 is written by layer 1's epilogue
+    const bool mk_u1 = relu_id;
+    const float w2n = mk_u1 ? 0.f : GPC(float, net.P + L2.w_off)[h * HQ + tid % HQ];
     const int lane = tid & 63, wv = wave_id();
     float w2l = 0.f;
     // one thread per element of X when it fits: s / a~ go global -> register -> X, one barrier
@@ -977,7 +1062,7 @@ __device__ __forceinline__ void actor_split_body(const EngineDev* __restrict__ E
       for (int i = tid; i < R * A; i += SAC_THREADS) aB[i] = GPC(float, E.a_st)[(size_t)r0 * A + i];
     }
     // behind the inputs: waiting for s / a~ must not wait for these (loads retire in order)
-    if (fuse2) w2l = GPC(float, net.P + L2.w_off)[h * HQ + (wv < w1.NT ? wv : 0) * 16 + (lane & 15)];
+    if (fuse2 || mk_u1) w2l = GPC(float, net.P + L2.w_off)[h * HQ + (wv < w1.NT ? wv : 0) * 16 + (lane & 15)];
     if (!fuse2) ks_issue<T, decltype(kc2)::MAXC>(kc2, w2);
     if (sizeof(T) == 2) ks_issue<T, decltype(kc0)::MAXC>(kc0, wt0);  // fp32: after layer 1 (its held W1 part is dead then; from here it spilled)
     if (x_direct) {
@@ -1012,7 +1097,10 @@ __device__ __forceinline__ void actor_split_body(const EngineDev* __restrict__ E
         const int r = (((threadIdx.x & 63) >> 4) << 2) + i;
         const float p = acc[i] + bn;
         const float hv = act == ACT_RELU ? (p > 0.f ? p : 0.f) : p;
-        P1[r * ldp1 + col] = p;
+        if (mk_u1)
+          U1[r * ldu1 + col] = act == ACT_RELU ? (p > 0.f ? w2l : 0.f) : w2l;
+        else
+          P1[r * ldp1 + col] = p;
         if (!fuse2) H1[r * ldh1 + col] = hv;
         q2[i] = hv * w2l;
       }
@@ -1036,11 +1124,13 @@ __device__ __forceinline__ void actor_split_body(const EngineDev* __restrict__ E
     STAMP(36 + qi);
     // unit-seed backward down to a~ (the pi role applies the min-Q weights and act'(q))
     {
-      for (int i = tid; i < R * HQ; i += SAC_THREADS) {
-        const int r = i / HQ, n = i % HQ;  // n == tid % HQ
-        U1[r * ldu1 + n] = act_bwd(act, P1[r * ldp1 + n], w2n);
+      if (!mk_u1) {  // uniform
+        for (int i = tid; i < R * HQ; i += SAC_THREADS) {
+          const int r = i / HQ, n = i % HQ;  // n == tid % HQ
+          U1[r * ldu1 + n] = act_bwd(act, P1[r * ldp1 + n], w2n);
+        }
+        __syncthreads();
       }
-      __syncthreads();
       gemm_hs<T, 2, NCH_HQ, false>(U1, ldu1, wt1, &ht1, [&](int j, int col, const f32x4& acc) {
         const bool kv = col < L1.K;
 #pragma unroll
@@ -1054,9 +1144,12 @@ __device__ __forceinline__ void actor_split_body(const EngineDev* __restrict__ E
       if (act != ACT_RELU && act != ACT_ID) act_pass_bwd<R>(Xb, ld, P0, ldp0, L1.Kp >> 4, L1.K, act);
       __syncthreads();
       // dX of layer 0 for the action columns: the 16-row tiles of W0^T holding [O, O + A)
-      gemm_ksplit<T, false, decltype(kc0)::MAXC>(Xb, ld, wt0, red, H0, ld, &kc0);  // H0 [R][k1 - k0]: partial dX0
       AS_G uint64_t* g = gs_at(E, GS_C1 + qi, rbi, h);
-      for (int i = tid; i < R * A; i += SAC_THREADS) gran_put(g + i, H0[(i / A) * ld + (O - k0) + i % A], ep);
+      // the partial dX0 [R][k1 - k0]: its action columns published by the threads that sum them
+      gemm_ksplit_epi<T, false, decltype(kc0)::MAXC>(Xb, ld, wt0, red, &kc0, [&](int r, int col, float s) {
+        const int j = col - (O - k0);
+        if (j >= 0 && j < A) gran_put(g + r * A + j, s, ep);
+      });
       if (tid < R) gran_put(g + R * A + tid, outB[tid * ldo], ep);
     }
     STAMP(38 + qi);
@@ -1070,7 +1163,9 @@ __device__ __forceinline__ void actor_split_body(const EngineDev* __restrict__ E
   const AS_C LayerDev& L2 = pi.l[2];
   // operands: layer 2's dX (rows = this half's n, reduction over 2A -> 32),
   // layer 1's dX (rows k all, reduction over this half's n), both held
-  const GemmW wt2 = gw_sub<T>(L2.WTc, L2.Np, h * HH, HH, 0, L2.Np, nullptr, 0);
+  // layer 2's dX multiplies only the chunks of dOut that hold its 2A columns
+  const int np2 = (2 * A + KC - 1) / KC * KC;
+  const GemmW wt2 = gw_sub<T>(L2.WTc, L2.Np, h * HH, HH, 0, np2, nullptr, 0);
   const GemmW wt1 = gw_sub<T>(L1.WTc, L1.Np, 0, L1.Kp, h * HH, HH, nullptr, 0);
   HTiles<T, 1, NCH_32> ht2;
   HTiles<T, 2, NCH_HH> ht1;
@@ -1131,7 +1226,7 @@ __device__ __forceinline__ void actor_split_body(const EngineDev* __restrict__ E
     hb_gdiff = 2.f * diff * g_sq;
     hb_sd = sd;
   }
-  const int pad = L2.Np - 2 * A;  // dOut's padding columns
+  const int pad = np2 - 2 * A;  // dOut's padding columns that are multiplied
   for (int i = tid; i < R * pad; i += SAC_THREADS) goutB[(i / pad) * ldo + 2 * A + i % pad] = 0.f;
   __syncthreads();
   STAMP(34);
@@ -1139,6 +1234,7 @@ __device__ __forceinline__ void actor_split_body(const EngineDev* __restrict__ E
   // the critics' parts, summed in part order by every consumer
   const AS_G uint64_t* c1p[WQ];
   const AS_G uint64_t* c2p[WQ];
+  float ga = 0.f;  // R A <= 64: this thread's d(-min Q) / d a~ of its (row, action dim)
 #pragma unroll
   for (int p = 0; p < WQ; ++p) {
     c1p[p] = gs_at(E, GS_C1, rbi, p);
@@ -1196,10 +1292,9 @@ __device__ __forceinline__ void actor_split_body(const EngineDev* __restrict__ E
           da1 += gv[p];
           da2 += gv[WQ + p];
         }
-        gaB[i] = w1r * da1 + w2r * da2;
+        ga = w1r * da1 + w2r * da2;  // lane (r, j) runs the head backward of (r, j) itself
       }
     }
-    __syncthreads();
   } else {
   if (tid < 64) {
     float term = 0.f;
@@ -1267,7 +1362,8 @@ __device__ __forceinline__ void actor_split_body(const EngineDev* __restrict__ E
     const bool v = r < nvalid;
     const float lo = E.ls_min, hi = E.ls_max, scale = E.scale;
     const float lsr = hsv[1], e = hsv[3];
-    float g_z = (gaB[r * A + j] * scale) * hb_omt;
+    const float gav = R * A <= 64 ? ga : gaB[r * A + j];
+    float g_z = (gav * scale) * hb_omt;
     g_z = g_z + hb_sp;
     g_z = g_z + hb_gdiff;
     const float g_mu = -hb_gdiff + g_z;
