@@ -790,6 +790,15 @@ __device__ __forceinline__ float adam_elem(float& p, float& m, float& v, float g
 // upd_slots x [256] f32 seeds (>= the alpha block's 5 x 1024 floats)
 #define SAC_UPD_SLOT_BYTES (64 * 528)
 #define SAC_UPD_LDS_FOR(slots) ((slots) * SAC_UPD_SLOT_BYTES + 2 * 32 * 33 * 4 + 32 * 17 * 4 + (slots) * 256 * 4)
+// static LDS of the 1024-thread update kernels, on top of the dynamic block: the
+// four K-quarter partials [4][32][33] f32 of a single-round tile (16.5 KB; with
+// two slots 95 KB per workgroup, one workgroup per CU as before).  One array
+// for every instance of the tile in a kernel (not a template).
+#define SAC_UPD_PART_BYTES (4 * 32 * 33 * 4)
+__device__ __forceinline__ lf* upd_partials() {
+  __shared__ float part[SAC_UPD_PART_BYTES / 4];
+  return (lf*)part;
+}
 template <typename T, int UT, int GS = 1, int MS = 2>
 __device__ __forceinline__ void dw_adam_tile(const AS_C EngineDev& E, const TileDesc* tdp_, bool polyak, int par,
                                              int par_x, lf* lds) {
@@ -946,129 +955,244 @@ __device__ __forceinline__ void dw_adam_tile(const AS_C EngineDev& E, const Tile
   // every load of the tile (operands, element state, bias) is in flight
   seeds_to_lds(0);
   if (lseeds) __syncthreads();  // uniform
-  for (int r0 = 0; r0 < Bp; r0 += rstep) {
-    // slot by slot: its pieces -> LDS (waits only for this slot's loads: they
-    // complete in issue order), the next round's loads into its registers,
-    // barrier, its MFMAs -- while the later slots' loads are still landing
-    static_for<MAXS>([&](auto slc) {
-      constexpr int sl = decltype(slc)::value;
-      const int b0 = r0 + sl * SAC_UPD_BCH;
-      if (sl < ns && b0 < Bp) {  // uniform
-        const int bch = Bp - b0 < SAC_UPD_BCH ? Bp - b0 : SAC_UPD_BCH;
-        const int per_row = bch / EPR;
+  // slot sl's pieces of a round -> LDS (waits only for this slot's loads: they
+  // complete in issue order): dY parts added and seed-scaled in registers
+  auto stage_slot = [&](auto slc, int bch) __attribute__((always_inline)) {
+    constexpr int sl = decltype(slc)::value;
+    const int per_row = bch / EPR;
 #pragma unroll
-        for (int op = 0; op < 2; ++op)
+    for (int op = 0; op < 2; ++op)
 #pragma unroll
-          for (int pi = 0; pi < PPO; ++pi) {
-            const int i = tid + pi * UT;
-            const int row = i / per_row + 32 * op, pc = i % per_row;
-            u32x4 v = rg[sl][op ? GS : 0][pi];
-            if constexpr (sizeof(T) == 4) {
-              if constexpr (GS > 1)
-                if (op == 0) {  // dY: the parts' partials added in part order
-                  f32x4 a = __builtin_bit_cast(f32x4, v);
+      for (int pi = 0; pi < PPO; ++pi) {
+        const int i = tid + pi * UT;
+        const int row = i / per_row + 32 * op, pc = i % per_row;
+        u32x4 v = rg[sl][op ? GS : 0][pi];
+        if constexpr (sizeof(T) == 4) {
+          if constexpr (GS > 1)
+            if (op == 0) {  // dY: the parts' partials added in part order
+              f32x4 a = __builtin_bit_cast(f32x4, v);
 #pragma unroll
-                  for (int q = 1; q < GS; ++q) a += __builtin_bit_cast(f32x4, rg[sl][q][pi]);
-                  v = __builtin_bit_cast(u32x4, a);
-                }
-              if (op == 0 && seedp)
-                v = __builtin_bit_cast(u32x4, __builtin_bit_cast(f32x4, v) *
-                                                  (lseeds ? *(const AS_L f32x4*)(seedL + sl * SAC_UPD_BCH + pc * EPR)
-                                                          : sdr[sl][pi][0]));
-            } else if (op == 0 && (GS > 1 || seedp)) {
-              // bf16 dY: the parts added in fp32 (part order), scaled by the
-              // rows' seeds in fp32, rounded to bf16 once
-              bf16x8 h = __builtin_bit_cast(bf16x8, v);
-              float a[8];
-#pragma unroll
-              for (int e = 0; e < 8; ++e) a[e] = (float)h[e];
-#pragma unroll
-              for (int q = 1; q < GS; ++q) {
-                const bf16x8 hq = __builtin_bit_cast(bf16x8, rg[sl][q][pi]);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) a[e] += (float)hq[e];
-              }
-              if (seedp)  // bf16: per-piece seeds (lseeds is fp32 only)
-#pragma unroll
-                for (int e = 0; e < 8; ++e) a[e] *= sdr[sl][pi][e >> 2][e & 3];
-#pragma unroll
-              for (int e = 0; e < 8; ++e) h[e] = (bf16)a[e];
-              v = __builtin_bit_cast(u32x4, h);
+              for (int q = 1; q < GS; ++q) a += __builtin_bit_cast(f32x4, rg[sl][q][pi]);
+              v = __builtin_bit_cast(u32x4, a);
             }
-            if (i < 32 * per_row) *(AS_L u32x4*)(stage + sl * slot_el + row * lds_row + pc * EPR) = v;
-          }
-        issue(r0 + rstep, slc);
-        __syncthreads();
-        if (r0 == 0 && sl == 0) STAMP(polyak ? 51 : 55);
-        if (bias_acc) {  // bias gradient: this lane's columns of the slot's (scaled) dY rows
+          if (op == 0 && seedp)
+            v = __builtin_bit_cast(u32x4, __builtin_bit_cast(f32x4, v) *
+                                              (lseeds ? *(const AS_L f32x4*)(seedL + sl * SAC_UPD_BCH + pc * EPR)
+                                                      : sdr[sl][pi][0]));
+        } else if (op == 0 && (GS > 1 || seedp)) {
+          // bf16 dY: the parts added in fp32 (part order), scaled by the
+          // rows' seeds in fp32, rounded to bf16 once
+          bf16x8 h = __builtin_bit_cast(bf16x8, v);
+          float a[8];
 #pragma unroll
-          for (int j = 0; j < BPT; ++j) {
-            const int t = tid + j * UT, bn = t >> 4, bs = t & 15;
-            if (t < 512)  // 16-B LDS reads: lane bs takes the row's 16-B pieces bs, bs + 16, ...
-              for (int c = bs * EPR; c < bch; c += 16 * EPR) {
-                const AS_L T* q = stage + sl * slot_el + bn * lds_row + c;
+          for (int e = 0; e < 8; ++e) a[e] = (float)h[e];
+#pragma unroll
+          for (int q = 1; q < GS; ++q) {
+            const bf16x8 hq = __builtin_bit_cast(bf16x8, rg[sl][q][pi]);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) a[e] += (float)hq[e];
+          }
+          if (seedp)  // bf16: per-piece seeds (lseeds is fp32 only)
+#pragma unroll
+            for (int e = 0; e < 8; ++e) a[e] *= sdr[sl][pi][e >> 2][e & 3];
+#pragma unroll
+          for (int e = 0; e < 8; ++e) h[e] = (bf16)a[e];
+          v = __builtin_bit_cast(u32x4, h);
+        }
+        if (i < 32 * per_row) *(AS_L u32x4*)(stage + sl * slot_el + row * lds_row + pc * EPR) = v;
+      }
+  };
+  // ---- single-round tiles: the 1024-thread kernels with the whole batch in
+  // one round's slots (every tile of the small-batch layouts).  One barrier
+  // once every slot is staged; each wave then issues all fragment reads of its
+  // (sub-tile, K-quarter) pair and runs its MFMAs in the multi-round order
+  // (slot 0's chunks kq, kq + 4, .., then slot 1's), the bias lanes' reads in
+  // flight under them.  The K-quarter partials go to an LDS area of their own
+  // (upd_partials: nothing waits for the stage to be free), and after the
+  // second barrier the thread that sums an element's partials keeps the sum in
+  // a register (gel) for its Adam step: 3 barriers per tile, 7 on the
+  // multi-round path below.  Every float operation is the multi-round path's,
+  // in the same order.
+  constexpr int NIT = SAC_UPD_BCH / KC / KQ;     // MFMA K-steps per (slot, K-quarter)
+  constexpr int NBP = SAC_UPD_BCH / (16 * EPR);  // bias pieces per lane per slot
+  bool single = false;
+  if constexpr (UT == SAC_UPD_THREADS) single = Bp <= rstep;  // uniform
+  float gel[EPT];  // single-round: the elements' dW (K-quarters summed, then the batch parts)
+  if (single) {
+    if constexpr (UT == SAC_UPD_THREADS) {
+      static_assert(PPW == 1 && BPT == 1, "one (sub-tile, K-quarter) pair per wave");
+      typedef typename MM<T>::Frag Frag;
+      static_for<MAXS>([&](auto slc) {
+        constexpr int sl = decltype(slc)::value;
+        const int b0 = sl * SAC_UPD_BCH;
+        if (sl < ns && b0 < Bp) stage_slot(slc, Bp - b0 < SAC_UPD_BCH ? Bp - b0 : SAC_UPD_BCH);  // uniform
+      });
+      __syncthreads();
+      STAMP(polyak ? 51 : 55);
+      const int kq = wave >> 2, sn = ((wave & 3) >> 1) * 16, sk = (wave & 1) * 16;
+      const int bn = tid >> 4, bs = tid & 15;
+      const bool bias_lane = bias_acc && tid < 512;
+      // FULL: every slot in use is a whole one (compile-time trip counts, no masks)
+      auto dw_and_bias = [&](auto fullc) __attribute__((always_inline)) {
+        constexpr bool FULL = decltype(fullc)::value;
+        Frag fa[MAXS][NIT], fb[MAXS][NIT], bx[MAXS][NBP];
+        auto slots = [&](auto&& f) __attribute__((always_inline)) {
+          static_for<MAXS>([&](auto slc) {
+            constexpr int sl = decltype(slc)::value;
+            const int b0 = sl * SAC_UPD_BCH;
+            if (sl < ns && b0 < Bp)  // uniform
+              f(slc, FULL || Bp - b0 >= SAC_UPD_BCH ? SAC_UPD_BCH : Bp - b0);
+          });
+        };
+        slots([&](auto slc, int bch) {
+          constexpr int sl = decltype(slc)::value;
+          const AS_L T* arow = stage + sl * slot_el + (sn + c) * lds_row + g * KL;
+          const AS_L T* brow = stage + sl * slot_el + (32 + sk + c) * lds_row + g * KL;
+#pragma unroll
+          for (int it = 0; it < NIT; ++it) {
+            const int ch = kq + it * KQ;
+            if (FULL || ch < bch / KC) {
+              fa[sl][it] = *(const AS_L Frag*)(arow + ch * KC);
+              fb[sl][it] = *(const AS_L Frag*)(brow + ch * KC);
+            }
+          }
+        });
+        if (bias_lane)  // lane bs takes its row's 16-B pieces bs, bs + 16, ... of the (scaled) dY rows
+          slots([&](auto slc, int bch) {
+            constexpr int sl = decltype(slc)::value;
+#pragma unroll
+            for (int it = 0; it < NBP; ++it) {
+              const int bc = (bs + it * 16) * EPR;
+              if (FULL || bc < bch) bx[sl][it] = *(const AS_L Frag*)(stage + sl * slot_el + bn * lds_row + bc);
+            }
+          });
+        slots([&](auto slc, int bch) {
+          constexpr int sl = decltype(slc)::value;
+#pragma unroll
+          for (int it = 0; it < NIT; ++it)
+            if (FULL || kq + it * KQ < bch / KC) MM<T>::mma(acc[0], fa[sl][it], fb[sl][it]);
+        });
+        if (bias_lane)
+          slots([&](auto slc, int bch) {
+            constexpr int sl = decltype(slc)::value;
+#pragma unroll
+            for (int it = 0; it < NBP; ++it)
+              if (FULL || (bs + it * 16) * EPR < bch) {
+                const Frag x = bx[sl][it];
                 if constexpr (sizeof(T) == 4) {
-                  const f32x4 x = *(const AS_L f32x4*)q;
-                  bsum[j] += (x[0] + x[1]) + (x[2] + x[3]);
+                  bsum[0] += (x[0] + x[1]) + (x[2] + x[3]);
                 } else {
-                  const bf16x8 x = *(const AS_L bf16x8*)q;
                   float s = 0.f;
 #pragma unroll
                   for (int e = 0; e < 8; ++e) s += (float)x[e];
-                  bsum[j] += s;
+                  bsum[0] += s;
                 }
               }
-          }
-        }
+          });
+      };
+      if (Bp % SAC_UPD_BCH == 0)  // uniform
+        dw_and_bias(std::true_type{});
+      else
+        dw_and_bias(std::false_type{});
+      STAMP(polyak ? 49 : 53);
+      lf* part = upd_partials();
 #pragma unroll
-        for (int j = 0; j < PPW; ++j) {
-          const int pr = wave + j * NWV, kq = pr >> 2;
-          const int ns = ((pr & 3) >> 1) * 16, ks = (pr & 1) * 16;
-          const AS_L T* arow = stage + sl * slot_el + (ns + c) * lds_row + g * KL;
-          const AS_L T* brow = stage + sl * slot_el + (32 + ks + c) * lds_row + g * KL;
-          for (int ch = kq; ch < bch / KC; ch += KQ) {
-            typename MM<T>::Frag a, b;
-            if constexpr (sizeof(T) == 2) {
-              a = *(const AS_L bf16x8*)(arow + ch * KC);
-              b = *(const AS_L bf16x8*)(brow + ch * KC);
-            } else {
-              a = *(const AS_L f32x4*)(arow + ch * KC);
-              b = *(const AS_L f32x4*)(brow + ch * KC);
-            }
-            MM<T>::mma(acc[j], a, b);
-          }
-        }
+      for (int i = 0; i < 4; ++i) part[kq * (32 * 33) + (sn + g * 4 + i) * 33 + sk + c] = acc[0][i];
+      if (bias_lane) red[bn * 17 + bs] = bsum[0];
+      __syncthreads();
+#pragma unroll
+      for (int e = 0; e < EPT; ++e) {  // summed in quarter order
+        const int el = tid + e * UT, o = (el >> 5) * 33 + (el & 31);
+        float sum = part[o];
+#pragma unroll
+        for (int q = 1; q < KQ; ++q) sum += part[q * (32 * 33) + o];
+        gel[e] = sum;
       }
-    });
-    seeds_to_lds(r0 + rstep);  // every thread's reads of this round's seeds are behind a slot barrier
-    __syncthreads();  // the stage is refilled by the next round
-  }
-  STAMP(polyak ? 49 : 53);
-  {  // K-quarter partials -> the (free) stage area, summed in quarter order below
-#pragma unroll
-    for (int j = 0; j < PPW; ++j) {
-      const int pr = wave + j * NWV;
-      const int ns = ((pr & 3) >> 1) * 16, ks = (pr & 1) * 16;
-      lf* part = (lf*)stage + (pr >> 2) * (32 * 33);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) part[(ns + g * 4 + i) * 33 + ks + c] = acc[j][i];
     }
-  }
-  __syncthreads();
-  for (int el = tid; el < 1024; el += UT) {
-    const int o = (el >> 5) * 33 + (el & 31);
-    const lf* part = (const lf*)stage;
-    float sum = part[o];
+  } else {
+    for (int r0 = 0; r0 < Bp; r0 += rstep) {
+      // slot by slot: its pieces -> LDS, the next round's loads into its
+      // registers, barrier, its MFMAs -- while the later slots' loads are still
+      // landing
+      static_for<MAXS>([&](auto slc) {
+        constexpr int sl = decltype(slc)::value;
+        const int b0 = r0 + sl * SAC_UPD_BCH;
+        if (sl < ns && b0 < Bp) {  // uniform
+          const int bch = Bp - b0 < SAC_UPD_BCH ? Bp - b0 : SAC_UPD_BCH;
+          stage_slot(slc, bch);
+          issue(r0 + rstep, slc);
+          __syncthreads();
+          if (r0 == 0 && sl == 0) STAMP(polyak ? 51 : 55);
+          if (bias_acc) {  // bias gradient: this lane's columns of the slot's (scaled) dY rows
 #pragma unroll
-    for (int q = 1; q < KQ; ++q) sum += part[q * (32 * 33) + o];
-    accs[o] = sum;
-  }
+            for (int j = 0; j < BPT; ++j) {
+              const int t = tid + j * UT, bn = t >> 4, bs = t & 15;
+              if (t < 512)  // 16-B LDS reads: lane bs takes the row's 16-B pieces bs, bs + 16, ...
+                for (int c = bs * EPR; c < bch; c += 16 * EPR) {
+                  const AS_L T* q = stage + sl * slot_el + bn * lds_row + c;
+                  if constexpr (sizeof(T) == 4) {
+                    const f32x4 x = *(const AS_L f32x4*)q;
+                    bsum[j] += (x[0] + x[1]) + (x[2] + x[3]);
+                  } else {
+                    const bf16x8 x = *(const AS_L bf16x8*)q;
+                    float s = 0.f;
 #pragma unroll
-  for (int j = 0; j < BPT; ++j) {
-    const int t = tid + j * UT;
-    if (bias_acc && t < 512) red[(t >> 4) * 17 + (t & 15)] = bsum[j];
+                    for (int e = 0; e < 8; ++e) s += (float)x[e];
+                    bsum[j] += s;
+                  }
+                }
+            }
+          }
+#pragma unroll
+          for (int j = 0; j < PPW; ++j) {
+            const int pr = wave + j * NWV, kq = pr >> 2;
+            const int ns = ((pr & 3) >> 1) * 16, ks = (pr & 1) * 16;
+            const AS_L T* arow = stage + sl * slot_el + (ns + c) * lds_row + g * KL;
+            const AS_L T* brow = stage + sl * slot_el + (32 + ks + c) * lds_row + g * KL;
+            for (int ch = kq; ch < bch / KC; ch += KQ) {
+              typename MM<T>::Frag a, b;
+              if constexpr (sizeof(T) == 2) {
+                a = *(const AS_L bf16x8*)(arow + ch * KC);
+                b = *(const AS_L bf16x8*)(brow + ch * KC);
+              } else {
+                a = *(const AS_L f32x4*)(arow + ch * KC);
+                b = *(const AS_L f32x4*)(brow + ch * KC);
+              }
+              MM<T>::mma(acc[j], a, b);
+            }
+          }
+        }
+      });
+      seeds_to_lds(r0 + rstep);  // every thread's reads of this round's seeds are behind a slot barrier
+      __syncthreads();  // the stage is refilled by the next round
+    }
+    STAMP(polyak ? 49 : 53);
+    {  // K-quarter partials -> the (free) stage area, summed in quarter order below
+#pragma unroll
+      for (int j = 0; j < PPW; ++j) {
+        const int pr = wave + j * NWV;
+        const int ns = ((pr & 3) >> 1) * 16, ks = (pr & 1) * 16;
+        lf* part = (lf*)stage + (pr >> 2) * (32 * 33);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) part[(ns + g * 4 + i) * 33 + ks + c] = acc[j][i];
+      }
+    }
+    __syncthreads();
+    for (int el = tid; el < 1024; el += UT) {
+      const int o = (el >> 5) * 33 + (el & 31);
+      const lf* part = (const lf*)stage;
+      float sum = part[o];
+#pragma unroll
+      for (int q = 1; q < KQ; ++q) sum += part[q * (32 * 33) + o];
+      accs[o] = sum;
+    }
+#pragma unroll
+    for (int j = 0; j < BPT; ++j) {
+      const int t = tid + j * UT;
+      if (bias_acc && t < 512) red[(t >> 4) * 17 + (t & 15)] = bsum[j];
+    }
+    __syncthreads();
   }
-  __syncthreads();
   // producer parts a consumer takes (the 512-thread tiles: up to 7, else 3)
   constexpr int MAXP = UT == 512 ? 7 : 3;
   float gbx[MAXP];  // staged-row bias: the producer parts' column sums (consumer, tid < 32)
@@ -1078,8 +1202,11 @@ __device__ __forceinline__ void dw_adam_tile(const AS_C EngineDev& E, const Tile
     const uint32_t ep = *GPC(uint32_t, E.sync) + 1u;  // per launch (B and D have their own granules)
     if (td.kpart >= 2) {
       AS_G uint64_t* mine = GP(uint64_t, td.part) + (size_t)(td.kpart - 2) * SAC_PART_STRIDE;
-      for (int el = tid; el < 1024; el += UT) {
-        const uint64_t x = (uint64_t)__float_as_uint(accs[(el >> 5) * 33 + (el & 31)]) | ((uint64_t)ep << 32);
+#pragma unroll
+      for (int e = 0; e < EPT; ++e) {
+        const int el = tid + e * UT;
+        const float dw = single ? gel[e] : accs[(el >> 5) * 33 + (el & 31)];
+        const uint64_t x = (uint64_t)__float_as_uint(dw) | ((uint64_t)ep << 32);
         __hip_atomic_store((uint64_t*)(mine + el), x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
       if (bias_acc && tid < 32) {
@@ -1128,13 +1255,16 @@ __device__ __forceinline__ void dw_adam_tile(const AS_C EngineDev& E, const Tile
 #pragma unroll
     for (int j = 0; j < EL; ++j) {
       const int el = tid + j * UT, o = (el >> 5) * 33 + (el & 31);
-      float sum = accs[o];
+      float sum = single ? gel[j] : accs[o];
 #pragma unroll
       for (int q = 0; q < MAXP; ++q)
         if (q < np) sum += v[q][j];
-      accs[o] = sum;
+      if (single)
+        gel[j] = sum;
+      else
+        accs[o] = sum;
     }
-    __syncthreads();
+    if (!single) __syncthreads();  // uniform
   }
   STAMP(polyak ? 50 : 54);
   // ---- 3. elements: Adam + Polyak on the masters; new values -> LDS
@@ -1147,7 +1277,8 @@ __device__ __forceinline__ void dw_adam_tile(const AS_C EngineDev& E, const Tile
     pn[e] = 0.f;
     tn[e] = 0.f;
     if (ok[e]) {
-      pn[e] = adam_elem(p[e], m[e], v[e], accs[(el >> 5) * 33 + (el & 31)], w1, b2, w2, bc2s, eps, neg_step);
+      const float dw = single ? gel[e] : accs[(el >> 5) * 33 + (el & 31)];
+      pn[e] = adam_elem(p[e], m[e], v[e], dw, w1, b2, w2, bc2s, eps, neg_step);
       W[idx[e]] = p[e];
       Wm[idx[e]] = m[e];
       Wv[idx[e]] = v[e];
@@ -1157,7 +1288,7 @@ __device__ __forceinline__ void dw_adam_tile(const AS_C EngineDev& E, const Tile
       }
     }
   }
-  __syncthreads();  // every read of accs done
+  if (!single) __syncthreads();  // every read of accs done (uniform; a single-round tile reads none)
 #pragma unroll
   for (int e = 0; e < EPT; ++e) {
     const int el = tid + e * UT;
