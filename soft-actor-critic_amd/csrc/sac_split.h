@@ -77,11 +77,14 @@ struct HTiles {
   float b[NTW];
 };
 
-template <typename T, int NTW, int HC, bool COH = false>
+// FULL: the view's reduction is known to fill all HC slots (every split-kernel
+// step but layer 0 and pi's layer-2 dX); otherwise a slot past the view's
+// chunks stays empty (no load: nothing multiplies it).
+template <typename T, int NTW, int HC, bool COH = false, bool FULL = false>
 __device__ __forceinline__ void ht_issue(HTiles<T, NTW, HC>& ht, const GemmW& w) {
   constexpr uint32_t FSB = 64 * MM<T>::KL * sizeof(T);
   const int lane = threadIdx.x & 63, wave = wave_id();
-  const int nch = w.cols / MM<T>::KC;
+  const int nch = FULL ? HC : w.cols / MM<T>::KC;
   const __amdgpu_buffer_rsrc_t rs = coh_rsrc(w.p, 0xFFFFFFF0u);
   static_for<NTW>([&](auto jc) {
     constexpr int j = decltype(jc)::value;
@@ -91,9 +94,8 @@ __device__ __forceinline__ void ht_issue(HTiles<T, NTW, HC>& ht, const GemmW& w)
     const uint32_t o = (uint32_t)(((size_t)t * 16 * w.tcols + lane * MM<T>::KL) * sizeof(T));
     static_for<HC>([&](auto uc) {
       constexpr int u = decltype(uc)::value;
-      const uint32_t cu = u < nch ? u : nch - 1;
-      if (has)
-        ht.f[j][u] = coh_frag<T, COH>(rs, o + cu * FSB);
+      if (has && u < nch)
+        ht.f[j][u] = coh_frag<T, COH>(rs, o + u * FSB);
       else
         ht.f[j][u] = typename MM<T>::Frag{};
     });
@@ -182,6 +184,49 @@ __device__ __forceinline__ void gemm_hs(const lf* __restrict__ A, int lda, const
   });
 }
 
+// gemm_hs for a step whose shape the split kernels know: NCH reduction chunks,
+// all held, and NTC output tiles (0: nt tiles, a run-time count, NTW = 1).
+// Whether the wave owns tile j is tested once, around the tile's whole chain
+// (a wave without the tile reads no LDS either); NTC = 2 SAC_NW: every wave
+// owns both tiles and nothing is tested.  The chain is then one basic block,
+// and the compiler's scheduler places the MFMAs of the even-chunk and odd-chunk
+// accumulators (and of the two tiles of NTW = 2) between one another; writing
+// them alternately in the source gave the same instruction stream and the same
+// speed (profiles/ab_split_gemm_shapes_items.txt), so the source keeps chunk
+// order.  Each accumulator takes the products gemm_hs gives it, in gemm_hs's
+// order, and the tile is acc0 + acc1: the same bits.
+template <typename T, int NTW, int NCH, int NTC, int HC, typename Epi>
+__device__ __forceinline__ void gemm_hf(const lf* __restrict__ A, int lda, int nt, const HTiles<T, NTW, HC>& ht,
+                                        Epi&& epi) {
+  typedef typename MM<T>::Frag F;
+  typedef MM<T> M;
+  static_assert(NCH >= 1 && NCH <= HC, "every chunk of a fixed-shape step is held");
+  static_assert(NTW == 1 ? NTC <= SAC_NW : NTC == NTW * SAC_NW, "one tile per wave, or every tile of every wave");
+  const int lane = threadIdx.x & 63, wave = wave_id();
+  const int c = lane & 15, g = lane >> 4;
+  const lf* arow = A + c * lda + g * M::KL;
+  const bool own = NTC == NTW * SAC_NW || wave < (NTC ? NTC : nt);  // wave-uniform
+  auto chain = [&]() __attribute__((always_inline)) {
+    constexpr int NJ = NTW;
+    F a[NCH];
+    static_for<NCH>([&](auto uc) { a[decltype(uc)::value] = M::from_lds(arow + decltype(uc)::value * M::KC); });
+    f32x4 acc[NJ][2];
+    static_for<NJ>([&](auto jc) { acc[decltype(jc)::value][0] = acc[decltype(jc)::value][1] = (f32x4){0.f, 0.f, 0.f, 0.f}; });
+    static_for<NCH>([&](auto uc) {
+      constexpr int u = decltype(uc)::value;
+      static_for<NJ>([&](auto jc) {
+        constexpr int j = decltype(jc)::value;
+        M::mma(acc[j][u & 1], a[u], ht.f[j][u]);
+      });
+    });
+    static_for<NJ>([&](auto jc) {
+      constexpr int j = decltype(jc)::value;
+      epi(j, (wave + j * SAC_NW) * 16 + c, acc[j][0] + acc[j][1]);
+    });
+  };
+  if (own) chain();
+}
+
 // ---------------------------------------------------------------------------- k-split GEMM
 // Small-N steps (NT <= 2 output tiles, long reduction): the reduction is
 // split over the waves (SAC_NW / NT waves per tile, consecutive chunk slices),
@@ -236,7 +281,12 @@ __device__ __forceinline__ void ks_issue(KsHeld<T, MC>& kh, const GemmW& w) {
 // the reducer instead of an LDS write, a second barrier and a re-read.  No
 // barrier follows: the caller adds one before anything reads what epi wrote to
 // LDS, and before red is written again.
-template <typename T, bool COH = false, int MC = 1, typename Epi>
+// NTK / NCHK: the view's tile count (1 or 2) and reduction chunk count where the
+// caller knows them at compile time (0: w's, at run time).  With NTK the sum
+// over the waves' partials has a fixed trip count, so its LDS reads go out
+// together instead of one per addition (added in the same slice order); with
+// both the slice bounds fold and a held slice runs unguarded.
+template <typename T, bool COH = false, int MC = 1, int NTK = 0, int NCHK = 0, typename Epi>
 __device__ __forceinline__ void gemm_ksplit_epi(const lf* __restrict__ A, int lda, const GemmW& w, lf* red,
                                                 const KsHeld<T, MC>* kh, Epi&& epi) {
   typedef typename MM<T>::Frag F;
@@ -244,14 +294,23 @@ __device__ __forceinline__ void gemm_ksplit_epi(const lf* __restrict__ A, int ld
   constexpr uint32_t FSB = 64 * KL * sizeof(T);
   const int lane = threadIdx.x & 63, wave = wave_id();
   const int c = lane & 15, g = lane >> 4;
-  const int NT = w.NT;  // 1 or 2
+  const int NT = NTK ? NTK : w.NT;  // 1 or 2
   int t, c0, c1, wpt;
-  ks_slice<T>(w, t, c0, c1, wpt);
+  if constexpr (NTK != 0) {  // ks_slice with the tile count (and the chunk count) folded
+    wpt = SAC_NW / NTK;
+    t = wave % NTK;
+    const int nch = NCHK ? NCHK : w.cols / KC, per = (nch + wpt - 1) / wpt;
+    c0 = (wave / NTK) * per;
+    c1 = c0 + per < nch ? c0 + per : nch;
+  } else {
+    ks_slice<T>(w, t, c0, c1, wpt);
+  }
   const __amdgpu_buffer_rsrc_t rs = coh_rsrc(w.p, 0xFFFFFFF0u);
   const uint32_t o = (uint32_t)(((size_t)t * 16 * w.tcols + lane * KL) * sizeof(T));
   const lf* arow = A + c * lda + g * KL;
   f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  if (kh && kh->ok) {  // uniform: the slice's fragments are already in registers
+  constexpr bool HELD = NTK != 0 && NCHK != 0 && (NCHK * NTK + SAC_NW - 1) / SAC_NW <= MC;  // ks_issue's ok, known
+  if (kh && (HELD || kh->ok)) {  // uniform: the slice's fragments are already in registers
     static_for<MC>([&](auto uc) {
       constexpr int u = decltype(uc)::value;
       if (c0 + u < c1) MM<T>::mma(acc, MM<T>::from_lds(arow + (c0 + u) * KC), kh->f[u]);
@@ -276,6 +335,17 @@ __device__ __forceinline__ void gemm_ksplit_epi(const lf* __restrict__ A, int ld
 #pragma unroll
   for (int i = 0; i < 4; ++i) red[wave * 256 + (g * 4 + i) * 16 + c] = acc[i];
   __syncthreads();
+  if constexpr (NTK != 0) {
+    static_assert(256 * NTK <= SAC_THREADS, "one element per thread");
+    if (threadIdx.x < 256 * NTK) {
+      const int i = threadIdx.x, tt = i / 256, e = i % 256, r = e / 16, cc = e % 16;
+      float s = 0.f;
+#pragma unroll
+      for (int q = 0; q < SAC_NW / NTK; ++q) s += red[(q * NTK + tt) * 256 + e];
+      epi(r, tt * 16 + cc, s);
+    }
+    return;
+  }
   for (int i = threadIdx.x; i < 256 * NT; i += SAC_THREADS) {
     const int tt = i / 256, e = i % 256, r = e / 16, cc = e % 16;
     float s = 0.f;
@@ -283,10 +353,10 @@ __device__ __forceinline__ void gemm_ksplit_epi(const lf* __restrict__ A, int ld
     epi(r, tt * 16 + cc, s);
   }
 }
-template <typename T, bool COH = false, int MC = 1>
+template <typename T, bool COH = false, int MC = 1, int NTK = 0, int NCHK = 0>
 __device__ __forceinline__ void gemm_ksplit(const lf* __restrict__ A, int lda, const GemmW& w, lf* red, lf* out,
                                             int ldo, const KsHeld<T, MC>* kh = nullptr) {
-  gemm_ksplit_epi<T, COH, MC>(A, lda, w, red, kh, [&](int r, int col, float s) { out[r * ldo + col] = s; });
+  gemm_ksplit_epi<T, COH, MC, NTK, NCHK>(A, lda, w, red, kh, [&](int r, int col, float s) { out[r * ldo + col] = s; });
   __syncthreads();
 }
 
@@ -355,6 +425,7 @@ __device__ __forceinline__ void target_critic_split_body(const EngineDev* __rest
   constexpr int KC = MM<T>::KC;
   constexpr int HC0 = 64 / KC;         // layer 0: chunks held (the rest streams)
   constexpr int NCH_H = SPLIT_H / KC;  // layer 1 reduction
+  constexpr int NT_H = SPLIT_H / 16;   // output tiles of a full-width step: two per wave
   constexpr int NCH_HH = HH / KC;      // layer 1 dX reduction of a half
   const int tid = threadIdx.x;
   // blocks: pi(s') as WP parts x nrt, then roles 1..5 as 2 halves x nrt each
@@ -454,7 +525,7 @@ __device__ __forceinline__ void target_critic_split_body(const EngineDev* __rest
         rr = p[2 * R * O + R * A + tid];
         rd = p[2 * R * O + R * A + R + tid];
       }
-      ht_issue<T, 1, NCH_H>(h1, w1);
+      ht_issue<T, 1, NCH_H, false, true>(h1, w1);
       h1_issued = true;
       if (L0.Kp <= 64) {  // uniform: the record goes straight into layer 0's input
         // X = [s' | 0] for pi(s') and the target critics (a~' comes after the head),
@@ -502,7 +573,7 @@ __device__ __forceinline__ void target_critic_split_body(const EngineDev* __rest
              hdr[3] == (uint64_t)(uintptr_t)rb.obs && hdr[4] == (uint64_t)GPC(int64_t, rb.state)[2];
   }
   x_direct = x_direct && staged;  // a stale record: the gather and build_x below overwrite Xb
-  if (!h1_issued) ht_issue<T, 1, NCH_H>(h1, w1);
+  if (!h1_issued) ht_issue<T, 1, NCH_H, false, true>(h1, w1);
   // layer 2's k-split slice (layer 2 runs after the hand-off for the target
   // critics, and at the end of pi(s')'s chain): held from here
   GemmW w2n = gw_sub<T>(L2.Wc, L2.Kp, 0, L2.Np, h * HHr, HHr, nullptr, 0);
@@ -630,7 +701,7 @@ __device__ __forceinline__ void target_critic_split_body(const EngineDev* __rest
   auto forward01 = [&](bool keepP, bool stXT, bool pi_actor, auto&& after_l1, bool l0_done = false) {
     // layer 0: X [R][Kp0] -> P0 / H0 [R][H] (l0_done: the caller computed H0)
     const int act = net.hid_act;
-    if (!l0_done) gemm_hs<T, 2, HC0, false>(Xb, ld, w0, &h0, [&](int j, int col, const f32x4& acc) {
+    auto epi0 = [&](int j, int col, const f32x4& acc) {
       const bool nv = col < L0.N;
       const float bn = h0.b[j];
 #pragma unroll
@@ -640,8 +711,15 @@ __device__ __forceinline__ void target_critic_split_body(const EngineDev* __rest
         if (keepP) P0[r * ldp0 + col] = p;
         H0[r * ld + col] = act == ACT_RELU ? (p > 0.f ? p : 0.f) : p;
       }
-    });
+    };
     if (!l0_done) {
+      // Kp0 = 32 / 64 (uniform): every chunk held, the fixed-shape step; wider: held chunks, then the stream
+      if (L0.Kp == 32)
+        gemm_hf<T, 2, 32 / KC, NT_H>(Xb, ld, 0, h0, epi0);
+      else if (L0.Kp == 64)
+        gemm_hf<T, 2, 64 / KC, NT_H>(Xb, ld, 0, h0, epi0);
+      else
+        gemm_hs<T, 2, HC0, false>(Xb, ld, w0, &h0, epi0);
       if (act != ACT_RELU && act != ACT_ID) act_pass_fwd<R>(H0, ld, L0.Np >> 4, act);
       __syncthreads();
     }
@@ -656,7 +734,7 @@ __device__ __forceinline__ void target_critic_split_body(const EngineDev* __rest
     STAMP(2);
     if (sizeof(T) == 4 && !kh2.ok) ks_issue<T, KsHeld<T>::MAXC, false>(kh2, w2n);  // fp32: under layer 1 (target critics: before the poll)
     // layer 1, this half: H0 -> P1 / H1 [R][HH]
-    gemm_hs<T, 1, NCH_H, false>(H0, ld, w1, &h1, [&](int j, int col, const f32x4& acc) {
+    gemm_hf<T, 1, NCH_H, 0>(H0, ld, w1.NT, h1, [&](int j, int col, const f32x4& acc) {
       const float bn = h1.b[j];
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
@@ -681,7 +759,7 @@ __device__ __forceinline__ void target_critic_split_body(const EngineDev* __rest
                        nvalid, nullptr);
     STAMP(3);
     // layer 2, this half's partial sum: outB [R][Np2]
-    gemm_ksplit_epi<T, false, decltype(kh2)::MAXC>(H1, ldh1, w2n, red, &kh2, [&](int r, int col, float s) {
+    auto epi2 = [&](int r, int col, float s) {
       if (l2_pub == 0) {
         outB[r * ldo + col] = s;
       } else if (l2_pub == 1) {
@@ -690,7 +768,11 @@ __device__ __forceinline__ void target_critic_split_body(const EngineDev* __rest
         gran_put(l2_g + r, s, ep);
         if (l2_keep) outB[r * ldo] = s;
       }
-    });
+    };
+    if (w2n.NT == 1)  // uniform: the critics, and pi up to 2A = 16
+      gemm_ksplit_epi<T, false, decltype(kh2)::MAXC, 1>(H1, ldh1, w2n, red, &kh2, epi2);
+    else
+      gemm_ksplit_epi<T, false, decltype(kh2)::MAXC, 2>(H1, ldh1, w2n, red, &kh2, epi2);
     if (l2_pub == 0 || l2_keep) __syncthreads();  // uniform
     STAMP(4);
   };
@@ -769,7 +851,7 @@ __device__ __forceinline__ void target_critic_split_body(const EngineDev* __rest
             const typename MM<T>::Frag a = MM<T>::from_lds(arow + u * KC);
             static_for<2>([&](auto jc) {
               constexpr int j = decltype(jc)::value;
-              if (wave + j * SAC_NW < w0.NT) MM<T>::mma(acc[j][u & 1], a, h0.f[j][u]);
+              MM<T>::mma(acc[j][u & 1], a, h0.f[j][u]);  // NT_H tiles: both are this wave's
             });
           }
         });
@@ -865,7 +947,7 @@ __device__ __forceinline__ void target_critic_split_body(const EngineDev* __rest
     // bf16: held from the start too; fp32 (no register room: 51 VGPRs would
     // spill) issued as soon as layer 1's forward GEMM has freed h1's registers.
     // W2's element for this thread's column n = tid % HH
-    if constexpr (sizeof(T) == 2) ht_issue<T, 2, NCH_HH, false>(ht1, wt1);
+    if constexpr (sizeof(T) == 2) ht_issue<T, 2, NCH_HH, false, true>(ht1, wt1);
     static_assert(SAC_THREADS % SPLIT_HH == 0, "one W2 column per thread in the unit-seed loop");
     const bool relu_id = net.hid_act == ACT_RELU || net.hid_act == ACT_ID;
     mk_u1 = relu_id;
@@ -878,7 +960,7 @@ __device__ __forceinline__ void target_critic_split_body(const EngineDev* __rest
     // layer-0 input X^T is shared by Q1 and Q2: Q1's halves store it (columns h Bp + r0)
     if (qi == 0) store_T<T, R>(Xb, ld, L0.Kp, L0.K, L0.XT, 2 * Bp, h * Bp + r0, nvalid, nullptr);
     forward01(true, true, false, [&] {
-      if constexpr (sizeof(T) == 4) ht_issue<T, 2, NCH_HH, false>(ht1, wt1);
+      if constexpr (sizeof(T) == 4) ht_issue<T, 2, NCH_HH, false, true>(ht1, wt1);
     });
     // unit-seed backward (every layer's dY is linear in the row's seed 2(q - y)/B):
     // U1[r][n] = act'(P1[r][n]) * W2[0][h HH + n];  U0p = act'(P0) * (U1 W1[half])
@@ -890,7 +972,7 @@ __device__ __forceinline__ void target_critic_split_body(const EngineDev* __rest
         }
         __syncthreads();
       }
-      gemm_hs<T, 2, NCH_HH, false>(U1, ldu1, wt1, &ht1, [&](int j, int col, const f32x4& acc) {
+      gemm_hf<T, 2, NCH_HH, NT_H>(U1, ldu1, 0, ht1, [&](int j, int col, const f32x4& acc) {
         const bool kv = col < L1.K;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -977,6 +1059,7 @@ __device__ __forceinline__ void actor_split_body(const EngineDev* __restrict__ E
   constexpr int KC = MM<T>::KC;
   constexpr int HC0 = 64 / KC;
   constexpr int NCH_H = SPLIT_H / KC;
+  constexpr int NT_H = SPLIT_H / 16;
   constexpr int NCH_HH = HH / KC, NCH_HQ = HQ / KC;
   constexpr int NCH_32 = 32 / KC;
   const int tid = threadIdx.x;
@@ -1025,8 +1108,8 @@ __device__ __forceinline__ void actor_split_body(const EngineDev* __restrict__ E
     const GemmW wt1 = gw_sub<T>(L1.WTc, L1.Np, 0, L1.Kp, h * HQ, HQ, nullptr, 0);
     HTiles<T, 2, NCH_HQ> ht1;
     ht_issue<T, 2, HC0>(h0, w0);
-    ht_issue<T, 1, NCH_H>(h1, w1);
-    ht_issue<T, 2, NCH_HQ>(ht1, wt1);
+    ht_issue<T, 1, NCH_H, false, true>(h1, w1);
+    ht_issue<T, 2, NCH_HQ, false, true>(ht1, wt1);
     // the two k-split steps of the critic's chain (layer 2's partial q, then
     // layer 0's dX for the action columns) read weights phase B has just
     // written: held (issued behind the inputs), not a cold round trip each
@@ -1076,7 +1159,7 @@ __device__ __forceinline__ void actor_split_body(const EngineDev* __restrict__ E
     }
     __syncthreads();
     STAMP(33);
-    gemm_hs<T, 2, HC0, false>(Xb, ld, w0, &h0, [&](int j, int col, const f32x4& acc) {
+    auto epi0 = [&](int j, int col, const f32x4& acc) {
       const bool nv = col < L0.N;
       const float bn = h0.b[j];
 #pragma unroll
@@ -1086,10 +1169,18 @@ __device__ __forceinline__ void actor_split_body(const EngineDev* __restrict__ E
         P0[r * ldp0 + col] = p;
         H0[r * ld + col] = act == ACT_RELU ? (p > 0.f ? p : 0.f) : p;
       }
-    });
+    };
+    // uniform, as phase A's layer 0.  The stream is tested first: with the tests
+    // in the other order this kernel took 250 VGPRs in fp32 (224 bf16), so 234 (216).
+    if (Kp0 > 64)
+      gemm_hs<T, 2, HC0, false>(Xb, ld, w0, &h0, epi0);
+    else if (Kp0 == 32)
+      gemm_hf<T, 2, 32 / KC, NT_H>(Xb, ld, 0, h0, epi0);
+    else
+      gemm_hf<T, 2, 64 / KC, NT_H>(Xb, ld, 0, h0, epi0);
     if (act != ACT_RELU && act != ACT_ID) act_pass_fwd<R>(H0, ld, L0.Np >> 4, act);
     __syncthreads();
-    gemm_hs<T, 1, NCH_H, false>(H0, ld, w1, &h1, [&](int j, int col, const f32x4& acc) {
+    gemm_hf<T, 1, NCH_H, HQ / 16>(H0, ld, 0, h1, [&](int j, int col, const f32x4& acc) {
       const float bn = h1.b[j];
       float q2[4];
 #pragma unroll
@@ -1119,7 +1210,7 @@ __device__ __forceinline__ void actor_split_body(const EngineDev* __restrict__ E
         outB[tid * ldo] = s;
       }
     } else {
-      gemm_ksplit<T, false, decltype(kc2)::MAXC>(H1, ldh1, w2, red, outB, ldo, &kc2);  // partial q
+      gemm_ksplit<T, false, decltype(kc2)::MAXC, 1, NCH_HQ>(H1, ldh1, w2, red, outB, ldo, &kc2);  // partial q (N = 1)
     }
     STAMP(36 + qi);
     // unit-seed backward down to a~ (the pi role applies the min-Q weights and act'(q))
@@ -1131,7 +1222,7 @@ __device__ __forceinline__ void actor_split_body(const EngineDev* __restrict__ E
         }
         __syncthreads();
       }
-      gemm_hs<T, 2, NCH_HQ, false>(U1, ldu1, wt1, &ht1, [&](int j, int col, const f32x4& acc) {
+      gemm_hf<T, 2, NCH_HQ, NT_H>(U1, ldu1, 0, ht1, [&](int j, int col, const f32x4& acc) {
         const bool kv = col < L1.K;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -1146,10 +1237,14 @@ __device__ __forceinline__ void actor_split_body(const EngineDev* __restrict__ E
       // dX of layer 0 for the action columns: the 16-row tiles of W0^T holding [O, O + A)
       AS_G uint64_t* g = gs_at(E, GS_C1 + qi, rbi, h);
       // the partial dX0 [R][k1 - k0]: its action columns published by the threads that sum them
-      gemm_ksplit_epi<T, false, decltype(kc0)::MAXC>(Xb, ld, wt0, red, &kc0, [&](int r, int col, float s) {
+      auto epi_da = [&](int r, int col, float s) {
         const int j = col - (O - k0);
         if (j >= 0 && j < A) gran_put(g + r * A + j, s, ep);
-      });
+      };
+      if (wt0.NT == 1)  // uniform: the action columns lie in one 16-row tile of W0^T, or straddle two
+        gemm_ksplit_epi<T, false, decltype(kc0)::MAXC, 1, NCH_H>(Xb, ld, wt0, red, &kc0, epi_da);
+      else
+        gemm_ksplit_epi<T, false, decltype(kc0)::MAXC, 2, NCH_H>(Xb, ld, wt0, red, &kc0, epi_da);
       if (tid < R) gran_put(g + R * A + tid, outB[tid * ldo], ep);
     }
     STAMP(38 + qi);
@@ -1170,7 +1265,7 @@ __device__ __forceinline__ void actor_split_body(const EngineDev* __restrict__ E
   HTiles<T, 1, NCH_32> ht2;
   HTiles<T, 2, NCH_HH> ht1;
   ht_issue<T, 1, NCH_32, false>(ht2, wt2);
-  ht_issue<T, 2, NCH_HH, false>(ht1, wt1);
+  ht_issue<T, 2, NCH_HH, false, true>(ht1, wt1);
   {  // the hidden layers' activation derivatives: for ReLU the masks, read from
      // the next layer's X^T that phase A's pi(s) role stashed for phase D
      // (relu(p) > 0 <=> p > 0); otherwise the stashed pre-activations
@@ -1378,7 +1473,7 @@ __device__ __forceinline__ void actor_split_body(const EngineDev* __restrict__ E
   if (h == 0) store_T<T, R>(goutB, ldo, L2.Np, L2.N, L2.GT, Bp, r0, nvalid, L2.dbp);
   // dY1 (this half) = act'(P1) * (dOut W2[:, half])
   const int act = pi.hid_act;
-  gemm_hs<T, 1, NCH_32, false>(goutB, ldo, wt2, &ht2, [&](int j, int col, const f32x4& acc) {
+  auto epi2 = [&](int j, int col, const f32x4& acc) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int r = (((threadIdx.x & 63) >> 4) << 2) + i;
@@ -1386,12 +1481,16 @@ __device__ __forceinline__ void actor_split_body(const EngineDev* __restrict__ E
       if (act == ACT_RELU && !(P1[r * ldp1 + col] > 0.f)) v = 0.f;
       U1[r * ldu1 + col] = v;
     }
-  });
+  };
+  if (NCH_32 == 1 || np2 == KC)  // uniform: the chunks of dOut that hold data, one or (fp32, 2A > 16) two
+    gemm_hf<T, 1, 1, HH / 16>(goutB, ldo, 0, ht2, epi2);
+  else
+    gemm_hf<T, 1, NCH_32, HH / 16>(goutB, ldo, 0, ht2, epi2);
   if (act != ACT_RELU && act != ACT_ID) act_pass_bwd<R>(U1, ldu1, P1, ldp1, HH >> 4, HH, act);
   __syncthreads();
   store_T<T, R>(U1, ldu1, HH, HH, (T*)L1.GT + (size_t)h * HH * Bp, Bp, r0, nvalid, L1.dbp ? L1.dbp + h * HH : nullptr, nullptr, L1.N);
   // dY0 partial = act'(P0) * (dY1 W1[half])
-  gemm_hs<T, 2, NCH_HH, false>(U1, ldu1, wt1, &ht1, [&](int j, int col, const f32x4& acc) {
+  gemm_hf<T, 2, NCH_HH, NT_H>(U1, ldu1, 0, ht1, [&](int j, int col, const f32x4& acc) {
     const bool kv = col < L1.K;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
