@@ -195,9 +195,21 @@ __device__ __forceinline__ void gemm_hs(const lf* __restrict__ A, int lda, const
 // speed (profiles/ab_split_gemm_shapes_items.txt), so the source keeps chunk
 // order.  Each accumulator takes the products gemm_hs gives it, in gemm_hs's
 // order, and the tile is acc0 + acc1: the same bits.
-template <typename T, int NTW, int NCH, int NTC, int HC, typename Epi>
-__device__ __forceinline__ void gemm_hf(const lf* __restrict__ A, int lda, int nt, const HTiles<T, NTW, HC>& ht,
-                                        Epi&& epi) {
+//
+// MASK (the dX steps): the epilogue masks its tile by the pre-activations Pm
+// [R][ldpm] of the tile's own elements (ReLU: dX = 0 where !(p > 0)).  Nothing
+// the chain computes goes into them, so the lane's 4 rows of every tile are
+// read into registers right behind the A fragments, all reads in flight
+// together with theirs: one round trip in front of the chain (the order
+// matters: issued ahead of the A fragments the compiler waited for them
+// first); epi(j, col, acc, p) gets them.  Read in
+// the epilogue, each p sat between two stores into the same LDS, which a read
+// may not be moved across: one exposed round trip per element behind the chain.
+// Pm = null (uniform: a hidden activation without a mask, or one that
+// act_pass_bwd applies): nothing is read and p is not to be used.
+template <typename T, int NTW, int NCH, int NTC, bool MASK, int HC, typename Epi>
+__device__ __forceinline__ void gemm_hf_impl(const lf* __restrict__ A, int lda, int nt, const HTiles<T, NTW, HC>& ht,
+                                             const lf* Pm, int ldpm, Epi&& epi) {
   typedef typename MM<T>::Frag F;
   typedef MM<T> M;
   static_assert(NCH >= 1 && NCH <= HC, "every chunk of a fixed-shape step is held");
@@ -210,6 +222,22 @@ __device__ __forceinline__ void gemm_hf(const lf* __restrict__ A, int lda, int n
     constexpr int NJ = NTW;
     F a[NCH];
     static_for<NCH>([&](auto uc) { a[decltype(uc)::value] = M::from_lds(arow + decltype(uc)::value * M::KC); });
+    float pm[MASK ? NJ : 1][4];
+    if constexpr (MASK) {
+      static_for<NJ>([&](auto jc) {
+        constexpr int j = decltype(jc)::value;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) pm[j][i] = 0.f;
+      });
+      if (Pm) {  // uniform
+        const lf* prow = Pm + g * 4 * ldpm + wave * 16 + c;
+        static_for<NJ>([&](auto jc) {
+          constexpr int j = decltype(jc)::value;
+#pragma unroll
+          for (int i = 0; i < 4; ++i) pm[j][i] = prow[i * ldpm + j * SAC_NW * 16];
+        });
+      }
+    }
     f32x4 acc[NJ][2];
     static_for<NJ>([&](auto jc) { acc[decltype(jc)::value][0] = acc[decltype(jc)::value][1] = (f32x4){0.f, 0.f, 0.f, 0.f}; });
     static_for<NCH>([&](auto uc) {
@@ -221,10 +249,24 @@ __device__ __forceinline__ void gemm_hf(const lf* __restrict__ A, int lda, int n
     });
     static_for<NJ>([&](auto jc) {
       constexpr int j = decltype(jc)::value;
-      epi(j, (wave + j * SAC_NW) * 16 + c, acc[j][0] + acc[j][1]);
+      if constexpr (MASK)
+        epi(j, (wave + j * SAC_NW) * 16 + c, acc[j][0] + acc[j][1], pm[j]);
+      else
+        epi(j, (wave + j * SAC_NW) * 16 + c, acc[j][0] + acc[j][1]);
     });
   };
   if (own) chain();
+}
+template <typename T, int NTW, int NCH, int NTC, int HC, typename Epi>
+__device__ __forceinline__ void gemm_hf(const lf* __restrict__ A, int lda, int nt, const HTiles<T, NTW, HC>& ht,
+                                        Epi&& epi) {
+  gemm_hf_impl<T, NTW, NCH, NTC, false>(A, lda, nt, ht, nullptr, 0, epi);
+}
+// the masked form: epi(j, col, acc, p), p[i] = Pm[4 g + i][col] (valid when Pm != null)
+template <typename T, int NTW, int NCH, int NTC, int HC, typename Epi>
+__device__ __forceinline__ void gemm_hf(const lf* __restrict__ A, int lda, int nt, const HTiles<T, NTW, HC>& ht,
+                                        const lf* Pm, int ldpm, Epi&& epi) {
+  gemm_hf_impl<T, NTW, NCH, NTC, true>(A, lda, nt, ht, Pm, ldpm, epi);
 }
 
 // ---------------------------------------------------------------------------- k-split GEMM
@@ -410,6 +452,27 @@ __device__ __forceinline__ float rows16_sum(const float (&p)[4]) {
   v += __shfl_xor(v, 1, 64);
   v += __shfl_xor(v, 2, 64);
   return v;
+}
+
+// A descriptor value (a field of EngineDev / NetDev / LayerDev, or an address
+// made from some) taken HERE and kept in a scalar register from here on.  The
+// split kernels run at the SGPR limit, and a scalar load of read-only memory
+// is something the register allocator would rather repeat than keep: left to
+// itself it re-reads the field where it is used, a scalar-cache round trip
+// that nothing overlaps when the use sits behind a hand-off.  The value that
+// leaves the (empty) asm is no longer a load, so under pressure it is parked
+// in a VGPR lane and read back in a few cycles instead.
+template <typename V>
+__device__ __forceinline__ V keep_s(V x) {
+  asm volatile("" : "+s"(x));
+  return x;
+}
+// The same into a vector register: for an address that only ever goes into the
+// threads' own store addresses (nothing uniform is decided by it).
+template <typename V>
+__device__ __forceinline__ V keep_v(V x) {
+  asm volatile("" : "+v"(x));
+  return x;
 }
 
 // ---------------------------------------------------------------------------- phase A
@@ -972,13 +1035,15 @@ __device__ __forceinline__ void target_critic_split_body(const EngineDev* __rest
         }
         __syncthreads();
       }
-      gemm_hf<T, 2, NCH_HH, NT_H>(U1, ldu1, 0, ht1, [&](int j, int col, const f32x4& acc) {
+      const bool relu = net.hid_act == ACT_RELU;
+      gemm_hf<T, 2, NCH_HH, NT_H>(U1, ldu1, 0, ht1, relu ? P0 : nullptr, ldp0,
+                                  [&](int j, int col, const f32x4& acc, const float (&p)[4]) {
         const bool kv = col < L1.K;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const int r = (((threadIdx.x & 63) >> 4) << 2) + i;
           float v = kv ? acc[i] : 0.f;
-          if (net.hid_act == ACT_RELU && !(P0[r * ldp0 + col] > 0.f)) v = 0.f;
+          if (relu && !(p[i] > 0.f)) v = 0.f;
           Xb[r * ld + col] = v;  // U0 partial
         }
       });
@@ -1131,6 +1196,8 @@ __device__ __forceinline__ void actor_split_body(const EngineDev* __restrict__ E
     // ReLU / identity: the unit seed U1 = act'(P1) * W2 is written by layer 1's epilogue
     const bool mk_u1 = relu_id;
     const float w2n = mk_u1 ? 0.f : GPC(float, net.P + L2.w_off)[h * HQ + tid % HQ];
+    // this part's granules (partial da, partial q), for the end of the chain (keep_s)
+    AS_G uint64_t* const g = keep_s(gs_at(E, GS_C1 + qi, rbi, h));
     const int lane = tid & 63, wv = wave_id();
     float w2l = 0.f;
     // one thread per element of X when it fits: s / a~ go global -> register -> X, one barrier
@@ -1222,20 +1289,20 @@ __device__ __forceinline__ void actor_split_body(const EngineDev* __restrict__ E
         }
         __syncthreads();
       }
-      gemm_hf<T, 2, NCH_HQ, NT_H>(U1, ldu1, 0, ht1, [&](int j, int col, const f32x4& acc) {
-        const bool kv = col < L1.K;
+      const bool relu = act == ACT_RELU;
+      gemm_hf<T, 2, NCH_HQ, NT_H>(U1, ldu1, 0, ht1, relu ? P0 : nullptr, ldp0,
+                                  [&](int j, int col, const f32x4& acc, const float (&p)[4]) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
+        for (int i = 0; i < 4; ++i) {  // every column is one of layer 1's K = H inputs
           const int r = (((threadIdx.x & 63) >> 4) << 2) + i;
-          float v = kv ? acc[i] : 0.f;
-          if (act == ACT_RELU && !(P0[r * ldp0 + col] > 0.f)) v = 0.f;
+          float v = acc[i];
+          if (relu && !(p[i] > 0.f)) v = 0.f;
           Xb[r * ld + col] = v;
         }
       });
-      if (act != ACT_RELU && act != ACT_ID) act_pass_bwd<R>(Xb, ld, P0, ldp0, L1.Kp >> 4, L1.K, act);
+      if (act != ACT_RELU && act != ACT_ID) act_pass_bwd<R>(Xb, ld, P0, ldp0, SPLIT_H >> 4, SPLIT_H, act);
       __syncthreads();
       // dX of layer 0 for the action columns: the 16-row tiles of W0^T holding [O, O + A)
-      AS_G uint64_t* g = gs_at(E, GS_C1 + qi, rbi, h);
       // the partial dX0 [R][k1 - k0]: its action columns published by the threads that sum them
       auto epi_da = [&](int r, int col, float s) {
         const int j = col - (O - k0);
@@ -1298,10 +1365,25 @@ __device__ __forceinline__ void actor_split_body(const EngineDev* __restrict__ E
     for (int q = 0; q < 4; ++q) hsv[q] = ldf<false>(hs + q * A + tid % A);
   }
   const float bq1 = ldf<false>(E.net[NET_Q1].l[2].bias), bq2 = ldf<false>(E.net[NET_Q2].l[2].bias);
+  // What the chain from the critics' hand-off to the role's last store takes
+  // from the descriptors, taken before the poll (keep_s / keep_v).  The layer
+  // widths in that chain are the split's own: H for both hidden layers, and
+  // pi's dOut is L2.N = 2A <= 32 columns padded to SAC_PAD.
+  const int oa1 = keep_s(E.net[NET_Q1].out_act), oa2 = keep_s(E.net[NET_Q2].out_act);
+  const float scale = keep_s(E.scale);
+  float* const lossp = keep_v(E.lossp + (par * E.nrt + rbi) * 4 + 2);
+  void* const gt2 = keep_v(L2.GT);
+  float* const dbp2 = keep_s(L2.dbp);
+  void* const gt1 = keep_v((void*)((T*)L1.GT + (size_t)h * HH * Bp));
+  float* const dbp1 = keep_s(L1.dbp ? L1.dbp + h * HH : nullptr);
+  void* const gt0 = keep_v(L0.GT);
+  float* const dbp0 = keep_s(L0.dbp);
+  static_assert(SAC_PAD == 32, "pi's layer-2 width in the split kernels: 2A <= 32 padded to SAC_PAD");
   // Every term of the head backward (below) that does not depend on the critics'
   // da, computed while the role waits for them: the same operations in the
   // same order, only earlier.  hb_*: this thread's (row, action dim).
   float hb_omt = 0.f, hb_sp = 0.f, hb_gstd = 0.f, hb_gdiff = 0.f, hb_sd = 0.f;
+  bool hb_in_range = false;  // log sigma inside the clamp (its backward passes the gradient)
   if (tid < R * A) {
     const bool v = tid / A < nvalid;
     const float gl = v ? alpha32 * (1.0f / (float)B) : 0.f;
@@ -1320,6 +1402,7 @@ __device__ __forceinline__ void actor_split_body(const EngineDev* __restrict__ E
     hb_gstd = 2.f * sd * g_var - gl / sd;
     hb_gdiff = 2.f * diff * g_sq;
     hb_sd = sd;
+    hb_in_range = (lsr >= lo) && (lsr <= hi);
   }
   const int pad = np2 - 2 * A;  // dOut's padding columns that are multiplied
   for (int i = tid; i < R * pad; i += SAC_THREADS) goutB[(i / pad) * ldo + 2 * A + i % pad] = 0.f;
@@ -1357,8 +1440,6 @@ __device__ __forceinline__ void actor_split_body(const EngineDev* __restrict__ E
       float term = 0.f, w1 = 0.f, w2 = 0.f;
       if (tid < R) {
         const bool v = tid < nvalid;
-        const AS_C NetDev& q1n = E.net[NET_Q1];
-        const AS_C NetDev& q2n = E.net[NET_Q2];
         float q1p = gv[2 * WQ], q2p = gv[3 * WQ];
 #pragma unroll
         for (int p = 1; p < WQ; ++p) {
@@ -1367,18 +1448,18 @@ __device__ __forceinline__ void actor_split_body(const EngineDev* __restrict__ E
         }
         q1p += bq1;
         q2p += bq2;
-        const float q1 = q1n.out_act == ACT_ID ? q1p : act_fwd(q1n.out_act, q1p);
-        const float q2 = q2n.out_act == ACT_ID ? q2p : act_fwd(q2n.out_act, q2p);
+        const float q1 = oa1 == ACT_ID ? q1p : act_fwd(oa1, q1p);
+        const float q2 = oa2 == ACT_ID ? q2p : act_fwd(oa2, q2p);
         const float m = fmin_nan(q1, q2);
         term = v ? alpha32 * lpB[tid] - m : 0.f;
         const float gm = v ? -1.0f / (float)B : 0.f;
         w1 = (q1 == q2) ? gm * 0.5f : (q1 > q2 ? 0.f : gm);
         w2 = (q1 == q2) ? gm * 0.5f : (q1 < q2 ? 0.f : gm);
-        if (q1n.out_act != ACT_ID) w1 = act_bwd(q1n.out_act, q1p, w1);
-        if (q2n.out_act != ACT_ID) w2 = act_bwd(q2n.out_act, q2p, w2);
+        if (oa1 != ACT_ID) w1 = act_bwd(oa1, q1p, w1);
+        if (oa2 != ACT_ID) w2 = act_bwd(oa2, q2p, w2);
       }
       term = wave_sum(term);
-      if (tid == 0 && h == 0) st_f<false>(E.lossp + (par * E.nrt + rbi) * 4 + 2, term);
+      if (tid == 0 && h == 0) st_f<false>(lossp, term);
       const float w1r = __shfl(w1, r, 64), w2r = __shfl(w2, r, 64);
       if (live) {
         float da1 = gv[0], da2 = gv[WQ];
@@ -1395,8 +1476,6 @@ __device__ __forceinline__ void actor_split_body(const EngineDev* __restrict__ E
     float term = 0.f;
     if (tid < R) {
       const bool v = tid < nvalid;
-      const AS_C NetDev& q1n = E.net[NET_Q1];
-      const AS_C NetDev& q2n = E.net[NET_Q2];
       const AS_G uint64_t* gg[2 * WQ];
 #pragma unroll
       for (int p = 0; p < WQ; ++p) {
@@ -1413,20 +1492,20 @@ __device__ __forceinline__ void actor_split_body(const EngineDev* __restrict__ E
       }
       q1p += bq1;
       q2p += bq2;
-      const float q1 = q1n.out_act == ACT_ID ? q1p : act_fwd(q1n.out_act, q1p);
-      const float q2 = q2n.out_act == ACT_ID ? q2p : act_fwd(q2n.out_act, q2p);
+      const float q1 = oa1 == ACT_ID ? q1p : act_fwd(oa1, q1p);
+      const float q2 = oa2 == ACT_ID ? q2p : act_fwd(oa2, q2p);
       const float m = fmin_nan(q1, q2);
       term = v ? alpha32 * lpB[tid] - m : 0.f;
       const float gm = v ? -1.0f / (float)B : 0.f;
       float w1 = (q1 == q2) ? gm * 0.5f : (q1 > q2 ? 0.f : gm);
       float w2 = (q1 == q2) ? gm * 0.5f : (q1 < q2 ? 0.f : gm);
-      if (q1n.out_act != ACT_ID) w1 = act_bwd(q1n.out_act, q1p, w1);
-      if (q2n.out_act != ACT_ID) w2 = act_bwd(q2n.out_act, q2p, w2);
+      if (oa1 != ACT_ID) w1 = act_bwd(oa1, q1p, w1);
+      if (oa2 != ACT_ID) w2 = act_bwd(oa2, q2p, w2);
       g1B[tid] = w1;
       g2B[tid] = w2;
     }
     term = wave_sum(term);
-    if (tid == 0 && h == 0) st_f<false>(E.lossp + (par * E.nrt + rbi) * 4 + 2, term);
+    if (tid == 0 && h == 0) st_f<false>(lossp, term);
   }
   __syncthreads();
   for (int i = tid; i < R * A; i += SAC_THREADS) {
@@ -1455,8 +1534,7 @@ __device__ __forceinline__ void actor_split_body(const EngineDev* __restrict__ E
   if (tid < R * A) {  // only the terms that need the critics' da are left (hb_*: before the poll)
     const int r = tid / A, j = tid % A;
     const bool v = r < nvalid;
-    const float lo = E.ls_min, hi = E.ls_max, scale = E.scale;
-    const float lsr = hsv[1], e = hsv[3];
+    const float e = hsv[3];
     const float gav = R * A <= 64 ? ga : gaB[r * A + j];
     float g_z = (gav * scale) * hb_omt;
     g_z = g_z + hb_sp;
@@ -1464,45 +1542,45 @@ __device__ __forceinline__ void actor_split_body(const EngineDev* __restrict__ E
     const float g_mu = -hb_gdiff + g_z;
     const float g_std = hb_gstd + g_z * e;
     const float g_ls = g_std * hb_sd;
-    const bool in_range = (lsr >= lo) && (lsr <= hi);
     goutB[r * ldo + j] = v ? g_mu : 0.f;
-    goutB[r * ldo + A + j] = (v && in_range) ? g_ls : 0.f;
+    goutB[r * ldo + A + j] = (v && hb_in_range) ? g_ls : 0.f;
   }
   __syncthreads();
   // layer 2 dY^T (= dOut) + bias partials: half 0
-  if (h == 0) store_T<T, R>(goutB, ldo, L2.Np, L2.N, L2.GT, Bp, r0, nvalid, L2.dbp);
+  if (h == 0) store_T<T, R>(goutB, ldo, SAC_PAD, 2 * A, gt2, Bp, r0, nvalid, dbp2);
   // dY1 (this half) = act'(P1) * (dOut W2[:, half])
   const int act = pi.hid_act;
-  auto epi2 = [&](int j, int col, const f32x4& acc) {
+  const bool relu = act == ACT_RELU;  // the masks P1 / P0 go to registers ahead of each dX chain (gemm_hf)
+  auto epi2 = [&](int j, int col, const f32x4& acc, const float (&p)[4]) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int r = (((threadIdx.x & 63) >> 4) << 2) + i;
       float v = acc[i];
-      if (act == ACT_RELU && !(P1[r * ldp1 + col] > 0.f)) v = 0.f;
+      if (relu && !(p[i] > 0.f)) v = 0.f;
       U1[r * ldu1 + col] = v;
     }
   };
   if (NCH_32 == 1 || np2 == KC)  // uniform: the chunks of dOut that hold data, one or (fp32, 2A > 16) two
-    gemm_hf<T, 1, 1, HH / 16>(goutB, ldo, 0, ht2, epi2);
+    gemm_hf<T, 1, 1, HH / 16>(goutB, ldo, 0, ht2, relu ? P1 : nullptr, ldp1, epi2);
   else
-    gemm_hf<T, 1, NCH_32, HH / 16>(goutB, ldo, 0, ht2, epi2);
+    gemm_hf<T, 1, NCH_32, HH / 16>(goutB, ldo, 0, ht2, relu ? P1 : nullptr, ldp1, epi2);
   if (act != ACT_RELU && act != ACT_ID) act_pass_bwd<R>(U1, ldu1, P1, ldp1, HH >> 4, HH, act);
   __syncthreads();
-  store_T<T, R>(U1, ldu1, HH, HH, (T*)L1.GT + (size_t)h * HH * Bp, Bp, r0, nvalid, L1.dbp ? L1.dbp + h * HH : nullptr, nullptr, L1.N);
+  store_T<T, R>(U1, ldu1, HH, HH, gt1, Bp, r0, nvalid, dbp1, nullptr, SPLIT_H);
   // dY0 partial = act'(P0) * (dY1 W1[half])
-  gemm_hf<T, 2, NCH_HH, NT_H>(U1, ldu1, 0, ht1, [&](int j, int col, const f32x4& acc) {
-    const bool kv = col < L1.K;
+  gemm_hf<T, 2, NCH_HH, NT_H>(U1, ldu1, 0, ht1, relu ? P0 : nullptr, ldp0,
+                              [&](int j, int col, const f32x4& acc, const float (&p)[4]) {
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
+    for (int i = 0; i < 4; ++i) {  // every column is one of layer 1's K = H inputs
       const int r = (((threadIdx.x & 63) >> 4) << 2) + i;
-      float v = kv ? acc[i] : 0.f;
-      if (act == ACT_RELU && !(P0[r * ldp0 + col] > 0.f)) v = 0.f;
+      float v = acc[i];
+      if (relu && !(p[i] > 0.f)) v = 0.f;
       Xb[r * ld + col] = v;
     }
   });
-  if (act != ACT_RELU && act != ACT_ID) act_pass_bwd<R>(Xb, ld, P0, ldp0, L1.Kp >> 4, L1.K, act);
+  if (act != ACT_RELU && act != ACT_ID) act_pass_bwd<R>(Xb, ld, P0, ldp0, SPLIT_H >> 4, SPLIT_H, act);
   __syncthreads();
-  store_T<T, R>(Xb, ld, L0.Np, L0.N, L0.GT, WP * Bp, h * Bp + r0, nvalid, L0.dbp);
+  store_T<T, R>(Xb, ld, SPLIT_H, SPLIT_H, gt0, WP * Bp, h * Bp + r0, nvalid, dbp0);
   STAMP(35);
 }
 
