@@ -282,30 +282,57 @@ const char *sac_phase_kernel_name(int32_t phase);
  * RNG: which = 4, block 0 at vector step t gives the reset state an episode
  * truncated at t restarts from (t = 0: the initial reset; key = the environment
  * seed): th = pi (2 u0 - 1), thdot = 2 u1 - 1 in double, u0 / u1 the block's
- * first two uniforms.  Codes 4..7 are not assigned. */
+ * first two uniforms.  Codes 4..7 are not assigned.
+ *
+ * SAC_ENV_REACHER is the one kind with TWO action components: a planar two-link
+ * arm reaching for a target (sac/control_envs.py ReacherEnv; links L1 = L2 =
+ * 0.1, GAIN = 10, DAMP = 2, CTRL_COST = 0.1, target half side 0.14).  The joints
+ * are decoupled first-order rotors, all in float64: with u_j the j-th action
+ * clipped to [action_low, action_high], dx = (L1 cos th1 + L2 cos(th1 + th2)) -
+ * tx and dy the same with sin and ty, a step gives reward -sqrt(dx^2 + dy^2) -
+ * 0.1 (u0^2 + u1^2) of the PRE-step state, w_j' = w_j + (10 u_j - 2 w_j) dt,
+ * th_j' = th_j + w_j' dt; never terminated, truncated at max_steps.  The
+ * observation is fp32 (cos th1, cos th2, sin th1, sin th2, tx, ty, w1, w2, dx,
+ * dy) of the new state (obs_dim = 10).  State: sac_envs.pos is [4][num_envs]
+ * doubles (th1, th2, tx, ty; row-major by component), sac_envs.vel is
+ * [2][num_envs] doubles (w1, w2).  RNG: which = 4, block 0 at vector step t is
+ * the reset draw, its four uniforms exactly one block: tx = 0.14 (2 u0 - 1), ty
+ * = 0.14 (2 u1 - 1), th1 = pi (2 u2 - 1), th2 = pi (2 u3 - 1) in double, w = 0.
+ * Codes 9..15 are not assigned.
+ *
+ * Per-kind widths          actions  obs_dim   pos doubles / env   vel doubles / env
+ *   the probes (0..3)         1     1 (2: any)       1              - (may be NULL)
+ *   SAC_ENV_PENDULUM          1        3             1                    1
+ *   SAC_ENV_REACHER           2       10             4                    2         */
 enum sac_env_kind {
   SAC_ENV_CONSTANT_REWARD = 0,  /* envs.py ConstantRewardEnv: r = reward, terminated at max_steps */
   SAC_ENV_QUADRATIC_ACTION = 1, /* QuadraticActionRewardEnv: r = -(clip(a) - target)^2 in fp32 */
   SAC_ENV_RANDOM_OBS = 2,       /* RandomObsBinaryRewardEnv: uniform obs, r = +1 iff |a| <= threshold */
   SAC_ENV_POINT_MASS = 3,       /* OneDPointMassReachEnv: pos += clip(a) * dt, reach goal_pos */
-  SAC_ENV_PENDULUM = 8          /* control_envs.py PendulumEnv: swing-up, obs (cos th, sin th, thdot) */
+  SAC_ENV_PENDULUM = 8,         /* control_envs.py PendulumEnv: swing-up, obs (cos th, sin th, thdot) */
+  SAC_ENV_REACHER = 16          /* control_envs.py ReacherEnv: two-link arm, two torques, obs_dim 10 */
 };
+
+/* Action components an environment of `kind` takes: the act_dim its replay buffer and engine must have. */
+#define SAC_ENV_ACT_DIM(kind) ((kind) == SAC_ENV_REACHER ? 2 : 1)
 
 /* The constructor arguments of the sac/envs.py class of `kind` (the others are
  * ignored); action bounds are rounded to fp32 as its Box stores them. */
 typedef struct sac_env_config {
   int32_t kind;                 /* enum sac_env_kind */
   int32_t num_envs;
-  int32_t obs_dim;              /* 1, except SAC_ENV_RANDOM_OBS (its obs_dim argument) and SAC_ENV_PENDULUM (3) */
+  int32_t obs_dim;              /* 1, except SAC_ENV_RANDOM_OBS (its obs_dim argument), SAC_ENV_PENDULUM (3) and
+                                   SAC_ENV_REACHER (10) */
   int32_t max_steps;
   double reward;                              /* SAC_ENV_CONSTANT_REWARD */
   double target;                              /* SAC_ENV_QUADRATIC_ACTION */
-  double action_low, action_high;             /* SAC_ENV_QUADRATIC_ACTION, SAC_ENV_POINT_MASS, SAC_ENV_PENDULUM
-                                                 (-max_torque, max_torque) */
+  double action_low, action_high;             /* SAC_ENV_QUADRATIC_ACTION, SAC_ENV_POINT_MASS, SAC_ENV_PENDULUM and
+                                                 SAC_ENV_REACHER (-max_torque, max_torque; every component) */
   double threshold;                           /* SAC_ENV_RANDOM_OBS */
   double start_pos, goal_pos, dt, step_penalty, goal_reward, goal_tolerance;  /* SAC_ENV_POINT_MASS; dt also
-                                                                                 SAC_ENV_PENDULUM */
-  uint64_t seed;                /* observation draws of SAC_ENV_RANDOM_OBS, reset draws of SAC_ENV_PENDULUM */
+                                                                                 SAC_ENV_PENDULUM, SAC_ENV_REACHER */
+  uint64_t seed;                /* observation draws of SAC_ENV_RANDOM_OBS, reset draws of SAC_ENV_PENDULUM and
+                                   SAC_ENV_REACHER */
 } sac_env_config;
 
 /* One cell of the episode record: written by every environment on every step. */
@@ -321,21 +348,23 @@ typedef struct sac_envs {
   float *obs;                   /* [num_envs][obs_dim] current observations */
   int32_t *step;                /* [num_envs] step in the episode (envs.py current_step) */
   int32_t *ep_length;           /* [num_envs] length of the running episode */
-  double *pos;                  /* [num_envs] SAC_ENV_POINT_MASS position; SAC_ENV_PENDULUM angle th */
+  double *pos;                  /* [num_envs] SAC_ENV_POINT_MASS position; SAC_ENV_PENDULUM angle th;
+                                   SAC_ENV_REACHER [4][num_envs]: th1, th2, tx, ty */
   double *ep_return;            /* [num_envs] return of the running episode */
   sac_env_episode *episodes;    /* [ring_steps][num_envs] dense ring indexed by t % ring_steps and env row;
                                    NULL: no record (sac_envs_step only) */
   int64_t ring_steps;
-  double *vel;                  /* [num_envs] SAC_ENV_PENDULUM angular velocity thdot; may be NULL for the probes */
+  double *vel;                  /* [num_envs] SAC_ENV_PENDULUM angular velocity thdot; SAC_ENV_REACHER
+                                   [2][num_envs]: w1, w2; may be NULL for the probes */
 } sac_envs;
 
 /* Reset every environment: step and episode counters to 0, the initial
- * observation (draws of SAC_ENV_RANDOM_OBS and SAC_ENV_PENDULUM: which = 4, t = 0,
- * key `seed`).
+ * observation (draws of SAC_ENV_RANDOM_OBS, SAC_ENV_PENDULUM and SAC_ENV_REACHER:
+ * which = 4, t = 0, key `seed`).
  * Replaces: SyncVectorEnv.reset (sac/vector_env.py:39-46). */
 int sac_envs_reset(const sac_envs *envs, uint64_t seed, void *stream);
 
-/* Vector step t (>= 1) with the caller's actions [num_envs][1]: obs
+/* Vector step t (>= 1) with the caller's actions [num_envs][SAC_ENV_ACT_DIM(kind)]: obs
  * [num_envs][obs_dim] (after autoreset), final_obs [num_envs][obs_dim] (the
  * true next state of every environment), reward [num_envs] fp32, terminated /
  * truncated [num_envs] bytes (0 / 1).

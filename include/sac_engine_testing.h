@@ -57,6 +57,9 @@ int sac_engine_debug_set_spin_limit(sac_engine *e, int32_t polls, void *stream);
  * action dims j < act_dim.  Counter (t, i, 2 << 16 | j / 2), key seed (the
  * engine's); Box-Muller gives dims 2p and 2p + 1. */
 int sac_debug_rollout_eps_host(uint64_t seed, uint64_t t, int32_t n, int32_t act_dim, float *out);
+/* The same draws computed on the device (out: device [n][act_dim]), with the
+ * device library's logf / sincosf: what the fused step adds to mu, to the bit. */
+int sac_debug_rollout_eps_device(uint64_t seed, uint64_t t, int32_t n, int32_t act_dim, float *out, void *stream);
 /* Host evaluation of the observation draws of SAC_ENV_RANDOM_OBS (the same
  * inline code as the device's): out[i][k], env rows i < n, k < obs_dim, for
  * which = 3 (the observation stepped to at t) or 4 (the reset observation at
@@ -77,6 +80,22 @@ int sac_debug_env_step_host(const sac_env_config *cfg, double state[2], int32_t 
  * as the device's, state_out = {pi (2 u0 - 1), 2 u1 - 1} with u0, u1 the first
  * two uniforms of sac_debug_env_obs_host's which = 4 block 0. */
 int sac_debug_env_reset_host(uint64_t seed, uint64_t t, int32_t row, double state_out[2]);
+/* One step of SAC_ENV_REACHER on the host: the inline dynamics the device
+ * kernels call (csrc/sac_envs.h reacher_dynamics), compiled for the host, so
+ * sin / cos / sqrt are the host libm's.  cfg supplies action_low, action_high,
+ * dt and max_steps (kind must be SAC_ENV_REACHER); state = (th1, th2, w1, w2,
+ * tx, ty), the order of ReacherEnv.state, is advanced in place; `step` is the
+ * step in the episode before this one.  Outputs: the observation stepped to,
+ * the reward of the pre-step state, truncated = step + 1 >= max_steps.  No
+ * autoreset: the caller applies the reset draw below. */
+int sac_debug_reacher_step_host(const sac_env_config *cfg, double state[6], int32_t step, const float action[2],
+                                float obs_out[10], double *reward, int32_t *truncated);
+/* The reset state of SAC_ENV_REACHER row `row` at vector step t (t = 0: the
+ * initial reset) for environment seed `seed`, in the same order: the same
+ * inline code as the device's, (th1, th2) = pi (2 u - 1) of the third and
+ * fourth uniform of sac_debug_env_obs_host's which = 4 block 0, w1 = w2 = 0,
+ * (tx, ty) = 0.14 (2 u - 1) of its first and second. */
+int sac_debug_reacher_reset_host(uint64_t seed, uint64_t t, int32_t row, double state_out[6]);
 /* A host-only engine: the validated config and no device state (no HIP call is
  * made).  For the argument checks of the forward-only entry points --
  * sac_q_values, sac_q_values_replay, sac_policy_act and sac_rollout_step -- on

@@ -321,6 +321,20 @@ static int validate(const sac_engine_config* c) {
   return SAC_OK;
 }
 
+// The rollout kernels' instantiation for a kind class (sac_envs.h EnvClass)
+template <typename T>
+static auto rollout_kernel(int kc) {
+  return kc == ENV_CLASS_REACHER    ? sac_rollout_step_kernel<T, ENV_CLASS_REACHER>
+         : kc == ENV_CLASS_PENDULUM ? sac_rollout_step_kernel<T, ENV_CLASS_PENDULUM>
+                                    : sac_rollout_step_kernel<T, ENV_CLASS_PROBES>;
+}
+template <typename T>
+static auto rollout_dev_kernel(int kc) {
+  return kc == ENV_CLASS_REACHER    ? sac_rollout_step_dev_kernel<T, ENV_CLASS_REACHER>
+         : kc == ENV_CLASS_PENDULUM ? sac_rollout_step_dev_kernel<T, ENV_CLASS_PENDULUM>
+                                    : sac_rollout_step_dev_kernel<T, ENV_CLASS_PROBES>;
+}
+
 template <typename T>
 static void set_lds_attrs(size_t bytes) {
   (void)bytes;
@@ -330,12 +344,10 @@ static void set_lds_attrs(size_t bytes) {
   (void)hipFuncSetAttribute((const void*)sac_actor<T, false>, hipFuncAttributeMaxDynamicSharedMemorySize, b);
   (void)hipFuncSetAttribute((const void*)sac_actor<T, true>, hipFuncAttributeMaxDynamicSharedMemorySize, b);
   (void)hipFuncSetAttribute((const void*)sac_policy_act_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, b);
-  (void)hipFuncSetAttribute((const void*)sac_rollout_step_kernel<T, false>, hipFuncAttributeMaxDynamicSharedMemorySize, b);
-  (void)hipFuncSetAttribute((const void*)sac_rollout_step_kernel<T, true>, hipFuncAttributeMaxDynamicSharedMemorySize, b);
-  (void)hipFuncSetAttribute((const void*)sac_rollout_step_dev_kernel<T, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            b);
-  (void)hipFuncSetAttribute((const void*)sac_rollout_step_dev_kernel<T, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            b);
+  for (int kc = ENV_CLASS_PROBES; kc <= ENV_CLASS_REACHER; ++kc) {
+    (void)hipFuncSetAttribute((const void*)rollout_kernel<T>(kc), hipFuncAttributeMaxDynamicSharedMemorySize, b);
+    (void)hipFuncSetAttribute((const void*)rollout_dev_kernel<T>(kc), hipFuncAttributeMaxDynamicSharedMemorySize, b);
+  }
   (void)hipFuncSetAttribute((const void*)sac_q_values_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, b);
   (void)hipFuncSetAttribute((const void*)sac_target_critic_split<T>, hipFuncAttributeMaxDynamicSharedMemorySize, b);
   (void)hipFuncSetAttribute((const void*)sac_target_critic_pairs<T>, hipFuncAttributeMaxDynamicSharedMemorySize, b);
@@ -500,16 +512,19 @@ static int check_replay(sac_engine* e, const sac_replay* rb) {
 static int check_envs(const sac_envs* ev, bool need_ring) {
   if (!ev) return fail(SAC_E_INVALID, "null environments");
   const sac_env_config& c = ev->cfg;
-  const bool pendulum = c.kind == SAC_ENV_PENDULUM;
-  if ((c.kind < SAC_ENV_CONSTANT_REWARD || c.kind > SAC_ENV_POINT_MASS) && !pendulum)
+  const bool pendulum = c.kind == SAC_ENV_PENDULUM, reacher = c.kind == SAC_ENV_REACHER;
+  if ((c.kind < SAC_ENV_CONSTANT_REWARD || c.kind > SAC_ENV_POINT_MASS) && !pendulum && !reacher)
     return fail(SAC_E_INVALID, "unknown environment kind " + std::to_string(c.kind));
   if (c.num_envs < 1) return fail(SAC_E_INVALID, "num_envs >= 1");
   if (c.max_steps < 1) return fail(SAC_E_INVALID, "max_steps >= 1");
   if (pendulum && c.obs_dim != SAC_PENDULUM_OBS_DIM)
     return fail(SAC_E_INVALID, "obs_dim must be 3 for SAC_ENV_PENDULUM");
-  if (!pendulum && (c.kind == SAC_ENV_RANDOM_OBS ? (c.obs_dim < 1 || c.obs_dim > 4 * 65536) : c.obs_dim != 1))
+  if (reacher && c.obs_dim != SAC_REACHER_OBS_DIM)
+    return fail(SAC_E_INVALID, "obs_dim must be 10 for SAC_ENV_REACHER");
+  if (!pendulum && !reacher && (c.kind == SAC_ENV_RANDOM_OBS ? (c.obs_dim < 1 || c.obs_dim > 4 * 65536) : c.obs_dim != 1))
     return fail(SAC_E_INVALID, "obs_dim must be 1 (SAC_ENV_RANDOM_OBS: 1..262144)");
-  if (!ev->obs || !ev->step || !ev->ep_length || !ev->pos || !ev->ep_return || (pendulum && !ev->vel))
+  if (!ev->obs || !ev->step || !ev->ep_length || !ev->pos || !ev->ep_return ||
+      ((pendulum || reacher) && !ev->vel))
     return fail(SAC_E_INVALID, "null environment state");
   if (need_ring ? (!ev->episodes || ev->ring_steps < 1) : (ev->episodes && ev->ring_steps < 1))
     return fail(SAC_E_INVALID, "episode ring needs episodes != NULL and ring_steps >= 1");
@@ -900,11 +915,12 @@ static int check_rollout_buffers(const sac_envs* envs, const sac_replay* rb) {
 }
 // ... and replay, environments and engine of one shape, on an engine that can run the policy's forward.
 static int check_rollout_dims(const sac_engine* e, const sac_envs* envs, const sac_replay* rb, const char* who) {
-  if (rb->obs_dim != envs->cfg.obs_dim || rb->act_dim != SAC_ENV_ACT_DIM)
-    return fail(SAC_E_INVALID, "replay dims do not match the environments (act_dim 1)");
+  const int A = env_act_dim(envs->cfg.kind);
+  if (rb->obs_dim != envs->cfg.obs_dim || rb->act_dim != A)
+    return fail(SAC_E_INVALID, "replay dims do not match the environments (act_dim " + std::to_string(A) + ")");
   if (!e) return fail(SAC_E_INVALID, "null engine");
-  if (e->cfg.obs_dim != envs->cfg.obs_dim || e->cfg.act_dim != SAC_ENV_ACT_DIM)
-    return fail(SAC_E_INVALID, "engine dims do not match the environments (act_dim 1)");
+  if (e->cfg.obs_dim != envs->cfg.obs_dim || e->cfg.act_dim != A)
+    return fail(SAC_E_INVALID, "engine dims do not match the environments (act_dim " + std::to_string(A) + ")");
   return check_policy_forward(e, who);
 }
 
@@ -921,9 +937,8 @@ int sac_rollout_step(sac_engine* e, const sac_envs* envs, const sac_replay* rb, 
   const int64_t new_pos = (pos_host + n) % cap;
   const int blocks = (int)((n + SAC_ROWS - 1) / SAC_ROWS);
   hipStream_t s = (hipStream_t)stream;
-  const bool bf = e->cfg.precision == SAC_PREC_BF16, pendulum = envs->cfg.kind == SAC_ENV_PENDULUM;
-  auto kernel = bf ? (pendulum ? sac_rollout_step_kernel<bf16, true> : sac_rollout_step_kernel<bf16, false>)
-                   : (pendulum ? sac_rollout_step_kernel<float, true> : sac_rollout_step_kernel<float, false>);
+  const int kc = env_class(envs->cfg.kind);
+  auto kernel = e->cfg.precision == SAC_PREC_BF16 ? rollout_kernel<bf16>(kc) : rollout_kernel<float>(kc);
   kernel<<<blocks, SAC_THREADS, e->lds_bytes, s>>>(e->d, *envs, *rb, pos_host, new_size, new_pos, t, deterministic ? 1 : 0,
                                                    store ? 1 : 0);
   HIPCHK(hipGetLastError());
@@ -936,9 +951,8 @@ static int launch_rollout_dev(sac_engine* e, const sac_envs* envs, const sac_rep
   const int blocks = (envs->cfg.num_envs + SAC_ROWS - 1) / SAC_ROWS;
   const int64_t* cur = cursor + 4 * parity;
   int64_t* nxt = cursor + 4 * (parity ^ 1);
-  const bool bf = e->cfg.precision == SAC_PREC_BF16, pendulum = envs->cfg.kind == SAC_ENV_PENDULUM;
-  auto kernel = bf ? (pendulum ? sac_rollout_step_dev_kernel<bf16, true> : sac_rollout_step_dev_kernel<bf16, false>)
-                   : (pendulum ? sac_rollout_step_dev_kernel<float, true> : sac_rollout_step_dev_kernel<float, false>);
+  const int kc = env_class(envs->cfg.kind);
+  auto kernel = e->cfg.precision == SAC_PREC_BF16 ? rollout_dev_kernel<bf16>(kc) : rollout_dev_kernel<float>(kc);
   kernel<<<blocks, SAC_THREADS, e->lds_bytes, s>>>(e->d, *envs, *rb, cur, nxt, deterministic, store);
   HIPCHK(hipGetLastError());
   return SAC_OK;
@@ -1035,6 +1049,26 @@ int sac_debug_rollout_eps_host(uint64_t seed, uint64_t t, int32_t n, int32_t act
   return SAC_OK;
 }
 
+// The rollout step's action noise as its row owners draw it, one thread per (env row, action pair)
+__global__ void rollout_eps_kernel(uint64_t seed, uint64_t t, int n, int A, float* __restrict__ out) {
+  const int NP = (A + 1) / 2;
+  const int64_t k = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (k >= (int64_t)n * NP) return;
+  const int i = (int)(k / NP), p = (int)(k % NP);
+  float n0, n1;
+  philox_normal2(seed, t, (uint32_t)i, ENV_WHICH_NOISE, (uint32_t)p, n0, n1);
+  out[(size_t)i * A + 2 * p] = n0;
+  if (2 * p + 1 < A) out[(size_t)i * A + 2 * p + 1] = n1;
+}
+
+int sac_debug_rollout_eps_device(uint64_t seed, uint64_t t, int32_t n, int32_t act_dim, float* out, void* stream) {
+  if (!out || n < 1 || act_dim < 1) return fail(SAC_E_INVALID, "need n >= 1, act_dim >= 1, out != NULL");
+  const int64_t work = (int64_t)n * ((act_dim + 1) / 2);
+  rollout_eps_kernel<<<(unsigned)((work + 255) / 256), 256, 0, (hipStream_t)stream>>>(seed, t, n, act_dim, out);
+  HIPCHK(hipGetLastError());
+  return SAC_OK;
+}
+
 int sac_debug_env_obs_host(uint64_t seed, uint64_t t, int32_t which, int32_t n, int32_t obs_dim, float* out) {
   if (!out || n < 1 || obs_dim < 1 || obs_dim > 4 * 65536 || which < 0 || which > 0xFFFF)
     return fail(SAC_E_INVALID, "need n >= 1, 1 <= obs_dim <= 262144, 0 <= which < 65536, out != NULL");
@@ -1061,6 +1095,23 @@ int sac_debug_env_step_host(const sac_env_config* cfg, double state[2], int32_t 
 int sac_debug_env_reset_host(uint64_t seed, uint64_t t, int32_t row, double state_out[2]) {
   if (!state_out || row < 0) return fail(SAC_E_INVALID, "need row >= 0 and state_out != NULL");
   pendulum_reset_draw(seed, t, (uint32_t)row, state_out[0], state_out[1]);
+  return SAC_OK;
+}
+
+int sac_debug_reacher_step_host(const sac_env_config* cfg, double state[6], int32_t step, const float action[2],
+                                float obs_out[10], double* reward, int32_t* truncated) {
+  if (!cfg || !state || !action || !obs_out || !reward || !truncated)
+    return fail(SAC_E_INVALID, "need cfg, state, action, obs_out, reward and truncated != NULL");
+  if (cfg->kind != SAC_ENV_REACHER) return fail(SAC_E_INVALID, "reacher_step_host: kind must be SAC_ENV_REACHER");
+  if (cfg->max_steps < 1 || step < 0) return fail(SAC_E_INVALID, "reacher_step_host: max_steps >= 1 and step >= 0");
+  *reward = reacher_dynamics(state, action[0], action[1], cfg->action_low, cfg->action_high, cfg->dt, obs_out);
+  *truncated = step + 1 >= cfg->max_steps ? 1 : 0;
+  return SAC_OK;
+}
+
+int sac_debug_reacher_reset_host(uint64_t seed, uint64_t t, int32_t row, double state_out[6]) {
+  if (!state_out || row < 0) return fail(SAC_E_INVALID, "need row >= 0 and state_out != NULL");
+  reacher_reset_draw(seed, t, (uint32_t)row, state_out);
   return SAC_OK;
 }
 

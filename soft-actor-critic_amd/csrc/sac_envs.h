@@ -1,20 +1,22 @@
 // sac_envs.h — the probe environments of sac/envs.py and the Pendulum swing-up
-// of sac/control_envs.py on the device, and the fused rollout step (act -> step
-// -> store in one launch).
+// and two-link reacher of sac/control_envs.py on the device, and the fused
+// rollout step (act -> step -> store in one launch).
 //
 //   * pendulum_dynamics: one step of the swing-up in float64, host-callable;
+//   * reacher_dynamics: one step of the reacher (two action components), likewise;
 //   * env_step: ONE statement of the environments' dynamics, with the semantics
 //     sac.vector_env.SyncVectorEnv gives the host classes (same-step autoreset;
 //     the transition is (obs, action, reward, final_obs, terminated | truncated)).
 //     Whatever sac/envs.py keeps as a Python float is a double here, so the
 //     fp32-rounded observations and rewards are the host's bit for bit;
 //   * sac_envs_step_kernel: N environments stepped with the caller's actions;
-//   * sac_rollout_step_kernel<T, PENDULUM>: sibling of sac_policy_act_kernel<T>
+//   * sac_rollout_step_kernel<T, KC>: sibling of sac_policy_act_kernel<T>
 //     (same workgroup shape, LDS layout and mlp_forward call); the thread that
 //     owns environment row i samples its action, steps the environment and
-//     writes the transition into the replay ring.  Compiled once for the probes
-//     and once for the pendulum; the host picks by the environments' kind;
-//   * sac_rollout_step_dev_kernel<T, PENDULUM>: the same body with (size, pos,
+//     writes the transition into the replay ring.  Compiled once per kind class
+//     KC (the probes, the pendulum, the reacher); the host picks by the
+//     environments' kind;
+//   * sac_rollout_step_dev_kernel<T, KC>: the same body with (size, pos,
 //     t) read from a two-slot cursor in device memory, so whole loop iterations
 //     replay from one hipGraph (sac_engine_loop_graph).
 //
@@ -26,8 +28,14 @@
 #include "../../include/sac_engine.h"
 #include "sac_phases.h"
 
-// Action components the probes take (envs.py: every action_space has shape (1,)).
-#define SAC_ENV_ACT_DIM 1
+// Action components an environment of `kind` takes: 1 (envs.py: every probe's action_space has shape
+// (1,), and so has the pendulum's) except the reacher's 2.
+__host__ __device__ inline int env_act_dim(int kind) { return SAC_ENV_ACT_DIM(kind); }
+// The rollout kernels are compiled once per kind class, so no class holds another's code.
+enum EnvClass { ENV_CLASS_PROBES = 0, ENV_CLASS_PENDULUM = 1, ENV_CLASS_REACHER = 2 };
+inline int env_class(int kind) {
+  return kind == SAC_ENV_PENDULUM ? ENV_CLASS_PENDULUM : (kind == SAC_ENV_REACHER ? ENV_CLASS_REACHER : ENV_CLASS_PROBES);
+}
 // Philox `which` values of the rollout (0 / 1 are the training draws)
 #define ENV_WHICH_NOISE 2u  // action noise of a rollout step, key = engine seed
 #define ENV_WHICH_STEP 3u   // observation an environment steps to at t, key = env seed
@@ -96,6 +104,91 @@ __host__ __device__ inline void pendulum_reset_draw(uint64_t seed, uint64_t t, u
   thdot = 2.0 * (double)u[1] - 1.0;
 }
 
+// ---- Two-link reacher (sac/control_envs.py ReacherEnv) ----------------------
+// State s = (th1, th2, w1, w2, tx, ty) in float64, the order of ReacherEnv.state.
+// Sine and cosine enter the reward and the observation only, never the state:
+// the state trajectory is the host's bit for bit whatever library they come from.
+#define SAC_REACHER_OBS_DIM 10
+#define SAC_REACHER_L1 0.1
+#define SAC_REACHER_L2 0.1
+#define SAC_REACHER_GAIN 10.0
+#define SAC_REACHER_DAMP 2.0
+#define SAC_REACHER_CTRL_COST 0.1
+#define SAC_REACHER_TARGET_HALF_SIDE 0.14
+
+// Fingertip minus target
+__host__ __device__ inline void reacher_tip(const double s[6], double& dx, double& dy) {
+  dx = (SAC_REACHER_L1 * cos(s[0]) + SAC_REACHER_L2 * cos(s[0] + s[1])) - s[4];
+  dy = (SAC_REACHER_L1 * sin(s[0]) + SAC_REACHER_L2 * sin(s[0] + s[1])) - s[5];
+}
+
+// The observation of a state, in fp32
+__host__ __device__ inline void reacher_obs(const double s[6], float obs[SAC_REACHER_OBS_DIM]) {
+  double dx, dy;
+  reacher_tip(s, dx, dy);
+  obs[0] = (float)cos(s[0]);
+  obs[1] = (float)cos(s[1]);
+  obs[2] = (float)sin(s[0]);
+  obs[3] = (float)sin(s[1]);
+  obs[4] = (float)s[4];
+  obs[5] = (float)s[5];
+  obs[6] = (float)s[2];
+  obs[7] = (float)s[3];
+  obs[8] = (float)dx;
+  obs[9] = (float)dy;
+}
+
+// One step from s with actions (a0, a1): the reward of the PRE-step state, the
+// new state in place and its observation in fp32.
+__host__ __device__ inline double reacher_dynamics(double s[6], float a0, float a1, double action_low,
+                                                   double action_high, double dt, float obs[SAC_REACHER_OBS_DIM]) {
+  const double u0 = (double)clip_f32(a0, (float)action_low, (float)action_high);
+  const double u1 = (double)clip_f32(a1, (float)action_low, (float)action_high);
+  double dx, dy;
+  reacher_tip(s, dx, dy);
+  const double reward = -sqrt(dx * dx + dy * dy) - SAC_REACHER_CTRL_COST * (u0 * u0 + u1 * u1);
+  s[2] = s[2] + (SAC_REACHER_GAIN * u0 - SAC_REACHER_DAMP * s[2]) * dt;
+  s[3] = s[3] + (SAC_REACHER_GAIN * u1 - SAC_REACHER_DAMP * s[3]) * dt;
+  s[0] = s[0] + s[2] * dt;
+  s[1] = s[1] + s[3] * dt;
+  reacher_obs(s, obs);
+  return reward;
+}
+
+// The reset draw of env row `row` at vector step t: the four uniforms of the
+// row's ENV_WHICH_RESET block 0 give the target in the square of half side 0.14
+// and both angles in [-pi, pi); the arm starts at rest.
+__host__ __device__ inline void reacher_reset_draw(uint64_t seed, uint64_t t, uint32_t row, double s[6]) {
+  float u[4];
+  philox_uniform4(seed, t, row, ENV_WHICH_RESET, 0, u);
+  s[4] = SAC_REACHER_TARGET_HALF_SIDE * (2.0 * (double)u[0] - 1.0);
+  s[5] = SAC_REACHER_TARGET_HALF_SIDE * (2.0 * (double)u[1] - 1.0);
+  s[0] = SAC_PI * (2.0 * (double)u[2] - 1.0);
+  s[1] = SAC_PI * (2.0 * (double)u[3] - 1.0);
+  s[2] = 0.0;
+  s[3] = 0.0;
+}
+
+// Row i's state in the component-major blocks ev.pos [4][N] (th1, th2, tx, ty) and ev.vel [2][N] (w1, w2)
+__device__ __forceinline__ void reacher_load(const sac_envs& ev, int i, double s[6]) {
+  const size_t n = (size_t)ev.cfg.num_envs;
+  s[0] = ev.pos[i];
+  s[1] = ev.pos[n + i];
+  s[2] = ev.vel[i];
+  s[3] = ev.vel[n + i];
+  s[4] = ev.pos[2 * n + i];
+  s[5] = ev.pos[3 * n + i];
+}
+__device__ __forceinline__ void reacher_store(const sac_envs& ev, int i, const double s[6]) {
+  const size_t n = (size_t)ev.cfg.num_envs;
+  ev.pos[i] = s[0];
+  ev.pos[n + i] = s[1];
+  ev.vel[i] = s[2];
+  ev.vel[n + i] = s[3];
+  ev.pos[2 * n + i] = s[4];
+  ev.pos[3 * n + i] = s[5];
+}
+
 struct EnvOut {
   double reward;  // as the host class returns it (probe 1's fp32 reward widened, as float(r) does)
   bool terminated, truncated;
@@ -130,16 +223,46 @@ __device__ __forceinline__ EnvOut env_step_pendulum(const sac_envs& ev, int i, u
   return o;
 }
 
+// The reacher's step of env_step: as the pendulum's, with two action components, ten observation
+// components and the state of reacher_load.
+__device__ __forceinline__ EnvOut env_step_reacher(const sac_envs& ev, int i, uint64_t t, float a0, float a1,
+                                                   float* final_obs) {
+  const sac_env_config& c = ev.cfg;
+  const int step = ev.step[i] + 1;
+  float* cur = ev.obs + (size_t)i * SAC_REACHER_OBS_DIM;
+  double s[6];
+  reacher_load(ev, i, s);
+  float fo[SAC_REACHER_OBS_DIM];
+  EnvOut o;
+  o.reward = reacher_dynamics(s, a0, a1, c.action_low, c.action_high, c.dt, fo);
+  o.terminated = false;
+  o.truncated = step >= c.max_steps;
+  if (final_obs)
+    for (int k = 0; k < SAC_REACHER_OBS_DIM; ++k) final_obs[k] = fo[k];
+  if (o.truncated) {
+    reacher_reset_draw(c.seed, t, (uint32_t)i, s);
+    reacher_obs(s, fo);
+  }
+  for (int k = 0; k < SAC_REACHER_OBS_DIM; ++k) cur[k] = fo[k];
+  ev.step[i] = o.truncated ? 0 : step;
+  reacher_store(ev, i, s);
+  return o;
+}
+
 // One step of environment row i at vector step t with the action's first
-// component.  Writes the observation stepped to into final_obs[obs_dim] (unless
-// NULL), the environment's new current observation (the reset observation where
-// the episode ended) into ev.obs, and its step counter / position.
-// PENDULUM is the kind, decided by the launch: the rollout kernels are compiled
-// once per side, so the probes' kernels hold none of the pendulum's code (behind
-// a run-time branch it cost them 16 more spilled SGPRs and 1-2 % per launch).
-template <bool PENDULUM>
-__device__ __forceinline__ EnvOut env_step(const sac_envs& ev, int i, uint64_t t, float action, float* final_obs) {
-  if (PENDULUM) return env_step_pendulum(ev, i, t, action, final_obs);
+// component `action` (and its second, a1, for the one kind that takes two).
+// Writes the observation stepped to into final_obs[obs_dim] (unless NULL), the
+// environment's new current observation (the reset observation where the
+// episode ended) into ev.obs, and its step counter / position.
+// KC is the kind class (EnvClass), decided by the launch: the rollout kernels are
+// compiled once per class, so the probes' kernels hold none of the pendulum's or
+// the reacher's code (behind a run-time branch the pendulum cost them 16 more
+// spilled SGPRs and 1-2 % per launch).
+template <int KC>
+__device__ __forceinline__ EnvOut env_step(const sac_envs& ev, int i, uint64_t t, float action, float a1,
+                                           float* final_obs) {
+  if (KC == ENV_CLASS_PENDULUM) return env_step_pendulum(ev, i, t, action, final_obs);
+  if (KC == ENV_CLASS_REACHER) return env_step_reacher(ev, i, t, action, a1, final_obs);
   const sac_env_config& c = ev.cfg;
   const int O = c.obs_dim;
   const int step = ev.step[i] + 1;
@@ -233,12 +356,17 @@ __global__ void sac_envs_reset_kernel(sac_envs ev, uint64_t seed) {
       for (int k = 0; k < 4; ++k)
         if (4 * b + k < O) cur[4 * b + k] = env_uniform_obs(u[k]);
     }
-  } else if (c.kind != SAC_ENV_PENDULUM) {
+  } else if (c.kind != SAC_ENV_PENDULUM && c.kind != SAC_ENV_REACHER) {
     cur[0] = c.kind == SAC_ENV_POINT_MASS ? (float)c.start_pos : 0.f;
   }
   ev.step[i] = 0;
   ev.ep_length[i] = 0;
-  if (c.kind == SAC_ENV_PENDULUM) {
+  if (c.kind == SAC_ENV_REACHER) {
+    double s[6];
+    reacher_reset_draw(seed, 0, (uint32_t)i, s);
+    reacher_obs(s, cur);
+    reacher_store(ev, i, s);
+  } else if (c.kind == SAC_ENV_PENDULUM) {
     double th, thdot;
     pendulum_reset_draw(seed, 0, (uint32_t)i, th, thdot);
     pendulum_obs(th, thdot, cur);
@@ -257,9 +385,16 @@ __global__ void sac_envs_step_kernel(sac_envs ev, const float* __restrict__ acti
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= ev.cfg.num_envs) return;
   const int O = ev.cfg.obs_dim;
-  const float a = actions[(size_t)i * SAC_ENV_ACT_DIM];
-  const EnvOut o = ev.cfg.kind == SAC_ENV_PENDULUM ? env_step<true>(ev, i, t, a, final_obs + (size_t)i * O)
-                                                   : env_step<false>(ev, i, t, a, final_obs + (size_t)i * O);
+  const int A = env_act_dim(ev.cfg.kind);
+  const float a = actions[(size_t)i * A];
+  float* fin = final_obs + (size_t)i * O;
+  EnvOut o;
+  if (ev.cfg.kind == SAC_ENV_REACHER)
+    o = env_step<ENV_CLASS_REACHER>(ev, i, t, a, actions[(size_t)i * A + 1], fin);
+  else if (ev.cfg.kind == SAC_ENV_PENDULUM)
+    o = env_step<ENV_CLASS_PENDULUM>(ev, i, t, a, 0.f, fin);
+  else
+    o = env_step<ENV_CLASS_PROBES>(ev, i, t, a, 0.f, fin);
   env_account(ev, i, t, o);
   for (int k = 0; k < O; ++k) obs[(size_t)i * O + k] = ev.obs[(size_t)i * O + k];
   reward[i] = (float)o.reward;
@@ -272,7 +407,7 @@ __global__ void sac_envs_step_kernel(sac_envs ev, const float* __restrict__ acti
 // replay's (size, write slot) after this step, as sac_replay_push computes
 // them.  Both kernels below are this body; they differ in where (pos, t) come
 // from.
-template <typename T, bool PENDULUM>
+template <typename T, int KC>
 __device__ __forceinline__ void rollout_step_body(const EngineDev* __restrict__ Ep, const sac_envs& ev,
                                                   const sac_replay& rb, int64_t pos, int64_t new_size, int64_t new_pos,
                                                   uint64_t t, int deterministic, int store) {
@@ -307,7 +442,7 @@ __device__ __forceinline__ void rollout_step_body(const EngineDev* __restrict__ 
     const int64_t slot = (pos + i) % rb.capacity;
     if (store)
       for (int k = 0; k < O; ++k) rb.obs[slot * rs.obs + k] = ev.obs[(size_t)i * O + k];
-    float a0 = 0.f;
+    float a0 = 0.f, a1 = 0.f;  // what the environment takes: registers, not a re-read of the replay row
     for (int p = 0; 2 * p < A; ++p) {
       float e2[2] = {0.f, 0.f};
       if (!deterministic) philox_normal2(E.seed, t, (uint32_t)i, ENV_WHICH_NOISE, (uint32_t)p, e2[0], e2[1]);
@@ -326,10 +461,11 @@ __device__ __forceinline__ void rollout_step_body(const EngineDev* __restrict__ 
           a = tanhf(z) * scale;
         }
         if (j == 0) a0 = a;
+        if (KC == ENV_CLASS_REACHER && j == 1) a1 = a;
         if (store) rb.act[slot * rs.act + j] = a;
       }
     }
-    const EnvOut eo = env_step<PENDULUM>(ev, i, t, a0, store ? rb.next_obs + slot * rs.obs : nullptr);
+    const EnvOut eo = env_step<KC>(ev, i, t, a0, a1, store ? rb.next_obs + slot * rs.obs : nullptr);
     env_account(ev, i, t, eo);
     if (store) {
       rb.rew[slot * rs.one] = (float)eo.reward;
@@ -344,14 +480,14 @@ __device__ __forceinline__ void rollout_step_body(const EngineDev* __restrict__ 
 }
 
 // One workgroup per SAC_ROWS environments; (size, pos, t) are host arguments,
-// new_size / new_pos computed by the host as sac_replay_push does.  PENDULUM:
-// ev.cfg.kind == SAC_ENV_PENDULUM (the host picks the instantiation).
-template <typename T, bool PENDULUM>
+// new_size / new_pos computed by the host as sac_replay_push does.  KC:
+// env_class(ev.cfg.kind) (the host picks the instantiation).
+template <typename T, int KC>
 __global__ void __launch_bounds__(SAC_THREADS) sac_rollout_step_kernel(const EngineDev* __restrict__ Ep, sac_envs ev,
                                                                       sac_replay rb, int64_t pos, int64_t new_size,
                                                                       int64_t new_pos, uint64_t t, int deterministic,
                                                                       int store) {
-  rollout_step_body<T, PENDULUM>(Ep, ev, rb, pos, new_size, new_pos, t, deterministic, store);
+  rollout_step_body<T, KC>(Ep, ev, rb, pos, new_size, new_pos, t, deterministic, store);
 }
 
 // The same step with the loop cursor on the device (include/sac_engine.h
@@ -362,7 +498,7 @@ __global__ void __launch_bounds__(SAC_THREADS) sac_rollout_step_kernel(const Eng
 // written), so nothing depends on the order workgroups run in and the launch
 // can be replayed from a hipGraph with the slots alternating.  A cursor outside
 // the ring (never seeded) stores nothing and does not advance.
-template <typename T, bool PENDULUM>
+template <typename T, int KC>
 __global__ void __launch_bounds__(SAC_THREADS) sac_rollout_step_dev_kernel(const EngineDev* __restrict__ Ep, sac_envs ev,
                                                                           sac_replay rb,
                                                                           const int64_t* __restrict__ cur,
@@ -373,7 +509,7 @@ __global__ void __launch_bounds__(SAC_THREADS) sac_rollout_step_dev_kernel(const
   if (size < 0 || size > cap || pos < 0 || pos >= cap) return;
   const int64_t new_size = store ? (size + n < cap ? size + n : cap) : size;
   const int64_t new_pos = store ? (pos + n) % cap : pos;
-  rollout_step_body<T, PENDULUM>(Ep, ev, rb, pos, new_size, new_pos, t, deterministic, store);
+  rollout_step_body<T, KC>(Ep, ev, rb, pos, new_size, new_pos, t, deterministic, store);
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     nxt[0] = new_size;
     nxt[1] = new_pos;

@@ -30,7 +30,8 @@
 // Environment state (envs_*, rollout_step): `obs` [N][O] fp32, `counters`
 // int32 [2][N] (step in episode, episode length), `dstate` float64 [2][N]
 // (position, episode return; the pendulum: [3][N], angle, episode return,
-// angular velocity), `ring` float64 [S][N][2] (the sac_env_episode
+// angular velocity; the reacher: [7][N], th1, th2, tx, ty, episode return, w1,
+// w2), `ring` float64 [S][N][2] (the sac_env_episode
 // cells: return, then length and ended as two int32); `icfg` = [kind, num_envs,
 // obs_dim, max_steps], `params` = the 11 doubles of sac_env_config in order.
 // Engine state: `engine` is the sac_engine* handle (int64) from
@@ -347,7 +348,8 @@ sac_envs make_envs(const at::Tensor& obs, const at::Tensor& counters, const at::
   TORCH_CHECK(icfg.size() == 4, "icfg must be [kind, num_envs, obs_dim, max_steps]");
   TORCH_CHECK(params.size() == 11, "params must hold the 11 doubles of sac_env_config");
   const int64_t N = icfg[1], O = icfg[2];
-  const bool pendulum = icfg[0] == SAC_ENV_PENDULUM;
+  const bool pendulum = icfg[0] == SAC_ENV_PENDULUM, reacher = icfg[0] == SAC_ENV_REACHER;
+  const int64_t pos_rows = reacher ? 4 : 1, vel_rows = reacher ? 2 : (pendulum ? 1 : 0);  // the kind's sac_envs.pos / .vel
   TORCH_CHECK(N >= 1 && N <= INT32_MAX && O >= 1 && O <= INT32_MAX, "num_envs and obs_dim must be >= 1");
   check_f32(obs, "env obs");
   TORCH_CHECK(obs.dim() == 2 && obs.size(0) == N && obs.size(1) == O, "env obs must be [num_envs][obs_dim]");
@@ -355,8 +357,9 @@ sac_envs make_envs(const at::Tensor& obs, const at::Tensor& counters, const at::
                   counters.dim() == 2 && counters.size(0) == 2 && counters.size(1) == N,
               "env counters must be a contiguous int32 [2][num_envs] device tensor");
   TORCH_CHECK(dstate.is_cuda() && dstate.scalar_type() == at::kDouble && dstate.is_contiguous() && dstate.dim() == 2 &&
-                  dstate.size(0) == (pendulum ? 3 : 2) && dstate.size(1) == N,
-              "env dstate must be a contiguous float64 [2][num_envs] device tensor ([3][num_envs] for the pendulum)");
+                  dstate.size(0) == pos_rows + 1 + vel_rows && dstate.size(1) == N,
+              "env dstate must be a contiguous float64 [2][num_envs] device tensor ([3][num_envs] for the pendulum, "
+              "[7][num_envs] for the reacher)");
   TORCH_CHECK(counters.device() == obs.device() && dstate.device() == obs.device(), "env state on different devices");
   sac_envs ev{};
   ev.cfg.kind = static_cast<int32_t>(icfg[0]);
@@ -379,8 +382,8 @@ sac_envs make_envs(const at::Tensor& obs, const at::Tensor& counters, const at::
   ev.step = counters.data_ptr<int32_t>();
   ev.ep_length = ev.step + N;
   ev.pos = dstate.data_ptr<double>();
-  ev.ep_return = ev.pos + N;
-  ev.vel = pendulum ? ev.pos + 2 * N : nullptr;
+  ev.ep_return = ev.pos + pos_rows * N;
+  ev.vel = vel_rows ? ev.ep_return + N : nullptr;
   if (ring && ring->defined()) {
     const auto& r = *ring;
     TORCH_CHECK(r.is_cuda() && r.scalar_type() == at::kDouble && r.is_contiguous() && r.dim() == 3 && r.size(0) >= 1 &&
@@ -405,9 +408,10 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor> envs_step
     at::IntArrayRef icfg, at::ArrayRef<double> params, int64_t seed, const at::Tensor& actions, int64_t t) {
   sac_envs ev = make_envs(obs, counters, dstate, ring, icfg, params, seed);
   check_f32(actions, "actions");
-  TORCH_CHECK(actions.dim() == 2 && actions.size(0) == obs.size(0) && actions.size(1) == 1 &&
+  const int64_t A = SAC_ENV_ACT_DIM(ev.cfg.kind);
+  TORCH_CHECK(actions.dim() == 2 && actions.size(0) == obs.size(0) && actions.size(1) == A &&
                   actions.device() == obs.device(),
-              "actions must be [num_envs][1] on the environments' device");
+              "actions must be [num_envs][", A, "] on the environments' device");
   TORCH_CHECK(t >= 1, "vector step t must be >= 1 (0 is the reset)");
   const int64_t N = obs.size(0), O = obs.size(1);
   auto o = obs.options();

@@ -765,7 +765,7 @@ class SAC:
         env = vec_env if vec_env is not None else self.env
         if not isinstance(env, DeviceVectorEnv):
             raise TypeError(f"{what} needs a sac.device_envs.DeviceVectorEnv (a probe environment of sac.envs or "
-                            "the pendulum of sac.control_envs resident on the device); other environments run "
+                            "a control task of sac.control_envs resident on the device); other environments run "
                             "through run_vectorized_training_loop")
         return env
 

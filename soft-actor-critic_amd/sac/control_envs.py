@@ -24,6 +24,33 @@ The device-resident form (``sac.device_envs.DeviceVectorEnv("pendulum", N)``,
 arithmetic in the same order; only its ``sin`` / ``cos`` (the device library's,
 not the host libm's) and its reset draws (Philox instead of numpy's generator)
 differ.
+
+``ReacherEnv`` is a planar two-link arm reaching for a target, the one task
+with TWO action components.  The joints are decoupled first-order rotors driven
+by a torque each (no mass matrix): what the policy has to learn is the
+kinematics that couple them.  With links ``L1 = L2 = 0.1``, ``GAIN = 10``,
+``DAMP = 2``, ``CTRL_COST = 0.1`` and the target (tx, ty) fixed for the episode:
+
+    u_j    = clip(a_j, -max_torque, max_torque)                        j = 0, 1
+    dx     = (L1 cos th1 + L2 cos(th1 + th2)) - tx
+    dy     = (L1 sin th1 + L2 sin(th1 + th2)) - ty
+    reward = -sqrt(dx^2 + dy^2) - CTRL_COST (u0^2 + u1^2)              (the pre-step state)
+    w_j'   = w_j + (GAIN u_j - DAMP w_j) dt
+    th_j'  = th_j + w_j' dt
+    obs    = float32 [cos th1', cos th2', sin th1', sin th2', tx, ty, w1', w2', dx', dy']
+
+It never terminates and is truncated after ``max_steps`` steps; ``reset`` draws
+``tx, ty ~ U(-0.14, 0.14)`` (a square inside the reach circle of radius 0.2),
+``th1, th2 ~ U(-pi, pi)`` and starts at rest.  |w| stays below GAIN / DAMP *
+max_torque = 5, so no speed clip is needed.  Standing still costs about -16 per
+100-step episode, a joint-space PD controller toward the inverse-kinematics
+solution about -3.6 (profiles/reacher_baselines.txt).  Train it with
+``policy_net.action_scale: 1.0``.
+
+Its device form (``DeviceVectorEnv("reacher", N)``, ``SAC_ENV_REACHER``) never
+feeds a sine or cosine back into the state, so the state trajectory is this
+class's bit for bit; observations and rewards differ by the device library's
+``sin`` / ``cos`` only.
 """
 from __future__ import annotations
 
@@ -90,4 +117,75 @@ class PendulumEnv(_Env):
         return self._obs(), reward, False, truncated, info
 
 
-__all__ = ["PendulumEnv"]
+class ReacherEnv(_Env):
+    """Planar two-link reacher; ``state`` = [th1, th2, w1, w2, tx, ty] as Python floats (settable)."""
+
+    L1 = 0.1
+    L2 = 0.1
+    GAIN = 10.0
+    DAMP = 2.0
+    CTRL_COST = 0.1
+    TARGET_HALF_SIDE = 0.14
+
+    def __init__(self, max_steps: int = 100, dt: float = 0.05, max_torque: float = 1.0):
+        super().__init__()
+        self.max_steps = int(max_steps)
+        self.dt = float(dt)
+        self.max_torque = float(max_torque)
+        self.action_space = Box(low=-self.max_torque, high=self.max_torque, shape=(2,), dtype=np.float32)
+        w_max = self.GAIN / self.DAMP * self.max_torque
+        reach = self.L1 + self.L2 + self.TARGET_HALF_SIDE
+        high = np.array([1.0, 1.0, 1.0, 1.0, self.TARGET_HALF_SIDE, self.TARGET_HALF_SIDE, w_max, w_max, reach, reach],
+                        dtype=np.float32)
+        self.observation_space = Box(low=-high, high=high, shape=(10,), dtype=np.float32)
+        self.current_step = 0
+        self.state = [0.0, 0.0, 0.0, 0.0, 0.0, 0.0]
+        self.episode_reward = 0.0
+
+    def _tip_to_target(self):
+        th1, th2, _, _, tx, ty = self.state
+        dx = (self.L1 * math.cos(th1) + self.L2 * math.cos(th1 + th2)) - tx
+        dy = (self.L1 * math.sin(th1) + self.L2 * math.sin(th1 + th2)) - ty
+        return dx, dy
+
+    def _obs(self) -> np.ndarray:
+        th1, th2, w1, w2, tx, ty = self.state
+        dx, dy = self._tip_to_target()
+        return np.array([math.cos(th1), math.cos(th2), math.sin(th1), math.sin(th2), tx, ty, w1, w2, dx, dy],
+                        dtype=np.float32)
+
+    def reset(self, seed: Optional[int] = None, options: Optional[dict] = None):
+        super().reset(seed=seed)
+        self.current_step, self.episode_reward = 0, 0.0
+        h = self.TARGET_HALF_SIDE
+        tx = float(self.np_random.uniform(low=-h, high=h))
+        ty = float(self.np_random.uniform(low=-h, high=h))
+        th1 = float(self.np_random.uniform(low=-math.pi, high=math.pi))
+        th2 = float(self.np_random.uniform(low=-math.pi, high=math.pi))
+        self.state = [th1, th2, 0.0, 0.0, tx, ty]
+        return self._obs(), {}
+
+    def step(self, action):
+        self.current_step += 1
+        th1, th2, w1, w2, tx, ty = (float(x) for x in self.state)
+        self.state = [th1, th2, w1, w2, tx, ty]
+        dt = self.dt
+        lo, hi = self.action_space.low, self.action_space.high
+        u0 = float(np.clip(np.float32(action[0]), lo[0], hi[0]))
+        u1 = float(np.clip(np.float32(action[1]), lo[1], hi[1]))
+        dx, dy = self._tip_to_target()
+        reward = -math.sqrt(dx * dx + dy * dy) - self.CTRL_COST * (u0 * u0 + u1 * u1)
+        w1 = w1 + (self.GAIN * u0 - self.DAMP * w1) * dt
+        w2 = w2 + (self.GAIN * u1 - self.DAMP * w2) * dt
+        th1 = th1 + w1 * dt
+        th2 = th2 + w2 * dt
+        self.state = [th1, th2, w1, w2, tx, ty]
+        self.episode_reward += reward
+        truncated = self.current_step >= self.max_steps
+        info = {"action": (u0, u1)}
+        if truncated:
+            info["episode"] = {"r": self.episode_reward, "l": self.current_step}
+        return self._obs(), reward, False, truncated, info
+
+
+__all__ = ["PendulumEnv", "ReacherEnv"]

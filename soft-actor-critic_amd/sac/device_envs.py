@@ -1,5 +1,6 @@
-"""The probe environments of ``sac.envs`` and the pendulum swing-up of
-``sac.control_envs`` resident on the device.
+"""The probe environments of ``sac.envs`` and the control tasks of
+``sac.control_envs`` (the pendulum swing-up, the two-link reacher) resident on
+the device.
 
 ``DeviceVectorEnv`` holds N copies of one environment as device state
 (``include/sac_engine.h`` ``sac_envs``) and steps them in HIP kernels with the
@@ -16,14 +17,17 @@ Two ways to step:
   launch (the policy forward, the squashed-Gaussian sample, the env step and
   the write into the replay ring), the step of ``SAC.run_device_training_loop``.
 
-The only randomness is ``RandomObsBinaryRewardEnv``'s observations and
-``PendulumEnv``'s reset states: Philox draws keyed by the seed given to
+The only randomness is ``RandomObsBinaryRewardEnv``'s observations and the
+reset states of ``PendulumEnv`` and ``ReacherEnv``: Philox draws keyed by the seed given to
 ``reset`` with counter (vector step, env row), so a run is reproducible
 whatever order the workgroups run in (the host classes draw from numpy's
 generator instead: same distribution, other numbers).  The pendulum's float64
 arithmetic is the host class's in the same order; its ``sin`` / ``cos`` are the
 device library's, so its fp32 observations and rewards may differ from the
-host's in the last bit.
+host's in the last bit.  The same holds for the reacher, whose state never
+takes a sine or cosine in: its (angles, speeds, target) are the host class's
+bit for bit.  The reacher is the one kind with two action components:
+``act_dim`` is the host class's action space's, per kind.
 
 Episode statistics: every step writes each env's running (return, length,
 ended) into a dense ring ``[ring_steps][N]`` indexed by ``t % ring_steps``;
@@ -52,7 +56,10 @@ KINDS = {
     "random_obs_binary": (2, host_envs.RandomObsBinaryRewardEnv),
     "point_mass": (3, host_envs.OneDPointMassReachEnv),
     "pendulum": (8, control_envs.PendulumEnv),
+    "reacher": (16, control_envs.ReacherEnv),
 }
+# rows of the float64 state tensor per kind: the kind's position block, the episode return, its velocity block
+_DSTATE_ROWS = {"pendulum": 3, "reacher": 7}
 _BY_CLASS = {cls.__name__: name for name, (_, cls) in KINDS.items()}
 _BY_CODE = {code: name for name, (code, _) in KINDS.items()}
 
@@ -64,6 +71,7 @@ _PARAM_ATTRS = {
     "point_mass": {"start_pos": "start_pos", "goal_pos": "goal_pos", "dt": "dt", "step_penalty": "step_penalty",
                    "goal_reward": "goal_reward", "goal_tolerance": "goal_tolerance"},
     "pendulum": {"dt": "dt"},  # the torque bound is the action space's, as for every kind
+    "reacher": {"dt": "dt"},
 }
 
 
@@ -90,8 +98,8 @@ class DeviceVectorEnv:
 
     @classmethod
     def from_env(cls, host_env, num_envs: int, device=None, ring_steps: Optional[int] = None) -> "DeviceVectorEnv":
-        """N device copies of ``host_env`` (an instance of a ``sac.envs`` class or of
-        ``sac.control_envs.PendulumEnv``), with its parameters."""
+        """N device copies of ``host_env`` (an instance of a ``sac.envs`` class or of a
+        ``sac.control_envs`` one), with its parameters."""
         kind_name(type(host_env))
         self = cls.__new__(cls)
         self._setup(host_env, num_envs, device, ring_steps)
@@ -128,8 +136,9 @@ class DeviceVectorEnv:
             raise ValueError("ring_steps must be >= 1")
         self.obs = torch.zeros(N, self.obs_dim, dtype=torch.float32, device=dev)
         self.counters = torch.zeros(2, N, dtype=torch.int32, device=dev)   # step in episode, episode length
-        # position (the pendulum: angle), episode return; the pendulum adds its angular velocity
-        self.dstate = torch.zeros(3 if self.kind == "pendulum" else 2, N, dtype=torch.float64, device=dev)
+        # position (the pendulum: angle), episode return; the pendulum adds its angular velocity.  The reacher:
+        # th1, th2, tx, ty, episode return, w1, w2
+        self.dstate = torch.zeros(_DSTATE_ROWS.get(self.kind, 2), N, dtype=torch.float64, device=dev)
         self.ring = torch.zeros(self.ring_steps, N, 2, dtype=torch.float64, device=dev)
         self.seed = 0
         self.t = 0  # vector steps taken since the last reset; step k (0-based) is RNG step t = k + 1
@@ -148,7 +157,7 @@ class DeviceVectorEnv:
         return self.obs.clone(), {}
 
     def step(self, actions):
-        """Step with device actions [N][1] -> device tensors (obs, rewards,
+        """Step with device actions [N][act_dim] -> device tensors (obs, rewards,
         terminated, truncated, {"final_obs": ...}); no host copy, no sync."""
         if not self._reset_done:
             self.reset()

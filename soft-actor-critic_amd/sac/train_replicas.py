@@ -17,12 +17,12 @@ aggregate as one JSON line.
         --env point_mass --num-envs 16 --env-steps 200000
 
 Without torchrun it runs one replica in-process.  ``--env`` names one of the
-probe envs of ``sac.envs``, ``pendulum`` (the swing-up of
+probe envs of ``sac.envs``, ``pendulum`` or ``reacher`` (the control tasks of
 ``sac.control_envs``) or, when gymnasium is importable, any registered
 gymnasium id (the reference's own envs).  The policy's output range is the
 config's ``policy_net.action_scale``, not the environment's: for ``pendulum``
 set it to 2.0 (its torque bound); at 1.0 the policy can use only half the
-torque.
+torque.  ``reacher`` takes 1.0.
 
 ``--device-envs`` (the built-in envs only) keeps the environments on the device
 (``sac.device_envs.DeviceVectorEnv``) and trains through
@@ -58,12 +58,13 @@ PROBE_ENVS = {
     "quadratic_action": ("envs", "QuadraticActionRewardEnv", {}),
     "random_obs_binary": ("envs", "RandomObsBinaryRewardEnv", {}),
     "pendulum": ("control_envs", "PendulumEnv", {}),
+    "reacher": ("control_envs", "ReacherEnv", {}),
 }
 
 
 def env_factory(name: str) -> Callable[[], object]:
     """A zero-argument env constructor for ``name``: a probe env of sac.envs or
-    the pendulum of sac.control_envs, else a gymnasium id (gymnasium must be
+    a control task of sac.control_envs, else a gymnasium id (gymnasium must be
     importable)."""
     if name in PROBE_ENVS:
         import importlib
@@ -90,7 +91,7 @@ def train_replica(config: dict, make_env: Callable[[], object], num_envs: int, e
     "aggregate": the all-reduced METRICS summary}.  ``agent_cls`` /
     ``vec_env_cls`` default to sac.agent.SAC / sac.vector_env.SyncVectorEnv
     (tests pass host stubs).  ``device_envs``: ``make_env`` must build a probe
-    env of sac.envs or sac.control_envs.PendulumEnv; num_envs device copies of it (DeviceVectorEnv.from_env)
+    env of sac.envs or a control task of sac.control_envs; num_envs device copies of it (DeviceVectorEnv.from_env)
     train through ``run_device_training_loop`` (``graph_steps``: its argument)."""
     if agent_cls is None:
         from sac.agent import SAC as agent_cls  # noqa: N813

@@ -1,0 +1,400 @@
+"""The device-resident two-link reacher on the MI355X, the one environment with
+two action components: the step kernel against sac.control_envs.ReacherEnv, the
+fused rollout step against the step kernel and sac_policy_act, the loop graph
+against the stepwise loop, and a training run whose evaluation return has to
+pass a bar set by scripted policies on the host class alone.
+
+Equality rules.  Sine and cosine enter the reacher's reward and observation
+only, so its float64 state (angles, speeds, target) is the host class's BIT FOR
+BIT at every step, resets included (the host instances take the reset draws of
+sac_debug_reacher_reset_host).  Observations and rewards go through the device
+library's sin / cos / sqrt, each accurate to a few float64 ulps: every fp32
+observation and fp32-rounded reward is within ONE fp32 ulp of the host's.
+Flags, counters, episode lengths and ended marks are exact; an episode return,
+a float64 sum of at most max_steps = 5 rewards of magnitude below 1 that each
+differ from the host's by a few float64 ulps (2.2e-16), is within 1e-13.
+Device against device (fused step against step kernel and policy_act, graph
+against stepwise) is bit for bit."""
+import ctypes
+import math
+
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+DEV = "cuda"
+u64, i32, vp = ctypes.c_uint64, ctypes.c_int32, ctypes.c_void_p
+f64p = ctypes.POINTER(ctypes.c_double)
+
+
+def _cfg(hidden=(40, 72), precision="fp32", capacity=1000, batch=32, warming=64, seed=3, log_episodes=False,
+         log_q=False):
+    hidden = list(hidden)
+    return {
+        "sac": {"gamma": 0.99, "tau": 0.005, "alpha": 0.2, "auto_entropy_tuning": True, "actor_lr": 3e-4,
+                "critic_lr": 3e-4, "alpha_lr": 3e-4},
+        "q_net": {"hidden_sizes": hidden, "hidden_layers_act": "relu", "output_activation": "identity"},
+        "policy_net": {"hidden_sizes": hidden, "hidden_layers_act": "relu", "output_activation": "identity",
+                       "log_std_min": -20, "log_std_max": 2, "action_scale": 1.0},
+        "buffer": {"capacity": capacity},
+        "train": {"gradient_steps_per_update": 1, "update_frequency": 1, "seed": seed, "batch_size": batch,
+                  "warming_steps": warming, "device": "cuda", "precision": precision, "graph_chunk": 4},
+        "logger": {"enabled": False, "env_name": "reacher", "agent_name": "SAC", "log_episode_stats": log_episodes,
+                   "log_q_values": log_q, "save_model": {"enabled": False, "path": None}},
+    }
+
+
+def bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def raw(t):
+    return t.detach().contiguous().view(torch.uint8).cpu()
+
+
+def within_one_ulp(dev, host, what):
+    """dev fp32 within one fp32 ulp of host fp32, elementwise; returns the number of non-identical elements."""
+    dev, host = np.asarray(dev, np.float32), np.asarray(host, np.float32)
+    err = np.abs(dev.astype(np.float64) - host.astype(np.float64))
+    ok = err <= np.spacing(np.abs(host)).astype(np.float64)
+    n_diff = int(np.sum(bits(dev) != bits(host)))
+    print(f"{what}: {n_diff} of {dev.size} not identical, max |err| {err.max():.3e}, beyond 1 ulp {int(np.sum(~ok))}")
+    assert np.all(ok), f"{what}: {int(np.sum(~ok))} of {dev.size} beyond 1 ulp (max |err| {err.max():.3e})"
+    return n_diff
+
+
+@pytest.fixture(scope="module")
+def lib():
+    from sac import _engine as E
+
+    lb = E.load_library()
+    lb.sac_debug_rollout_eps_device.argtypes = [u64, u64, i32, i32, vp, vp]
+    lb.sac_debug_rollout_eps_device.restype = ctypes.c_int
+    lb.sac_debug_reacher_reset_host.argtypes = [u64, u64, i32, f64p]
+    lb.sac_debug_reacher_reset_host.restype = ctypes.c_int
+    return lb
+
+
+def host_state(dstate, i):
+    """ReacherEnv.state of row i from the device's float64 rows (th1, th2, tx, ty, episode return, w1, w2)."""
+    return [float(dstate[0, i]), float(dstate[1, i]), float(dstate[5, i]), float(dstate[6, i]), float(dstate[2, i]),
+            float(dstate[3, i])]
+
+
+# ---------------------------------------------------------------- 1. step kernel against the host class
+def test_step_matches_host_class(lib):
+    from sac.control_envs import ReacherEnv
+    from sac.device_envs import DeviceVectorEnv
+
+    N, max_steps, T, seed = 37, 5, 12, 11  # three workgroups of SAC_ROWS = 16 rows, the last partial; two resets
+    dv = DeviceVectorEnv.from_env(ReacherEnv(max_steps=max_steps), N, device=DEV)
+    assert dv.obs_dim == 10 and dv.act_dim == 2 and tuple(dv.dstate.shape) == (7, N) and dv.kind_code == 16
+    hosts = [ReacherEnv(max_steps=max_steps) for _ in range(N)]
+    obs0, info = dv.reset(seed=seed)
+    assert info == {} and obs0.is_cuda and tuple(obs0.shape) == (N, 10)
+
+    def adopt(rows, t):  # the host instances take the reset draws of step t (their own generator's differ by design)
+        for i in rows:
+            st = (ctypes.c_double * 6)()
+            assert lib.sac_debug_reacher_reset_host(seed, t, i, st) == 0
+            hosts[i].reset()
+            hosts[i].state = list(st)
+
+    def assert_state_is_the_hosts(what):
+        st = dv.dstate.cpu().numpy()
+        got = np.array([host_state(st, i) for i in range(N)])
+        want = np.array([h.state for h in hosts], np.float64)
+        assert np.array_equal(got.view(np.uint64), want.view(np.uint64)), (what, np.argwhere(got != want)[:4])
+        return st
+
+    adopt(range(N), 0)
+    st = assert_state_is_the_hosts("reset")
+    assert np.all(np.abs(st[2:4]) <= 0.14) and np.all(st[:2] >= -math.pi) and np.all(st[:2] < math.pi)
+    assert np.all(st[5:] == 0.0) and len(np.unique(st[0])) == N
+    n_diff = within_one_ulp(obs0.cpu().numpy(), np.stack([h._obs() for h in hosts]), "reset obs")
+    n_all = obs0.numel()
+    rng = np.random.default_rng(100 + N)
+    actions = rng.uniform(-1.5, 1.5, size=(T, N, 2)).astype(np.float32)  # a third of them beyond the torque bound
+    assert (np.abs(actions) > 1.0).any() and (np.abs(actions) < 1.0).any() and not np.any(actions[..., 0] == actions[..., 1])
+    acts = torch.from_numpy(actions).to(DEV)
+    ep_ret, ep_len, cells = np.zeros(N), np.zeros(N, np.int64), []
+    for t in range(T):
+        if t == 3:  # the columns are not interchangeable: the same state stepped with them swapped goes elsewhere
+            tw = twin_of(dv)
+            tw.step(acts[t].flip(1))
+        o, r, te, tr, inf = dv.step(acts[t])
+        if t == 3:
+            assert not torch.equal(raw(tw.dstate), raw(dv.dstate)) and not torch.equal(raw(tw.obs), raw(dv.obs))
+            assert torch.equal(raw(tw.dstate[2:5]), raw(dv.dstate[2:5]))  # targets the same; u0^2 + u1^2 symmetric
+        assert all(x.is_cuda for x in (o, r, te, tr, inf["final_obs"])) and te.dtype == torch.bool
+        o, r, te, tr, fin = (x.cpu().numpy() for x in (o, r, te, tr, inf["final_obs"]))
+        want = [h.step(actions[t, i]) for i, h in enumerate(hosts)]
+        w_fin = np.stack([w[0] for w in want])
+        w_rew = np.array([w[1] for w in want], np.float64)
+        w_trunc = np.array([w[3] for w in want], bool)
+        assert not te.any() and np.array_equal(tr, w_trunc), t
+        assert np.array_equal(tr, np.full(N, (t + 1) % max_steps == 0)), t
+        n_diff += within_one_ulp(fin, w_fin, f"step {t + 1} final_obs")
+        n_diff += within_one_ulp(r, w_rew.astype(np.float32), f"step {t + 1} reward")
+        n_all += fin.size + r.size
+        ep_ret += w_rew
+        ep_len += 1
+        cells.append((ep_ret.copy(), ep_len.copy(), w_trunc.copy()))
+        ep_ret[w_trunc], ep_len[w_trunc] = 0.0, 0
+        if w_trunc.any():
+            adopt(np.nonzero(w_trunc)[0], t + 1)
+            w_cur = np.stack([h._obs() for h in hosts])
+            assert not np.array_equal(o, fin)  # a fresh draw, not the state stepped to
+        else:
+            w_cur = w_fin
+        assert_state_is_the_hosts(f"step {t + 1}")
+        n_diff += within_one_ulp(o, w_cur, f"step {t + 1} obs after autoreset")
+        n_all += o.size
+        counters = dv.counters.cpu().numpy()
+        assert np.array_equal(counters[0], [h.current_step for h in hosts]), t
+        assert np.array_equal(counters[1], ep_len), t
+    print(f"{n_diff} of {n_all} fp32 elements not identical to the host's")
+    # the episode ring: lengths and ended marks exact, returns within 1e-13 (module docstring)
+    ring = dv.ring.cpu()
+    ints = ring[..., 1].contiguous().view(torch.int32).reshape(ring.shape[0], N, 2).numpy()
+    rets = ring[..., 0].numpy()
+    worst = 0.0
+    for t, (w_ret, w_len, w_end) in enumerate(cells, start=1):
+        c = t % dv.ring_steps
+        assert np.array_equal(ints[c, :, 0], w_len) and np.array_equal(ints[c, :, 1], w_end.astype(np.int32)), t
+        worst = max(worst, float(np.abs(rets[c] - w_ret).max()))
+    print(f"episode returns: max |device - host| {worst:.3e}")
+    assert worst <= 1e-13
+    assert sum(int(c[2].sum()) for c in cells) == N * (T // max_steps) == 2 * N
+
+
+# ---------------------------------------------------------------- 2. the fused rollout step
+def make_agent(N, max_steps=5, precision="fp32", layout="records", **cfg_kw):
+    from sac.agent import SAC
+    from sac.control_envs import ReacherEnv
+    from sac.device_envs import DeviceVectorEnv
+    from sac.replay_buffer import ReplayBuffer
+
+    cfg = _cfg(precision=precision, **cfg_kw)
+    dv = DeviceVectorEnv.from_env(ReacherEnv(max_steps=max_steps), N, device=DEV)
+    agent = SAC(dv, cfg)  # _set_seed resets the envs with train.seed
+    if layout != "records":
+        agent.replay_buffer = ReplayBuffer(cfg["buffer"]["capacity"], device=agent.device, layout=layout)
+    return agent, dv
+
+
+def twin_of(dv):
+    """Another DeviceVectorEnv in dv's state: stepping it with the stored actions is the step kernel's answer."""
+    from sac.control_envs import ReacherEnv
+    from sac.device_envs import DeviceVectorEnv
+
+    tw = DeviceVectorEnv.from_env(ReacherEnv(max_steps=dv.max_steps), dv.num_envs, device=DEV)
+    tw.seed, tw.t, tw._reset_done = dv.seed, dv.t, True
+    for name in ("obs", "counters", "dstate", "ring"):
+        getattr(tw, name).copy_(getattr(dv, name))
+    return tw
+
+
+@pytest.mark.parametrize("precision", ["fp32", "bf16"])
+@pytest.mark.parametrize("layout", ["records", "soa"])
+def test_fused_rollout_matches_step_kernel_and_policy_act(lib, layout, precision):
+    N, T, cap = 37, 7, 100  # the ring wraps on the third step, at a capacity that is no multiple of N
+    agent, dv = make_agent(N, max_steps=5, precision=precision, layout=layout, capacity=cap, batch=16)
+    eng, rb = agent.engine, agent.replay_buffer
+    assert float(eng.cfg.action_scale) == 1.0 and int(eng.cfg.act_dim) == 2 and int(eng.cfg.obs_dim) == 10
+    rb._alloc(dv.obs_dim, dv.act_dim)
+    assert rb.layout == layout and tuple(rb.act.shape) == (cap, 2)
+    torch.cuda.synchronize()
+    gen0 = int(rb.state.cpu()[2])
+    seed = int(eng.cfg.seed)
+    dones, all_acts = [], []
+    for t in range(1, T + 1):
+        tw = twin_of(dv)
+        before = dv.obs.clone()
+        slots = (torch.arange(N, device=DEV) + rb._pos) % cap
+        eng.rollout_step(dv, rb)
+        got = {k: getattr(rb, k)[slots].clone() for k in ("obs", "act", "rew", "next_obs", "done")}
+        # the stored action, BOTH columns: policy_act on the observations the step saw with the step's Philox
+        # noise as the device draws it (pair 0 of the row: column 0 its first normal, column 1 its second)
+        eps = torch.full((N, 2), float("nan"), device=DEV)
+        assert lib.sac_debug_rollout_eps_device(seed, t, N, 2, eps.data_ptr(), None) == 0
+        want_act = eng.policy_act(before, eps)
+        err = float((got["act"] - want_act).abs().max())
+        print(f"step {t}: stored actions against policy_act max |err| {err:.3e}")
+        assert tuple(want_act.shape) == (N, 2) and torch.equal(raw(got["act"]), raw(want_act)), (t, err)
+        assert not torch.equal(got["act"][:, 0], got["act"][:, 1])
+        # the stored transition: the step kernel's from the same state with those actions, bit for bit
+        o, r, te, tr, inf = tw.step(got["act"])
+        assert torch.equal(raw(got["obs"]), raw(before)), t
+        assert torch.equal(raw(got["next_obs"]), raw(inf["final_obs"])), t
+        assert torch.equal(raw(got["rew"]), raw(r)), t
+        assert torch.equal(got["done"], (te | tr).to(torch.float32)), t
+        for name in ("obs", "counters", "dstate", "ring"):
+            assert torch.equal(raw(getattr(dv, name)), raw(getattr(tw, name))), (t, name)
+        assert torch.equal(raw(o), raw(dv.obs))
+        dones.append(got["done"].cpu().numpy())
+        all_acts.append(got["act"].cpu().numpy())
+    dones = np.stack(dones)
+    assert np.array_equal(dones, np.repeat((np.arange(1, T + 1) % 5 == 0)[:, None], N, 1).astype(np.float32))
+    acts = np.stack(all_acts)
+    assert len(np.unique(acts)) > 2 * N and np.abs(acts).max() <= 1.0
+    obs = rb.obs.cpu().numpy()
+    assert np.allclose(obs[:, 0] ** 2 + obs[:, 2] ** 2, 1.0, atol=1e-6) and np.abs(obs[:, 4:6]).max() <= 0.14
+    assert np.allclose(obs[:, 1] ** 2 + obs[:, 3] ** 2, 1.0, atol=1e-6) and np.abs(obs[:, 6:8]).max() <= 5.0
+    assert rb.state.cpu().tolist() == [cap, (T * N) % cap, gen0 + T] and (rb._size, rb._pos) == (cap, (T * N) % cap)
+
+    # store = 0 (evaluation): the environments step, the replay and its generation stay; the deterministic
+    # action is tanh(mu) * scale on both columns (policy_act without noise)
+    storage0, state0 = raw(rb.storage), rb.state.cpu().tolist()
+    tw = twin_of(dv)
+    before = dv.obs.clone()
+    eng.rollout_step(dv, rb, deterministic=True, store=False)
+    torch.cuda.synchronize()
+    assert torch.equal(storage0, raw(rb.storage)) and rb.state.cpu().tolist() == state0
+    assert (rb._size, rb._pos) == (cap, (T * N) % cap)
+    det = eng.policy_act(before)
+    assert tuple(det.shape) == (N, 2) and not torch.equal(det[:, 0], det[:, 1])
+    tw.step(det)
+    for name in ("obs", "counters", "dstate"):
+        assert torch.equal(raw(getattr(dv, name)), raw(getattr(tw, name))), name
+    assert dv.t == T + 1
+    # deterministic AND stored: both stored columns are tanh(mu) * scale
+    before = dv.obs.clone()
+    slots = (torch.arange(N, device=DEV) + rb._pos) % cap
+    eng.rollout_step(dv, rb, deterministic=True, store=True)
+    assert torch.equal(raw(rb.act[slots]), raw(eng.policy_act(before)))
+
+
+# ---------------------------------------------------------------- 3. device cursor and graph
+class Logger:
+    def __init__(self):
+        self.episodes, self.q, self.hparams = [], [], []
+
+    def log_episode_metrics(self, episode_idx, reward, length):
+        self.episodes.append((episode_idx, reward, length))
+
+    def log_q_values(self, q1, q2, step):
+        self.q.append((step, q1, q2))
+
+    def log_hparams(self, cfg, metrics):
+        self.hparams.append(dict(metrics))
+
+
+def test_training_loop_with_graph_steps_matches_stepwise():
+    N, warming = 17, 64
+    total = 4 * N + 40 * N + 5  # the warm-up ends with the fourth vector step; 40 whole steps and a ragged one follow
+    runs = []
+    for graph_steps in (0, 8):
+        agent, dv = make_agent(N, max_steps=5, capacity=300, batch=32, warming=warming, log_episodes=True, log_q=True)
+        logger = Logger()
+        calls = []
+        orig = agent.engine.loop_graph
+        agent.engine.loop_graph = lambda *a, **k: (calls.append(1), orig(*a, **k))[1]
+        m = agent.run_device_training_loop(total, logger=logger, graph_steps=graph_steps, drain_every=8,
+                                           device_q_values=True)
+        torch.cuda.synchronize()
+        agent.engine.check()
+        state = dict(agent.engine.state_tensors(), storage=agent.replay_buffer.storage,
+                     replay_state=agent.replay_buffer.state, env_obs=dv.obs, env_counters=dv.counters,
+                     env_dstate=dv.dstate, env_ring=dv.ring)
+        runs.append(dict(metrics=m, episodes=logger.episodes, q=logger.q, state={k: raw(v) for k, v in state.items()},
+                         graphs=len(calls)))
+    a, b = runs
+    assert a["graphs"] == 0 and b["graphs"] >= 4  # resets (every fifth step) fall inside blocks of eight
+    assert a["metrics"] == b["metrics"] and a["metrics"]["total_env_steps"] == 45 * N
+    assert a["metrics"]["gradient_steps"] == 45 * N - (warming - 1) and a["metrics"]["total_episodes"] == 9 * N
+    assert a["episodes"] == b["episodes"] and len(a["episodes"]) == 9 * N
+    # five steps of at most 0.34 sqrt(2) distance and 0.2 control cost each
+    assert all(length == 5 and -5 * 0.69 <= ret < 0.0 for _, ret, length in a["episodes"])
+    assert [s for s, _, _ in a["q"]] == [s for s, _, _ in b["q"]] == list(range(1, 45 * N + 1))
+    qa = np.array([(q1, q2) for _, q1, q2 in a["q"]], np.float32).view(np.uint32)
+    qb = np.array([(q1, q2) for _, q1, q2 in b["q"]], np.float32).view(np.uint32)
+    assert np.array_equal(qa, qb) and len(np.unique(qa)) > 100
+    bad = [k for k in a["state"] if not torch.equal(a["state"][k], b["state"][k])]
+    assert not bad, f"graph_steps = 8 against stepwise: {bad} differ"
+    assert a["state"].keys() >= {"param/pi", "param/q1", "storage", "env_dstate"}
+
+
+# ---------------------------------------------------------------- 4. learning
+# 16 environments, one gradient step per environment step after a warm-up of 1,000 transitions, blocks of 8 vector
+# steps from the loop graph; evaluation: 64 deterministic episodes of 100 steps.
+LEARNING = dict(num_envs=16, hidden=[256, 256], precision="fp32", batch=256, capacity=100_000, warming=1000,
+                gradient_steps=80_000, graph_steps=8, eval_episodes=64)
+# profiles/reacher_baselines.txt, the host class alone: zero torque -16.395, the PD controller -3.011 (means of 100
+# seeded episodes).  The bar is their midpoint, -9.703.
+ZERO_TORQUE, PD_CONTROLLER = -16.395, -3.011
+LEARNING_BAR = (ZERO_TORQUE + PD_CONTROLLER) / 2
+# The step count is the smallest multiple of 20,000 at which the worst of seeds 1, 2, 3 cleared the bar by a tenth of
+# the zero-to-PD gap (1.338, so -8.365), measured once (profiles/reacher_learning.txt): worst seed -10.609 at 20,000,
+# -9.442 at 40,000, -9.065 at 60,000, -8.328 at 80,000 (seeds 1, 2, 3: -7.280, -8.328, -7.799).
+
+
+def learning_run(seed, gradient_steps=None):
+    import time
+
+    from sac.agent import SAC
+    from sac.device_envs import DeviceVectorEnv
+
+    c = dict(LEARNING, gradient_steps=gradient_steps or LEARNING["gradient_steps"])
+    t0 = time.perf_counter()
+    dv = DeviceVectorEnv("reacher", c["num_envs"], device=DEV)
+    agent = SAC(dv, _cfg(hidden=c["hidden"], precision=c["precision"], capacity=c["capacity"], batch=c["batch"],
+                         warming=c["warming"], seed=seed))
+    untrained = agent.evaluate_device(c["eval_episodes"], dv)
+    t1 = time.perf_counter()
+    # whole vector steps; the first update is at the warming-th transition: at most c["gradient_steps"] of them
+    vec_steps = (c["gradient_steps"] + c["warming"] - 1) // c["num_envs"]
+    m = agent.run_device_training_loop(vec_steps * c["num_envs"], seed=seed, graph_steps=c["graph_steps"])
+    assert 0.99 * c["gradient_steps"] <= m["gradient_steps"] <= c["gradient_steps"]
+    torch.cuda.synchronize()
+    t2 = time.perf_counter()
+    trained = agent.evaluate_device(c["eval_episodes"], dv)
+    agent.engine.close()
+    return dict(untrained=untrained, trained=trained, gradient_steps=m["gradient_steps"],
+                env_steps=m["total_env_steps"], episodes=m["total_episodes"], train_s=t2 - t1,
+                total_s=time.perf_counter() - t0)
+
+
+@pytest.mark.parametrize("seed", [1, 2, 3])
+def test_training_passes_the_bar_of_the_scripted_policies(seed):
+    """The engine learns with two action components, end to end: the device loop lifts the deterministic policy's
+    mean return over 64 episodes from the zero-torque side of the bar to the PD controller's side.  Everything
+    that depends on A > 1 and that no few-step parity test sees has to be right for that: log pi summed over
+    both components, the target entropy -2, the second Box-Muller output of the noise pair, the action columns
+    of a replay record, the head's [mu | log sigma] split, the critics' [obs | act] input of width 12.
+    profiles/reacher_learning.txt holds the measured returns per seed and step count."""
+    r = learning_run(seed)
+    print(f"seed {seed}: untrained {r['untrained']:.3f} trained {r['trained']:.3f} bar {LEARNING_BAR:.3f} "
+          f"gradient_steps {r['gradient_steps']} train_wall_s {r['train_s']:.2f} total_s {r['total_s']:.2f}")
+    assert -70.0 <= r["untrained"] < LEARNING_BAR, r  # a return lies in [-100 (0.34 sqrt(2) + 0.2), 0]
+    assert LEARNING_BAR < r["trained"] <= 0.0, r
+
+
+# ---------------------------------------------------------------- 5. replica training
+@pytest.mark.parametrize("device_envs,graph_steps", [(True, 0), (True, 4), (False, 0)])
+def test_train_replica_on_reacher(device_envs, graph_steps):
+    """sac/train_replicas.py --env reacher, with and without --device-envs: one rank over RCCL."""
+    import socket
+
+    import torch.distributed as dist
+
+    from sac.train_replicas import env_factory, train_replica
+
+    with socket.socket() as s:
+        s.bind(("127.0.0.1", 0))
+        port = s.getsockname()[1]
+    cfg = _cfg(hidden=(32, 32), batch=16, warming=24, capacity=4096, seed=5)
+    torch.cuda.set_device(0)
+    dist.init_process_group("nccl", init_method=f"tcp://127.0.0.1:{port}", rank=0, world_size=1)
+    try:
+        out = train_replica(cfg, env_factory("reacher"), num_envs=4, env_steps=1000, every=64, rank=0,
+                            device="cuda:0", device_envs=device_envs, graph_steps=graph_steps)
+    finally:
+        dist.destroy_process_group()
+    m, agg = out["metrics"], out["aggregate"]
+    # 250 vector steps of 4 environments with episodes of 100 steps: two finished per environment
+    assert m["total_env_steps"] == 1000 and m["total_episodes"] == 8
+    assert m["gradient_steps"] == 1000 - 23 and -70.0 <= m["final_avg_return"] < 0.0
+    assert agg["world"] == 1 and agg["aggregations"] >= 1
