@@ -47,7 +47,7 @@
 extern "C" {
 #endif
 
-#define SAC_MAX_LAYERS 8
+#define SAC_MAX_LAYERS 8   /* slots of q_dims / pi_dims: the struct's layout.  The kernels take fewer: q_layers, pi_layers */
 
 enum sac_status {
   SAC_OK = 0,
@@ -70,10 +70,11 @@ enum sac_precision {
  * (sac.*, q_net.*, policy_net.*, train.batch_size; sac/agent.py:22-115). */
 typedef struct sac_engine_config {
   int32_t obs_dim, act_dim, batch;
-  int32_t q_layers;                         /* number of Linear layers of Q   */
+  int32_t q_layers;                         /* number of Linear layers of Q: 2..6 (one to five hidden layers);
+                                               anything else fails with SAC_E_INVALID, as for pi_layers */
   int32_t q_dims[SAC_MAX_LAYERS + 1];       /* q_dims[0]=obs+act ... q_dims[q_layers]=1 */
   int32_t q_hidden_act, q_out_act;
-  int32_t pi_layers;
+  int32_t pi_layers;                        /* number of Linear layers of pi: 2..6, independent of q_layers */
   int32_t pi_dims[SAC_MAX_LAYERS + 1];      /* pi_dims[0]=obs ... pi_dims[pi_layers]=2*act */
   int32_t pi_hidden_act, pi_out_act;
   float gamma, tau;

@@ -262,7 +262,10 @@ static PathChoice choose_path(const sac_engine_config* c, const NetShape& s, con
   // an explicit layout override runs the kernels it names or fails (as stage_path = -1 does)
   const char* refused = nullptr;
   if (c->layout == SAC_LAYOUT_ROLES && path != PATH_ROLES)
-    refused = "roles (needs 6 * row tiles <= 256 co-resident workgroups)";
+    refused = role_a_groups(nrt) > SAC_PLAN_CUS ? "roles (needs 6 * row tiles <= 256 co-resident workgroups)"
+              : !hand_fits                      ? "roles (a row tile's actions do not fit the hand-off payload)"
+              : too_big                         ? "roles (the R-row LDS layout does not fit: stage path)"
+                                                : "roles (stage_path = 1 selects the stage path)";
   if (c->layout == SAC_LAYOUT_PAIRS && path != PATH_PAIRS)
     refused = "pairs (the pair-tile LDS layout or record does not fit)";
   if (c->layout == SAC_LAYOUT_ROWS && path != PATH_ROWS) refused = "rows (the row-tile LDS layout does not fit: stage path)";

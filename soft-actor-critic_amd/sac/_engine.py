@@ -12,7 +12,8 @@ from typing import Optional, Sequence
 
 import torch
 
-MAX_LAYERS = 8
+MAX_LAYERS = 8  # slots of sac_engine_config.q_dims / pi_dims (SAC_MAX_LAYERS): the struct's layout
+DEV_LAYERS = 6  # Linear layers per network the library takes (SAC_DEV_LAYERS): 1..5 hidden layers
 PREC_FP32, PREC_BF16 = 0, 1
 
 _LIB_NAME = "libsac_engine.so"
@@ -236,3 +237,12 @@ def ptr(t: Optional[torch.Tensor]) -> ctypes.c_void_p:
 def net_dims(layers: Sequence[torch.nn.Linear]):
     dims = [layers[0].in_features] + [lin.out_features for lin in layers]
     return len(layers), dims
+
+
+def check_depth(**linear_layers: int) -> None:
+    """ValueError unless every named network has 2..DEV_LAYERS Linear layers,
+    the range sac_engine_create takes (1..5 hidden layers)."""
+    for name, n in linear_layers.items():
+        if not 2 <= n <= DEV_LAYERS:
+            raise ValueError(f"the engine takes 1 to {DEV_LAYERS - 1} hidden layers per network; "
+                             f"{name} has {n - 1}")

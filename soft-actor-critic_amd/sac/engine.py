@@ -71,6 +71,8 @@ class SacEngine:
         create), stage_path (1 force / -1 refuse the stage path),
         stage_batch (-1: phase A gathers its own batch), upd_parts (batch parts
         of the large-batch update tiles), upd_threads (512 / 1024)."""
+        # the library's depth limit, before anything is allocated or loaded
+        E.check_depth(q_net=len(q_net1.linears()), policy_net=len(policy_net.linears()))
         self.device = torch.device(device)
         E.require_gpu(self.device)
         self.lib = E.load_library()
@@ -103,8 +105,6 @@ class SacEngine:
         cfg.obs_dim, cfg.act_dim, cfg.batch = pi.obs_size, pi.action_size, self.batch
         ql, qd = E.net_dims(q.linears())
         pl, pd = E.net_dims(pi.linears())
-        if ql > E.MAX_LAYERS or pl > E.MAX_LAYERS:
-            raise ValueError(f"at most {E.MAX_LAYERS - 1} hidden layers are supported")
         cfg.q_layers, cfg.pi_layers = ql, pl
         for i, d in enumerate(qd):
             cfg.q_dims[i] = d

@@ -167,13 +167,17 @@ def build_engine(c, precision, seed=3, device=None, layout=None, replay=None):
     return eng, rb, c
 
 
+def layout_of(eng):
+    """The kernel family phases A and C of a build_engine engine run, by assert_layout's names."""
+    return "stage" if eng.wide else "split" if eng.split else "roles" if eng.roles else "pairs" if eng.pairs else "rows"
+
+
 def assert_layout(eng, want):
     """The kernel family phases A and C run: "split" (hidden-split role
     kernels), "roles" (per-network role kernels without the split), "rows"
     (one workgroup per row tile), "pairs" (pair tiles) or "stage" (the
     layer-synchronous stage path)."""
-    got = ("stage" if eng.wide else "split" if eng.split else "roles" if eng.roles else "pairs" if eng.pairs
-           else "rows")
+    got = layout_of(eng)
     flags = dict(split=eng.split, roles=eng.roles, pairs=eng.pairs, wide=eng.wide)
     assert got == want, (want, flags)
     # the flags exclude one another, except that the hidden split is a form of the role kernels

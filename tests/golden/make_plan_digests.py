@@ -19,7 +19,8 @@ The matrix (cases()):
   * the shapes and layout overrides of the GPU activation matrix
     (test_plan_cpu._activation_cases) with ReLU and with ELU hidden layers;
   * the five shapes of test_shapes_past_the_lds_layout_take_the_stage_path;
-  * edge shapes of the planner's own thresholds (EDGES below).
+  * edge shapes of the planner's own thresholds (EDGES below), the network
+    depths 1..5 and unequal depths of tests/_depth.py among them.
 """
 from __future__ import annotations
 
@@ -71,6 +72,30 @@ EDGES = {
     "stage_b4096_ncu256": (_edge(batch=4096, hidden=(512, 512)), {}, 256),  # the stages' K buffers depend on ncu
     "stage_b4096_ncu128": (_edge(batch=4096, hidden=(512, 512)), {}, 128),
 }
+
+
+def _depth_edges():
+    """Network depths 1..5 and unequal depths (tests/_depth.py): every case of
+    the GPU depth matrix on its layout, each shape as the engine plans it by
+    default, stage_path = 1 where a one-hidden-layer net makes it a no-op,
+    layout = roles refused by the LDS layout, and five wide hidden layers."""
+    import _depth
+
+    lay = {"layout": {"roles": 1, "rows": 2, "pairs": 3}}
+    out = {}
+    for case, (shape, over, _) in _depth.CASES.items():
+        out[f"depth_{case}"] = (shape, {k: lay.get(k, {}).get(v, v) for k, v in (over or {}).items()}, NCU)
+    for name, shape in _depth.SHAPES.items():
+        out[f"depth_{name}_default"] = (shape, {}, NCU)
+    for name in ("h1", "q1_pi3", "q5_pi1"):
+        out[f"depth_{name}_stage_ignored"] = (_depth.SHAPES[name], {"stage_path": 1}, NCU)
+    out["depth_h5_256_b40_roles_refused"] = (dict(_depth.SHAPES["h5_256"], batch=40), {"layout": 1}, NCU)
+    out["depth_512x5"] = (_edge(batch=64, hidden=(512,) * 5), {}, NCU)
+    out["depth_400_300x5_b1100"] = (_edge(batch=1100, obs=17, act=6, hidden=(400, 300, 400, 300, 400)), {}, NCU)
+    return out
+
+
+EDGES.update(_depth_edges())
 
 
 def cases():

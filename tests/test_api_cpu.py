@@ -72,6 +72,32 @@ def test_cpu_device_resolution(monkeypatch):
     assert resolve_device({"device": "cuda:0"}) == torch.device("cuda", 0)
 
 
+@pytest.mark.parametrize("deep", ["q", "pi"])
+def test_engine_refuses_a_sixth_hidden_layer_with_the_librarys_limit(deep):
+    """sac_engine_create takes one to five hidden layers per network: the Python
+    engine says so itself, with the number, before it touches a device, loads
+    the library or allocates (so it shows with or without a GPU); five hidden
+    layers pass that check and stop at the missing device."""
+    from _gpu import torch_nets
+    from sac import _engine as E
+    from sac.engine import SacEngine
+
+    def make(n):
+        c = dict(obs=5, act=3, q_hidden=[16, 16], pi_hidden=[16, 16])
+        c[f"{deep}_hidden"] = [16] * n
+        pi, q1, q2 = torch_nets(c)
+        return lambda: SacEngine(pi, q1, q2, copy.deepcopy(q1), copy.deepcopy(q2), batch_size=8, gamma=0.99, tau=0.005,
+                                 actor_lr=3e-4, critic_lr=3e-4, alpha_lr=3e-4, alpha=0.1, auto_entropy_tuning=True,
+                                 device="cpu")
+
+    assert E.DEV_LAYERS == 6 <= E.MAX_LAYERS
+    with pytest.raises(ValueError, match="1 to 5 hidden layers") as e:
+        make(6)()
+    assert ("q_net has 6" if deep == "q" else "policy_net has 6") in str(e.value)
+    with pytest.raises(E.EngineUnavailable):
+        make(5)()
+
+
 def test_substeps_need_the_engine():
     """The reference sub-steps run on the engine's device state: without a GPU
     they fail loudly like the fused step (no CPU fallback)."""

@@ -44,6 +44,8 @@ import numpy as np
 import pytest
 import torch
 
+import _depth
+
 pytestmark = pytest.mark.gpu
 
 DEV = torch.device("cuda", 0)
@@ -76,6 +78,12 @@ ENGINES = {
     "act32_roles": (dict(PAD, act=32), {"layout": "roles"}, "roles"),
     "act8_stage": (dict(PAD, act=8), {"stage_path": 1}, "stage"),
 }
+# network depths 1 and 5 (tests/_depth.py): the kernels' own layer loops with one hidden layer (the output layer is
+# layer 1) and with all SAC_DEV_LAYERS slots in use; q5_pi1: a one-layer policy on an LDS layout the five-layer
+# critics size; h1_256: one hidden layer of 256 (the hidden split refused by depth)
+DEPTH_ENGINES = ("h1_roles", "h1_rows", "h1_pairs", "h5_roles", "h5_pairs", "h5_stage", "q5_pi1_roles", "q5_pi1_rows",
+                 "h1_256_roles")
+ENGINES.update({k: (dict(_depth.CASES[k][0], capacity=64),) + _depth.CASES[k][1:] for k in DEPTH_ENGINES})
 ACTS = {"relu": dict(),
         "tanh": dict(pi_act="tanh", pi_out_act="tanh", log_std_min=-0.5, log_std_max=0.5, action_scale=2.5)}
 CASES = [(name, "relu") for name in ENGINES] + [(name, "tanh") for name in ("roles_pad", "pairs_pad", "stage_pad")]
@@ -309,7 +317,8 @@ def test_policy_head_in_saturation(name, acts, precision):
 
 # ---------------------------------------------------------------- 3. row independence
 @pytest.mark.parametrize("precision", ["fp32", "bf16"])
-@pytest.mark.parametrize("name", ["rows_pad", "pairs_pad", "pairs_deep", "stage_512", "split_c2", "act17"])
+@pytest.mark.parametrize("name", ["rows_pad", "pairs_pad", "pairs_deep", "stage_512", "split_c2", "act17",
+                                  "h1_roles", "h1_pairs", "h5_roles", "h5_stage", "q5_pi1_rows"])
 def test_rows_do_not_depend_on_their_tile(name, precision):
     eng, _, c = shared_engine(name, "relu", precision)
     n = 33
@@ -338,7 +347,8 @@ def test_rows_do_not_depend_on_their_tile(name, precision):
 
 # ---------------------------------------------------------------- 4. freshness
 @pytest.mark.parametrize("precision", ["fp32", "bf16"])
-@pytest.mark.parametrize("name", ["roles_pad", "rows_pad", "pairs_pad", "stage_pad", "stage_512", "split_c2"])
+@pytest.mark.parametrize("name", ["roles_pad", "rows_pad", "pairs_pad", "stage_pad", "stage_512", "split_c2",
+                                  "h1_roles", "h1_rows", "h1_pairs", "h5_roles", "h5_pairs", "h5_stage"])
 def test_policy_act_reads_the_updated_copies(name, precision):
     """A large actor step (actor_lr 3e-2) so that two gradient steps move the
     policy's outputs by more than the bound: after train, after train_graph and
@@ -380,7 +390,11 @@ def test_policy_act_reads_the_updated_copies(name, precision):
 ENVS = {"random_obs": ("random_obs_binary", dict(obs_dim=5, threshold=0.2, max_steps=4)),
         "point_mass": ("point_mass", dict(max_steps=7, dt=0.5, action_low=-1.0, action_high=1.0, goal_pos=0.5,
                                           goal_tolerance=0.2))}
-ROLLOUT_LAYOUTS = {"rows": {"layout": "rows"}, "pairs": {"layout": "pairs"}, "stage": {"stage_path": 1}, "roles": None}
+ROLLOUT_LAYOUTS = {"rows": {"layout": "rows"}, "pairs": {"layout": "pairs"}, "stage": {"stage_path": 1}, "roles": None,
+                   # "<depth>_<family>": a one-layer and a five-layer policy under the fused step
+                   "h1_roles": None, "h1_rows": {"layout": "rows"}, "h1_pairs": {"layout": "pairs"},
+                   "h5_roles": None, "h5_pairs": {"layout": "pairs"}, "h5_stage": {"stage_path": 1}}
+ROLLOUT_HIDDEN = {"": [64, 64], "h1": [64], "h5": [64, 40, 56, 24, 48]}
 
 
 @pytest.mark.parametrize("precision", ["fp32", "bf16"])
@@ -399,9 +413,11 @@ def test_fused_actions_match_policy_act(env, family, precision):
     dv = DeviceVectorEnv(kind, N, device=DEV, **kw)
     O = dv.obs_dim
     assert (O, dv.act_dim) == (5 if env == "random_obs" else 1, 1)
-    eng, _, c = build_engine(dict(obs=O, act=1, hidden=[64, 64], batch=17, capacity=64), precision, device=DEV,
-                             layout=ROLLOUT_LAYOUTS[family])
-    assert_layout(eng, family)
+    depth, _, kernels = family.rpartition("_")
+    eng, _, c = build_engine(dict(obs=O, act=1, hidden=ROLLOUT_HIDDEN[depth], batch=17, capacity=64), precision,
+                             device=DEV, layout=ROLLOUT_LAYOUTS[family])
+    assert_layout(eng, kernels)
+    assert len(eng.nets["pi"].linears()) == len(ROLLOUT_HIDDEN[depth]) + 1
     randomise(eng)
     lib = E.load_library()
     lib.sac_debug_rollout_eps_host.argtypes = [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int32, ctypes.c_int32,

@@ -15,6 +15,8 @@ import numpy as np
 import pytest
 import torch
 
+import _depth
+
 pytestmark = pytest.mark.gpu
 
 DEV = torch.device("cuda", 0)
@@ -56,6 +58,11 @@ SHAPES = {
     "act8_stage": (dict(obs=5, act=8, q_hidden=[72, 40], pi_hidden=[40, 72], batch=40, capacity=64),
                    {"stage_path": 1}, "stage"),
 }
+# critics of depth 1 and 5 (tests/_depth.py), with a policy as deep and with one of another depth (q1_pi3,
+# q5_pi1: the kernel's LDS layout is sized over all five nets), each on every layout the shape can take
+DEPTH_SHAPES = ("h1_roles", "h1_rows", "h1_pairs", "h5_roles", "h5_rows", "h5_pairs", "h5_stage",
+                "q1_pi3_roles", "q1_pi3_rows", "q1_pi3_pairs", "q5_pi1_roles", "q5_pi1_rows", "q5_pi1_pairs")
+SHAPES.update({k: (dict(_depth.CASES[k][0], capacity=64),) + _depth.CASES[k][1:] for k in DEPTH_SHAPES})
 ACTS = {"relu": dict(), "gelu_tanh": dict(q_act="gelu", q_out_act="tanh")}
 ROWS = (1, 16, 17, 33)  # one row, a full tile, a ragged tile, three tiles
 
@@ -174,7 +181,9 @@ def test_q_values_match_float64(shape, acts, precision):
 # ---------------------------------------------------------------- 2. row independence
 @pytest.mark.parametrize("precision", ["fp32", "bf16"])
 @pytest.mark.parametrize("shape,acts", [("pad_roles", "gelu_tanh"), ("c2", "relu"), ("deep", "relu"),
-                                        ("rows_pad", "relu"), ("pairs_deep", "relu"), ("stage_512", "relu")])
+                                        ("rows_pad", "relu"), ("pairs_deep", "relu"), ("stage_512", "relu"),
+                                        ("h1_pairs", "relu"), ("h5_stage", "gelu_tanh"), ("q5_pi1_rows", "relu"),
+                                        ("q1_pi3_roles", "gelu_tanh")])
 def test_rows_do_not_depend_on_their_tile(shape, acts, precision):
     eng, _, c = shared_engine(shape, acts, precision)
     n = 33
@@ -194,7 +203,8 @@ def test_rows_do_not_depend_on_their_tile(shape, acts, precision):
 
 # ---------------------------------------------------------------- 3. freshness
 @pytest.mark.parametrize("precision", ["fp32", "bf16"])
-@pytest.mark.parametrize("shape", ["pad_roles", "pad_stage", "c2", "rows_pad", "pairs_pad", "stage_512"])
+@pytest.mark.parametrize("shape", ["pad_roles", "pad_stage", "c2", "rows_pad", "pairs_pad", "stage_512",
+                                   "h1_roles", "h1_rows", "h1_pairs"])
 def test_q_values_read_the_updated_copies(shape, precision):
     """Large steps (critic_lr 3e-2, tau 0.5) so that two gradient steps move
     online and target values by more than the bound."""

@@ -230,6 +230,12 @@ def _plan(c, precision, **overrides):
     sac_engine_testing.h: no HIP call, with or without a GPU)."""
     import json
 
+    rc, text = _plan_text(c, precision, **overrides)
+    return rc, json.loads(text)["path"] if rc == 0 else text
+
+
+def _plan_text(c, precision, **overrides):
+    """(rc, the export's whole JSON text or the error message)."""
     lib = E.load_library()
     lib.sac_debug_plan_host.restype = ctypes.c_int
     lib.sac_debug_plan_host.argtypes = [ctypes.POINTER(E.EngineConfig), ctypes.c_int32, ctypes.c_char_p,
@@ -239,7 +245,7 @@ def _plan(c, precision, **overrides):
         setattr(cfg, k, v)
     buf = ctypes.create_string_buffer(1 << 16)
     rc = lib.sac_debug_plan_host(ctypes.byref(cfg), 256, buf, len(buf))
-    return rc, json.loads(buf.value)["path"] if rc == 0 else lib.sac_last_error().decode()
+    return rc, (buf.value if rc == 0 else lib.sac_last_error()).decode()
 
 
 PADH = dict(obs=5, q_hidden=[72, 40], pi_hidden=[40, 72], batch=40)  # tests/test_gpu_action_width.py's small shape
@@ -287,6 +293,121 @@ def test_shapes_past_the_lds_layout_need_act_up_to_8(shape, precision):
         assert _plan(dict(shape, act=8), precision) == (0, "wide")
     rc, msg = _plan(shape, precision)
     assert rc == SAC_E_INVALID and "B of LDS per workgroup (max 163840)" in msg, (rc, msg)
+
+
+# ---------------------------------------------------------------- network depths (tests/_depth.py)
+PATH_OF = {"roles": "roles", "rows": "rows", "pairs": "pairs", "stage": "wide"}
+DEPTH_SMALL = ("h1", "h4", "h5", "q1_pi3", "q5_pi1", "q2_pi5", "q5_pi2")  # obs 5, act 3, B = 40
+
+
+def _depth_paths():
+    """(id, shape name, overrides, the planner's path): the small shapes by
+    default and on each forced layout; stage_path = 1, honoured where both
+    nets have two hidden layers or more and ignored elsewhere; the 256-wide
+    and the B = 1100 shapes; and every case of the GPU matrix."""
+    import _depth
+
+    t = []
+    for s in DEPTH_SMALL:
+        t += [(f"{s}/default", s, {}, "roles"), (f"{s}/layout=1", s, {"layout": 1}, "roles"),
+              (f"{s}/layout=2", s, {"layout": 2}, "rows"), (f"{s}/layout=3", s, {"layout": 3}, "pairs")]
+    t += [(f"{s}/stage_path=1", s, {"stage_path": 1}, "wide") for s in ("h4", "h5", "q2_pi5", "q5_pi2")]
+    t += [(f"{s}/stage_path=1", s, {"stage_path": 1}, "roles") for s in ("h1", "q1_pi3", "q5_pi1")]
+    t += [("h1_256/default", "h1_256", {}, "roles"),  # the hidden split refused by depth
+          ("h5_256/default", "h5_256", {}, "wide"),  # the R-row layout does not fit
+          ("h1_b1100/default", "h1_b1100", {}, "pairs"), ("h1_b1100/stage_path=1", "h1_b1100", {"stage_path": 1}, "pairs"),
+          ("h5_b1100/default", "h5_b1100", {}, "pairs")]
+    for case, (shape, lay, family) in sorted(_depth.CASES.items()):
+        kv = {k: E.LAYOUTS[v] if k == "layout" else int(v) for k, v in (lay or {}).items()}
+        t.append((f"case/{case}", _depth.SHAPE_OF[case], kv, PATH_OF[family]))
+    return t
+
+
+@pytest.mark.parametrize("precision", ["fp32", "bf16"])
+@pytest.mark.parametrize("shape,kv,path", [p[1:] for p in _depth_paths()], ids=[p[0] for p in _depth_paths()])
+def test_depths_1_to_5_are_planned_on_the_expected_path(shape, kv, path, precision):
+    import _depth
+
+    assert _plan(_depth.SHAPES[shape], precision, **kv) == (0, path)
+
+
+@pytest.mark.parametrize("precision", ["fp32", "bf16"])
+def test_stage_path_override_is_ignored_at_one_hidden_layer(precision):
+    """stage_path = 1 where a net has one hidden layer: the same plan as
+    without it, byte for byte, and no error; create accepts it too."""
+    import _depth
+
+    for shape in ("h1", "q1_pi3", "q5_pi1", "h1_b1100", "h1_256"):
+        c = _depth.SHAPES[shape]
+        plain, forced = _plan_text(c, precision), _plan_text(c, precision, stage_path=1)
+        assert plain[0] == 0 and forced == plain, (shape, forced)
+        rc, msg = _create(_cfg_of(c, precision), stage_path=1)
+        assert rc == SAC_E_HIP and "internal" not in msg, (shape, rc, msg)
+
+
+def _create(cfg, **overrides):
+    """(rc, message) of sac_engine_create on fake buffers: the planner runs
+    whole before the first HIP call, where a machine without a GPU stops."""
+    for k, v in overrides.items():
+        setattr(cfg, k, v)
+    lib = E.load_library()
+    ws = lib.sac_engine_workspace_bytes(ctypes.byref(cfg))
+    bufs = E.EngineBuffers(*([0x1000] * 15), 0x100000, max(ws, 1))
+    out = ctypes.c_void_p()
+    rc = lib.sac_engine_create(ctypes.byref(cfg), ctypes.byref(bufs), None, ctypes.byref(out))
+    if rc == 0:
+        lib.sac_engine_destroy(out)
+        pytest.skip("GPU present: the planner ran for real")
+    return rc, lib.sac_last_error().decode()
+
+
+@pytest.mark.parametrize("net", ["q", "pi"])
+def test_six_hidden_layers_are_refused(net):
+    """The library takes 2..6 Linear layers per network (SAC_DEV_LAYERS): a
+    sixth hidden layer of either net fails validation in the workspace query
+    and in create, before any HIP call."""
+    c = dict(obs=5, act=3, batch=40, q_hidden=[72, 40], pi_hidden=[40, 72])
+    c[f"{net}_hidden"] = [32] * 6
+    cfg = _cfg_of(c, "fp32")
+    assert max(cfg.q_layers, cfg.pi_layers) == 7
+    lib = E.load_library()
+    assert lib.sac_engine_workspace_bytes(ctypes.byref(cfg)) == 0
+    assert "1..5 hidden layers" in lib.sac_last_error().decode()
+    rc, msg = _create(cfg)
+    assert rc == SAC_E_INVALID and "1..5 hidden layers" in msg, (rc, msg)
+    rc, msg = _plan(c, "fp32")
+    assert rc == SAC_E_INVALID and "1..5 hidden layers" in msg, (rc, msg)
+    c[f"{net}_hidden"] = [32] * 5  # the limit itself is planned
+    assert _plan(c, "fp32")[0] == 0
+
+
+@pytest.mark.parametrize("precision", ["fp32", "bf16"])
+@pytest.mark.parametrize("c", [dict(obs=24, act=4, hidden=[512] * 5, batch=64),
+                               dict(obs=17, act=6, hidden=[400, 300, 400, 300, 400], batch=1100)],
+                         ids=["512x5", "400_300x5_b1100"])
+def test_five_wide_hidden_layers_take_the_stage_path(c, precision):
+    """Five hidden layers past the phase kernels' LDS layout: the stage path's
+    job list grows with the depth (WIDE_MAX_JOBS) and the update tiles' tables
+    with it; the planner's own consistency check ("internal: ...") stays
+    quiet, in the host-only export and in create."""
+    assert _plan(c, precision) == (0, "wide")
+    rc, msg = _create(_cfg_of(c, precision))
+    assert "internal" not in msg, msg
+    assert rc == SAC_E_HIP, (rc, msg)
+
+
+@pytest.mark.parametrize("precision", ["fp32", "bf16"])
+def test_a_refused_roles_override_names_the_cause_that_applies(precision):
+    """layout = roles at [256] * 5, B = 40: three row tiles are 18 co-resident
+    workgroups, well inside 256; what refuses the role kernels is their R-row
+    LDS layout, and the message says so.  C3's 256 row tiles keep the
+    workgroup count as their cause."""
+    import _depth
+
+    rc, msg = _plan(dict(_depth.SHAPES["h5_256"], batch=40), precision, layout=1)
+    assert rc == SAC_E_INVALID and "cannot be honoured: roles (the R-row LDS layout does not fit" in msg, (rc, msg)
+    rc, msg = _plan(bench.CONFIGS["c3"], precision, layout=1)
+    assert rc == SAC_E_INVALID and "roles (needs 6 * row tiles <= 256 co-resident workgroups)" in msg, (rc, msg)
 
 
 def test_engine_library_reads_no_environment():
