@@ -301,17 +301,37 @@ const char *sac_phase_kernel_name(int32_t phase);
  * = 0.14 (2 u1 - 1), th1 = pi (2 u2 - 1), th2 = pi (2 u3 - 1) in double, w = 0.
  * Codes 9..15 are not assigned.
  *
+ * SAC_ENV_CARTPOLE is the one kind that ends by FAILURE: the classic balancing
+ * cart-pole (sac/control_envs.py CartPoleEnv; G = 9.8, M_CART = 1, M_POLE = 0.1,
+ * HALF_LEN = 0.5, FORCE_MAG = 10, X_LIMIT = 2.4, TH_LIMIT = 12 degrees, all
+ * compile-time constants).  State (x, xdot, th, thdot) in float64, one force
+ * component: with u the action clipped to [action_low, action_high], F = 10 u,
+ * c = cos th, s = sin th, M = 1.1, temp = (F + 0.05 thdot^2 s) / M, thacc =
+ * (G s - c temp) / (0.5 (4/3 - 0.1 c^2 / M)), xacc = temp - 0.05 thacc c / M, an
+ * explicit Euler step x' = x + dt xdot, xdot' = xdot + dt xacc, th' = th + dt
+ * thdot, thdot' = thdot + dt thacc.  Reward 1.0 on every step; terminated when
+ * |x'| > X_LIMIT or |th'| > TH_LIMIT, truncated at max_steps (independently:
+ * both may be set).  The observation is fp32 (x, xdot, th, thdot) of the new
+ * state (obs_dim = 4).  State: sac_envs.pos is [2][num_envs] doubles (x, th),
+ * sac_envs.vel is [2][num_envs] doubles (xdot, thdot).  RNG: which = 4, block 0
+ * at vector step t is the reset draw, its four uniforms exactly one block: x,
+ * xdot, th, thdot = 0.05 (2 u_k - 1) in double, k = 0..3.  sin th and cos th
+ * feed back into the state, so the device's trajectory follows the host class's
+ * to a few float64 ulps, not to the bit.  Codes 17..31 are not assigned.
+ *
  * Per-kind widths          actions  obs_dim   pos doubles / env   vel doubles / env
  *   the probes (0..3)         1     1 (2: any)       1              - (may be NULL)
  *   SAC_ENV_PENDULUM          1        3             1                    1
- *   SAC_ENV_REACHER           2       10             4                    2         */
+ *   SAC_ENV_REACHER           2       10             4                    2
+ *   SAC_ENV_CARTPOLE          1        4             2                    2         */
 enum sac_env_kind {
   SAC_ENV_CONSTANT_REWARD = 0,  /* envs.py ConstantRewardEnv: r = reward, terminated at max_steps */
   SAC_ENV_QUADRATIC_ACTION = 1, /* QuadraticActionRewardEnv: r = -(clip(a) - target)^2 in fp32 */
   SAC_ENV_RANDOM_OBS = 2,       /* RandomObsBinaryRewardEnv: uniform obs, r = +1 iff |a| <= threshold */
   SAC_ENV_POINT_MASS = 3,       /* OneDPointMassReachEnv: pos += clip(a) * dt, reach goal_pos */
   SAC_ENV_PENDULUM = 8,         /* control_envs.py PendulumEnv: swing-up, obs (cos th, sin th, thdot) */
-  SAC_ENV_REACHER = 16          /* control_envs.py ReacherEnv: two-link arm, two torques, obs_dim 10 */
+  SAC_ENV_REACHER = 16,         /* control_envs.py ReacherEnv: two-link arm, two torques, obs_dim 10 */
+  SAC_ENV_CARTPOLE = 32         /* control_envs.py CartPoleEnv: balance, +1 per step, ends by failure, obs_dim 4 */
 };
 
 /* Action components an environment of `kind` takes: the act_dim its replay buffer and engine must have. */
@@ -322,18 +342,20 @@ enum sac_env_kind {
 typedef struct sac_env_config {
   int32_t kind;                 /* enum sac_env_kind */
   int32_t num_envs;
-  int32_t obs_dim;              /* 1, except SAC_ENV_RANDOM_OBS (its obs_dim argument), SAC_ENV_PENDULUM (3) and
-                                   SAC_ENV_REACHER (10) */
+  int32_t obs_dim;              /* 1, except SAC_ENV_RANDOM_OBS (its obs_dim argument), SAC_ENV_PENDULUM (3),
+                                   SAC_ENV_REACHER (10) and SAC_ENV_CARTPOLE (4) */
   int32_t max_steps;
   double reward;                              /* SAC_ENV_CONSTANT_REWARD */
   double target;                              /* SAC_ENV_QUADRATIC_ACTION */
   double action_low, action_high;             /* SAC_ENV_QUADRATIC_ACTION, SAC_ENV_POINT_MASS, SAC_ENV_PENDULUM and
-                                                 SAC_ENV_REACHER (-max_torque, max_torque; every component) */
+                                                 SAC_ENV_REACHER (-max_torque, max_torque; every component),
+                                                 SAC_ENV_CARTPOLE (-max_action, max_action) */
   double threshold;                           /* SAC_ENV_RANDOM_OBS */
   double start_pos, goal_pos, dt, step_penalty, goal_reward, goal_tolerance;  /* SAC_ENV_POINT_MASS; dt also
-                                                                                 SAC_ENV_PENDULUM, SAC_ENV_REACHER */
-  uint64_t seed;                /* observation draws of SAC_ENV_RANDOM_OBS, reset draws of SAC_ENV_PENDULUM and
-                                   SAC_ENV_REACHER */
+                                                                                 SAC_ENV_PENDULUM, SAC_ENV_REACHER,
+                                                                                 SAC_ENV_CARTPOLE */
+  uint64_t seed;                /* observation draws of SAC_ENV_RANDOM_OBS, reset draws of SAC_ENV_PENDULUM,
+                                   SAC_ENV_REACHER and SAC_ENV_CARTPOLE */
 } sac_env_config;
 
 /* One cell of the episode record: written by every environment on every step. */
@@ -350,18 +372,20 @@ typedef struct sac_envs {
   int32_t *step;                /* [num_envs] step in the episode (envs.py current_step) */
   int32_t *ep_length;           /* [num_envs] length of the running episode */
   double *pos;                  /* [num_envs] SAC_ENV_POINT_MASS position; SAC_ENV_PENDULUM angle th;
-                                   SAC_ENV_REACHER [4][num_envs]: th1, th2, tx, ty */
+                                   SAC_ENV_REACHER [4][num_envs]: th1, th2, tx, ty; SAC_ENV_CARTPOLE
+                                   [2][num_envs]: x, th */
   double *ep_return;            /* [num_envs] return of the running episode */
   sac_env_episode *episodes;    /* [ring_steps][num_envs] dense ring indexed by t % ring_steps and env row;
                                    NULL: no record (sac_envs_step only) */
   int64_t ring_steps;
   double *vel;                  /* [num_envs] SAC_ENV_PENDULUM angular velocity thdot; SAC_ENV_REACHER
-                                   [2][num_envs]: w1, w2; may be NULL for the probes */
+                                   [2][num_envs]: w1, w2; SAC_ENV_CARTPOLE [2][num_envs]: xdot, thdot; may be NULL
+                                   for the probes */
 } sac_envs;
 
 /* Reset every environment: step and episode counters to 0, the initial
- * observation (draws of SAC_ENV_RANDOM_OBS, SAC_ENV_PENDULUM and SAC_ENV_REACHER:
- * which = 4, t = 0, key `seed`).
+ * observation (draws of SAC_ENV_RANDOM_OBS, SAC_ENV_PENDULUM, SAC_ENV_REACHER and
+ * SAC_ENV_CARTPOLE: which = 4, t = 0, key `seed`).
  * Replaces: SyncVectorEnv.reset (sac/vector_env.py:39-46). */
 int sac_envs_reset(const sac_envs *envs, uint64_t seed, void *stream);
 

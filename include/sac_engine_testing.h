@@ -96,6 +96,22 @@ int sac_debug_reacher_step_host(const sac_env_config *cfg, double state[6], int3
  * fourth uniform of sac_debug_env_obs_host's which = 4 block 0, w1 = w2 = 0,
  * (tx, ty) = 0.14 (2 u - 1) of its first and second. */
 int sac_debug_reacher_reset_host(uint64_t seed, uint64_t t, int32_t row, double state_out[6]);
+/* One step of SAC_ENV_CARTPOLE on the host: the inline dynamics the device
+ * kernels call (csrc/sac_envs.h cartpole_dynamics), compiled for the host, so
+ * sin / cos are the host libm's.  cfg supplies action_low, action_high, dt and
+ * max_steps (kind must be SAC_ENV_CARTPOLE); state = (x, xdot, th, thdot), the
+ * order of CartPoleEnv.state, is advanced in place; `step` is the step in the
+ * episode before this one.  Outputs: the observation stepped to, the reward
+ * (1.0), terminated = the new state is outside a limit, truncated = step + 1 >=
+ * max_steps (both may be set).  No autoreset: the caller applies the reset draw
+ * below. */
+int sac_debug_cartpole_step_host(const sac_env_config *cfg, double state[4], int32_t step, const float action[1],
+                                 float obs_out[4], double *reward, int32_t *terminated, int32_t *truncated);
+/* The reset state of SAC_ENV_CARTPOLE row `row` at vector step t (t = 0: the
+ * initial reset) for environment seed `seed`, in the same order: the same
+ * inline code as the device's, 0.05 (2 u_k - 1) of the four uniforms of
+ * sac_debug_env_obs_host's which = 4 block 0. */
+int sac_debug_cartpole_reset_host(uint64_t seed, uint64_t t, int32_t row, double state_out[4]);
 /* A host-only engine: the validated config and no device state (no HIP call is
  * made).  For the argument checks of the forward-only entry points --
  * sac_q_values, sac_q_values_replay, sac_policy_act and sac_rollout_step -- on

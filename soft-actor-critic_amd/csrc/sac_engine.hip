@@ -324,13 +324,15 @@ static int validate(const sac_engine_config* c) {
 // The rollout kernels' instantiation for a kind class (sac_envs.h EnvClass)
 template <typename T>
 static auto rollout_kernel(int kc) {
-  return kc == ENV_CLASS_REACHER    ? sac_rollout_step_kernel<T, ENV_CLASS_REACHER>
+  return kc == ENV_CLASS_CARTPOLE   ? sac_rollout_step_kernel<T, ENV_CLASS_CARTPOLE>
+         : kc == ENV_CLASS_REACHER  ? sac_rollout_step_kernel<T, ENV_CLASS_REACHER>
          : kc == ENV_CLASS_PENDULUM ? sac_rollout_step_kernel<T, ENV_CLASS_PENDULUM>
                                     : sac_rollout_step_kernel<T, ENV_CLASS_PROBES>;
 }
 template <typename T>
 static auto rollout_dev_kernel(int kc) {
-  return kc == ENV_CLASS_REACHER    ? sac_rollout_step_dev_kernel<T, ENV_CLASS_REACHER>
+  return kc == ENV_CLASS_CARTPOLE   ? sac_rollout_step_dev_kernel<T, ENV_CLASS_CARTPOLE>
+         : kc == ENV_CLASS_REACHER  ? sac_rollout_step_dev_kernel<T, ENV_CLASS_REACHER>
          : kc == ENV_CLASS_PENDULUM ? sac_rollout_step_dev_kernel<T, ENV_CLASS_PENDULUM>
                                     : sac_rollout_step_dev_kernel<T, ENV_CLASS_PROBES>;
 }
@@ -344,7 +346,7 @@ static void set_lds_attrs(size_t bytes) {
   (void)hipFuncSetAttribute((const void*)sac_actor<T, false>, hipFuncAttributeMaxDynamicSharedMemorySize, b);
   (void)hipFuncSetAttribute((const void*)sac_actor<T, true>, hipFuncAttributeMaxDynamicSharedMemorySize, b);
   (void)hipFuncSetAttribute((const void*)sac_policy_act_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, b);
-  for (int kc = ENV_CLASS_PROBES; kc <= ENV_CLASS_REACHER; ++kc) {
+  for (int kc = ENV_CLASS_PROBES; kc <= ENV_CLASS_CARTPOLE; ++kc) {
     (void)hipFuncSetAttribute((const void*)rollout_kernel<T>(kc), hipFuncAttributeMaxDynamicSharedMemorySize, b);
     (void)hipFuncSetAttribute((const void*)rollout_dev_kernel<T>(kc), hipFuncAttributeMaxDynamicSharedMemorySize, b);
   }
@@ -513,7 +515,8 @@ static int check_envs(const sac_envs* ev, bool need_ring) {
   if (!ev) return fail(SAC_E_INVALID, "null environments");
   const sac_env_config& c = ev->cfg;
   const bool pendulum = c.kind == SAC_ENV_PENDULUM, reacher = c.kind == SAC_ENV_REACHER;
-  if ((c.kind < SAC_ENV_CONSTANT_REWARD || c.kind > SAC_ENV_POINT_MASS) && !pendulum && !reacher)
+  const bool cartpole = c.kind == SAC_ENV_CARTPOLE;
+  if ((c.kind < SAC_ENV_CONSTANT_REWARD || c.kind > SAC_ENV_POINT_MASS) && !pendulum && !reacher && !cartpole)
     return fail(SAC_E_INVALID, "unknown environment kind " + std::to_string(c.kind));
   if (c.num_envs < 1) return fail(SAC_E_INVALID, "num_envs >= 1");
   if (c.max_steps < 1) return fail(SAC_E_INVALID, "max_steps >= 1");
@@ -521,10 +524,12 @@ static int check_envs(const sac_envs* ev, bool need_ring) {
     return fail(SAC_E_INVALID, "obs_dim must be 3 for SAC_ENV_PENDULUM");
   if (reacher && c.obs_dim != SAC_REACHER_OBS_DIM)
     return fail(SAC_E_INVALID, "obs_dim must be 10 for SAC_ENV_REACHER");
-  if (!pendulum && !reacher && (c.kind == SAC_ENV_RANDOM_OBS ? (c.obs_dim < 1 || c.obs_dim > 4 * 65536) : c.obs_dim != 1))
+  if (cartpole && c.obs_dim != SAC_CARTPOLE_OBS_DIM)
+    return fail(SAC_E_INVALID, "obs_dim must be 4 for SAC_ENV_CARTPOLE");
+  if (!pendulum && !reacher && !cartpole && (c.kind == SAC_ENV_RANDOM_OBS ? (c.obs_dim < 1 || c.obs_dim > 4 * 65536) : c.obs_dim != 1))
     return fail(SAC_E_INVALID, "obs_dim must be 1 (SAC_ENV_RANDOM_OBS: 1..262144)");
   if (!ev->obs || !ev->step || !ev->ep_length || !ev->pos || !ev->ep_return ||
-      ((pendulum || reacher) && !ev->vel))
+      ((pendulum || reacher || cartpole) && !ev->vel))
     return fail(SAC_E_INVALID, "null environment state");
   if (need_ring ? (!ev->episodes || ev->ring_steps < 1) : (ev->episodes && ev->ring_steps < 1))
     return fail(SAC_E_INVALID, "episode ring needs episodes != NULL and ring_steps >= 1");
@@ -1112,6 +1117,24 @@ int sac_debug_reacher_step_host(const sac_env_config* cfg, double state[6], int3
 int sac_debug_reacher_reset_host(uint64_t seed, uint64_t t, int32_t row, double state_out[6]) {
   if (!state_out || row < 0) return fail(SAC_E_INVALID, "need row >= 0 and state_out != NULL");
   reacher_reset_draw(seed, t, (uint32_t)row, state_out);
+  return SAC_OK;
+}
+
+int sac_debug_cartpole_step_host(const sac_env_config* cfg, double state[4], int32_t step, const float action[1],
+                                 float obs_out[4], double* reward, int32_t* terminated, int32_t* truncated) {
+  if (!cfg || !state || !action || !obs_out || !reward || !terminated || !truncated)
+    return fail(SAC_E_INVALID, "need cfg, state, action, obs_out, reward, terminated and truncated != NULL");
+  if (cfg->kind != SAC_ENV_CARTPOLE) return fail(SAC_E_INVALID, "cartpole_step_host: kind must be SAC_ENV_CARTPOLE");
+  if (cfg->max_steps < 1 || step < 0) return fail(SAC_E_INVALID, "cartpole_step_host: max_steps >= 1 and step >= 0");
+  *terminated = cartpole_dynamics(state, action[0], cfg->action_low, cfg->action_high, cfg->dt, obs_out) ? 1 : 0;
+  *reward = 1.0;
+  *truncated = step + 1 >= cfg->max_steps ? 1 : 0;
+  return SAC_OK;
+}
+
+int sac_debug_cartpole_reset_host(uint64_t seed, uint64_t t, int32_t row, double state_out[4]) {
+  if (!state_out || row < 0) return fail(SAC_E_INVALID, "need row >= 0 and state_out != NULL");
+  cartpole_reset_draw(seed, t, (uint32_t)row, state_out);
   return SAC_OK;
 }
 

@@ -1,9 +1,10 @@
 // sac_envs.h — the probe environments of sac/envs.py and the Pendulum swing-up
-// and two-link reacher of sac/control_envs.py on the device, and the fused
-// rollout step (act -> step -> store in one launch).
+// two-link reacher and balancing cart-pole of sac/control_envs.py on the
+// device, and the fused rollout step (act -> step -> store in one launch).
 //
 //   * pendulum_dynamics: one step of the swing-up in float64, host-callable;
 //   * reacher_dynamics: one step of the reacher (two action components), likewise;
+//   * cartpole_dynamics: one step of the cart-pole (the kind that terminates by failure), likewise;
 //   * env_step: ONE statement of the environments' dynamics, with the semantics
 //     sac.vector_env.SyncVectorEnv gives the host classes (same-step autoreset;
 //     the transition is (obs, action, reward, final_obs, terminated | truncated)).
@@ -14,7 +15,7 @@
 //     (same workgroup shape, LDS layout and mlp_forward call); the thread that
 //     owns environment row i samples its action, steps the environment and
 //     writes the transition into the replay ring.  Compiled once per kind class
-//     KC (the probes, the pendulum, the reacher); the host picks by the
+//     KC (the probes, the pendulum, the reacher, the cart-pole); the host picks by the
 //     environments' kind;
 //   * sac_rollout_step_dev_kernel<T, KC>: the same body with (size, pos,
 //     t) read from a two-slot cursor in device memory, so whole loop iterations
@@ -32,9 +33,12 @@
 // (1,), and so has the pendulum's) except the reacher's 2.
 __host__ __device__ inline int env_act_dim(int kind) { return SAC_ENV_ACT_DIM(kind); }
 // The rollout kernels are compiled once per kind class, so no class holds another's code.
-enum EnvClass { ENV_CLASS_PROBES = 0, ENV_CLASS_PENDULUM = 1, ENV_CLASS_REACHER = 2 };
+enum EnvClass { ENV_CLASS_PROBES = 0, ENV_CLASS_PENDULUM = 1, ENV_CLASS_REACHER = 2, ENV_CLASS_CARTPOLE = 3 };
 inline int env_class(int kind) {
-  return kind == SAC_ENV_PENDULUM ? ENV_CLASS_PENDULUM : (kind == SAC_ENV_REACHER ? ENV_CLASS_REACHER : ENV_CLASS_PROBES);
+  return kind == SAC_ENV_PENDULUM   ? ENV_CLASS_PENDULUM
+         : kind == SAC_ENV_REACHER  ? ENV_CLASS_REACHER
+         : kind == SAC_ENV_CARTPOLE ? ENV_CLASS_CARTPOLE
+                                    : ENV_CLASS_PROBES;
 }
 // Philox `which` values of the rollout (0 / 1 are the training draws)
 #define ENV_WHICH_NOISE 2u  // action noise of a rollout step, key = engine seed
@@ -189,6 +193,71 @@ __device__ __forceinline__ void reacher_store(const sac_envs& ev, int i, const d
   ev.pos[3 * n + i] = s[5];
 }
 
+// ---- Balancing cart-pole (sac/control_envs.py CartPoleEnv) ------------------
+// State s = (x, xdot, th, thdot) in float64, the order of CartPoleEnv.state.
+// Every operation is the host class's, in its order.  sin th and cos th feed
+// back into the state, so the trajectory follows the host's to the library's
+// few float64 ulps, not to the bit.
+#define SAC_CARTPOLE_OBS_DIM 4
+#define SAC_CARTPOLE_G 9.8
+#define SAC_CARTPOLE_M_CART 1.0
+#define SAC_CARTPOLE_M_POLE 0.1
+#define SAC_CARTPOLE_HALF_LEN 0.5
+#define SAC_CARTPOLE_FORCE_MAG 10.0
+#define SAC_CARTPOLE_X_LIMIT 2.4
+#define SAC_CARTPOLE_TH_LIMIT (12.0 * 2.0 * SAC_PI / 360.0)
+#define SAC_CARTPOLE_RESET_HALF_SIDE 0.05
+
+// The observation of a state, in fp32
+__host__ __device__ inline void cartpole_obs(const double s[4], float obs[SAC_CARTPOLE_OBS_DIM]) {
+  for (int k = 0; k < SAC_CARTPOLE_OBS_DIM; ++k) obs[k] = (float)s[k];
+}
+
+// One Euler step from s with action a: the new state in place, its observation
+// in fp32; returns terminated (the new state is outside a limit).  The reward
+// is 1.0 on every step, the failing one included.
+__host__ __device__ inline bool cartpole_dynamics(double s[4], float a, double action_low, double action_high,
+                                                  double dt, float obs[SAC_CARTPOLE_OBS_DIM]) {
+  const double u = (double)clip_f32(a, (float)action_low, (float)action_high);
+  const double x = s[0], xdot = s[1], th = s[2], thdot = s[3];
+  const double F = SAC_CARTPOLE_FORCE_MAG * u, c = cos(th), sn = sin(th);
+  const double M = SAC_CARTPOLE_M_CART + SAC_CARTPOLE_M_POLE;
+  const double temp = (F + SAC_CARTPOLE_M_POLE * SAC_CARTPOLE_HALF_LEN * thdot * thdot * sn) / M;
+  const double thacc =
+      (SAC_CARTPOLE_G * sn - c * temp) / (SAC_CARTPOLE_HALF_LEN * (4.0 / 3.0 - SAC_CARTPOLE_M_POLE * c * c / M));
+  const double xacc = temp - SAC_CARTPOLE_M_POLE * SAC_CARTPOLE_HALF_LEN * thacc * c / M;
+  s[0] = x + dt * xdot;
+  s[1] = xdot + dt * xacc;
+  s[2] = th + dt * thdot;
+  s[3] = thdot + dt * thacc;
+  cartpole_obs(s, obs);
+  return fabs(s[0]) > SAC_CARTPOLE_X_LIMIT || fabs(s[2]) > SAC_CARTPOLE_TH_LIMIT;
+}
+
+// The reset draw of env row `row` at vector step t: the four uniforms of the
+// row's ENV_WHICH_RESET block 0 give x, xdot, th, thdot in [-0.05, 0.05).
+__host__ __device__ inline void cartpole_reset_draw(uint64_t seed, uint64_t t, uint32_t row, double s[4]) {
+  float u[4];
+  philox_uniform4(seed, t, row, ENV_WHICH_RESET, 0, u);
+  for (int k = 0; k < 4; ++k) s[k] = SAC_CARTPOLE_RESET_HALF_SIDE * (2.0 * (double)u[k] - 1.0);
+}
+
+// Row i's state in the component-major blocks ev.pos [2][N] (x, th) and ev.vel [2][N] (xdot, thdot)
+__device__ __forceinline__ void cartpole_load(const sac_envs& ev, int i, double s[4]) {
+  const size_t n = (size_t)ev.cfg.num_envs;
+  s[0] = ev.pos[i];
+  s[1] = ev.vel[i];
+  s[2] = ev.pos[n + i];
+  s[3] = ev.vel[n + i];
+}
+__device__ __forceinline__ void cartpole_store(const sac_envs& ev, int i, const double s[4]) {
+  const size_t n = (size_t)ev.cfg.num_envs;
+  ev.pos[i] = s[0];
+  ev.vel[i] = s[1];
+  ev.pos[n + i] = s[2];
+  ev.vel[n + i] = s[3];
+}
+
 struct EnvOut {
   double reward;  // as the host class returns it (probe 1's fp32 reward widened, as float(r) does)
   bool terminated, truncated;
@@ -249,20 +318,49 @@ __device__ __forceinline__ EnvOut env_step_reacher(const sac_envs& ev, int i, ui
   return o;
 }
 
+// The cart-pole's step of env_step: the one kind whose rows end by failure, each at its own step;
+// terminated and truncated are independent, and a row that ended either way takes its reset draw of
+// this t.
+__device__ __forceinline__ EnvOut env_step_cartpole(const sac_envs& ev, int i, uint64_t t, float action,
+                                                    float* final_obs) {
+  const sac_env_config& c = ev.cfg;
+  const int step = ev.step[i] + 1;
+  float* cur = ev.obs + (size_t)i * SAC_CARTPOLE_OBS_DIM;
+  double s[4];
+  cartpole_load(ev, i, s);
+  float fo[SAC_CARTPOLE_OBS_DIM];
+  EnvOut o;
+  o.terminated = cartpole_dynamics(s, action, c.action_low, c.action_high, c.dt, fo);
+  o.reward = 1.0;
+  o.truncated = step >= c.max_steps;
+  const bool done = o.terminated || o.truncated;
+  if (final_obs)
+    for (int k = 0; k < SAC_CARTPOLE_OBS_DIM; ++k) final_obs[k] = fo[k];
+  if (done) {
+    cartpole_reset_draw(c.seed, t, (uint32_t)i, s);
+    cartpole_obs(s, fo);
+  }
+  for (int k = 0; k < SAC_CARTPOLE_OBS_DIM; ++k) cur[k] = fo[k];
+  ev.step[i] = done ? 0 : step;
+  cartpole_store(ev, i, s);
+  return o;
+}
+
 // One step of environment row i at vector step t with the action's first
 // component `action` (and its second, a1, for the one kind that takes two).
 // Writes the observation stepped to into final_obs[obs_dim] (unless NULL), the
 // environment's new current observation (the reset observation where the
 // episode ended) into ev.obs, and its step counter / position.
 // KC is the kind class (EnvClass), decided by the launch: the rollout kernels are
-// compiled once per class, so the probes' kernels hold none of the pendulum's or
-// the reacher's code (behind a run-time branch the pendulum cost them 16 more
+// compiled once per class, so the probes' kernels hold none of the pendulum's, the
+// reacher's or the cart-pole's code (behind a run-time branch the pendulum cost them 16 more
 // spilled SGPRs and 1-2 % per launch).
 template <int KC>
 __device__ __forceinline__ EnvOut env_step(const sac_envs& ev, int i, uint64_t t, float action, float a1,
                                            float* final_obs) {
   if (KC == ENV_CLASS_PENDULUM) return env_step_pendulum(ev, i, t, action, final_obs);
   if (KC == ENV_CLASS_REACHER) return env_step_reacher(ev, i, t, action, a1, final_obs);
+  if (KC == ENV_CLASS_CARTPOLE) return env_step_cartpole(ev, i, t, action, final_obs);
   const sac_env_config& c = ev.cfg;
   const int O = c.obs_dim;
   const int step = ev.step[i] + 1;
@@ -356,12 +454,17 @@ __global__ void sac_envs_reset_kernel(sac_envs ev, uint64_t seed) {
       for (int k = 0; k < 4; ++k)
         if (4 * b + k < O) cur[4 * b + k] = env_uniform_obs(u[k]);
     }
-  } else if (c.kind != SAC_ENV_PENDULUM && c.kind != SAC_ENV_REACHER) {
+  } else if (c.kind != SAC_ENV_PENDULUM && c.kind != SAC_ENV_REACHER && c.kind != SAC_ENV_CARTPOLE) {
     cur[0] = c.kind == SAC_ENV_POINT_MASS ? (float)c.start_pos : 0.f;
   }
   ev.step[i] = 0;
   ev.ep_length[i] = 0;
-  if (c.kind == SAC_ENV_REACHER) {
+  if (c.kind == SAC_ENV_CARTPOLE) {
+    double s[4];
+    cartpole_reset_draw(seed, 0, (uint32_t)i, s);
+    cartpole_obs(s, cur);
+    cartpole_store(ev, i, s);
+  } else if (c.kind == SAC_ENV_REACHER) {
     double s[6];
     reacher_reset_draw(seed, 0, (uint32_t)i, s);
     reacher_obs(s, cur);
@@ -391,6 +494,8 @@ __global__ void sac_envs_step_kernel(sac_envs ev, const float* __restrict__ acti
   EnvOut o;
   if (ev.cfg.kind == SAC_ENV_REACHER)
     o = env_step<ENV_CLASS_REACHER>(ev, i, t, a, actions[(size_t)i * A + 1], fin);
+  else if (ev.cfg.kind == SAC_ENV_CARTPOLE)
+    o = env_step<ENV_CLASS_CARTPOLE>(ev, i, t, a, 0.f, fin);
   else if (ev.cfg.kind == SAC_ENV_PENDULUM)
     o = env_step<ENV_CLASS_PENDULUM>(ev, i, t, a, 0.f, fin);
   else

@@ -31,7 +31,7 @@
 // int32 [2][N] (step in episode, episode length), `dstate` float64 [2][N]
 // (position, episode return; the pendulum: [3][N], angle, episode return,
 // angular velocity; the reacher: [7][N], th1, th2, tx, ty, episode return, w1,
-// w2), `ring` float64 [S][N][2] (the sac_env_episode
+// w2; the cart-pole: [5][N], x, th, episode return, xdot, thdot), `ring` float64 [S][N][2] (the sac_env_episode
 // cells: return, then length and ended as two int32); `icfg` = [kind, num_envs,
 // obs_dim, max_steps], `params` = the 11 doubles of sac_env_config in order.
 // Engine state: `engine` is the sac_engine* handle (int64) from
@@ -349,7 +349,9 @@ sac_envs make_envs(const at::Tensor& obs, const at::Tensor& counters, const at::
   TORCH_CHECK(params.size() == 11, "params must hold the 11 doubles of sac_env_config");
   const int64_t N = icfg[1], O = icfg[2];
   const bool pendulum = icfg[0] == SAC_ENV_PENDULUM, reacher = icfg[0] == SAC_ENV_REACHER;
-  const int64_t pos_rows = reacher ? 4 : 1, vel_rows = reacher ? 2 : (pendulum ? 1 : 0);  // the kind's sac_envs.pos / .vel
+  const bool cartpole = icfg[0] == SAC_ENV_CARTPOLE;
+  // the kind's sac_envs.pos / .vel
+  const int64_t pos_rows = reacher ? 4 : (cartpole ? 2 : 1), vel_rows = reacher || cartpole ? 2 : (pendulum ? 1 : 0);
   TORCH_CHECK(N >= 1 && N <= INT32_MAX && O >= 1 && O <= INT32_MAX, "num_envs and obs_dim must be >= 1");
   check_f32(obs, "env obs");
   TORCH_CHECK(obs.dim() == 2 && obs.size(0) == N && obs.size(1) == O, "env obs must be [num_envs][obs_dim]");
@@ -359,7 +361,7 @@ sac_envs make_envs(const at::Tensor& obs, const at::Tensor& counters, const at::
   TORCH_CHECK(dstate.is_cuda() && dstate.scalar_type() == at::kDouble && dstate.is_contiguous() && dstate.dim() == 2 &&
                   dstate.size(0) == pos_rows + 1 + vel_rows && dstate.size(1) == N,
               "env dstate must be a contiguous float64 [2][num_envs] device tensor ([3][num_envs] for the pendulum, "
-              "[7][num_envs] for the reacher)");
+              "[7][num_envs] for the reacher, [5][num_envs] for the cart-pole)");
   TORCH_CHECK(counters.device() == obs.device() && dstate.device() == obs.device(), "env state on different devices");
   sac_envs ev{};
   ev.cfg.kind = static_cast<int32_t>(icfg[0]);

@@ -5,7 +5,7 @@ Modules (reference counterparts in parentheses):
     sac.models         QNetwork, PolicyNetwork, build_mlp   (sac/models.py)
     sac.replay_buffer  HBM struct-of-arrays ReplayBuffer    (sac/replay_buffer.py)
     sac.envs           probe environments                   (sac/envs.py)
-    sac.control_envs   the pendulum swing-up and the two-link reacher, control tasks (no counterpart)
+    sac.control_envs   the pendulum swing-up, the two-link reacher and the cart-pole, control tasks (no counterpart)
     sac.engine         host wrapper of libsac_engine.so (C ABI: include/sac_engine.h)
     sac.replicas       independent-seed replicas, one process per GPU
 """

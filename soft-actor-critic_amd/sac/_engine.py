@@ -78,7 +78,7 @@ class ReplayDesc(ctypes.Structure):
 
 # sac_env_kind (include/sac_engine.h) by the names sac/train_replicas.py uses
 ENV_KINDS = {"constant_reward": 0, "quadratic_action": 1, "random_obs_binary": 2, "point_mass": 3, "pendulum": 8,
-             "reacher": 16}
+             "reacher": 16, "cartpole": 32}
 # the double parameters of sac_env_config, in struct order
 ENV_PARAMS = ("reward", "target", "action_low", "action_high", "threshold", "start_pos", "goal_pos", "dt",
               "step_penalty", "goal_reward", "goal_tolerance")

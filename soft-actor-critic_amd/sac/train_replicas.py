@@ -17,12 +17,12 @@ aggregate as one JSON line.
         --env point_mass --num-envs 16 --env-steps 200000
 
 Without torchrun it runs one replica in-process.  ``--env`` names one of the
-probe envs of ``sac.envs``, ``pendulum`` or ``reacher`` (the control tasks of
+probe envs of ``sac.envs``, ``pendulum``, ``reacher`` or ``cartpole`` (the control tasks of
 ``sac.control_envs``) or, when gymnasium is importable, any registered
 gymnasium id (the reference's own envs).  The policy's output range is the
 config's ``policy_net.action_scale``, not the environment's: for ``pendulum``
 set it to 2.0 (its torque bound); at 1.0 the policy can use only half the
-torque.  ``reacher`` takes 1.0.
+torque.  ``reacher`` and ``cartpole`` take 1.0.
 
 ``--device-envs`` (the built-in envs only) keeps the environments on the device
 (``sac.device_envs.DeviceVectorEnv``) and trains through
@@ -59,6 +59,7 @@ PROBE_ENVS = {
     "random_obs_binary": ("envs", "RandomObsBinaryRewardEnv", {}),
     "pendulum": ("control_envs", "PendulumEnv", {}),
     "reacher": ("control_envs", "ReacherEnv", {}),
+    "cartpole": ("control_envs", "CartPoleEnv", {}),
 }
 
 

@@ -4,7 +4,7 @@ between two events, queued behind large device copies so that the host is ahead
 of the device and the interval is device time; median of `--repeats`, min .. max.
 Nets 2x[256,256] fp32, B = 256, buffer 1e6 rows.
 
-    python tools/rollout_launch_time.py [--envs point_mass,pendulum,reacher] [--num-envs 4096]
+    python tools/rollout_launch_time.py [--envs point_mass,pendulum,reacher,cartpole] [--num-envs 4096]
                                         [--package DIR] [--label this] [--out FILE]
 --package DIR imports the `sac` package (and the libraries beside it) from DIR
 instead of this tree's soft-actor-critic_amd: another build of the project, for
@@ -19,7 +19,7 @@ R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 # --env name -> (module of the sac package, host class, policy_net.action_scale)
 ENVS = {"point_mass": ("envs", "OneDPointMassReachEnv", 1.0), "pendulum": ("control_envs", "PendulumEnv", 2.0),
-        "reacher": ("control_envs", "ReacherEnv", 1.0)}
+        "reacher": ("control_envs", "ReacherEnv", 1.0), "cartpole": ("control_envs", "CartPoleEnv", 1.0)}
 
 
 def cfg(env):
@@ -39,7 +39,7 @@ def cfg(env):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--envs", default="point_mass,pendulum,reacher")
+    ap.add_argument("--envs", default="point_mass,pendulum,reacher,cartpole")
     ap.add_argument("--num-envs", default="4096")
     ap.add_argument("--launches", type=int, default=1000)
     ap.add_argument("--repeats", type=int, default=7)
