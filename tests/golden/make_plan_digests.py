@@ -20,7 +20,8 @@ The matrix (cases()):
     (test_plan_cpu._activation_cases) with ReLU and with ELU hidden layers;
   * the five shapes of test_shapes_past_the_lds_layout_take_the_stage_path;
   * edge shapes of the planner's own thresholds (EDGES below), the network
-    depths 1..5 and unequal depths of tests/_depth.py among them.
+    depths 1..5 and unequal depths of tests/_depth.py and the odd layer widths
+    of tests/_widths.py among them.
 """
 from __future__ import annotations
 
@@ -96,6 +97,25 @@ def _depth_edges():
 
 
 EDGES.update(_depth_edges())
+
+
+def _width_edges():
+    """Layer widths off the 8-column grid (tests/_widths.py): every case of the
+    GPU width matrix on its layout, each shape as the engine plans it by
+    default, and layout = pairs refused one past 256."""
+    import _widths
+
+    lay = {"layout": {"roles": 1, "rows": 2, "pairs": 3}}
+    out = {}
+    for case, (shape, over, _) in _widths.CASES.items():
+        out[f"width_{case}"] = (shape, {k: lay.get(k, {}).get(v, v) for k, v in (over or {}).items()}, NCU)
+    for name, shape in _widths.SHAPES.items():
+        out[f"width_{name}_default"] = (shape, {}, NCU)
+    out["width_w257_pairs_refused"] = (_widths.SHAPES["w257"], {"layout": 3}, NCU)
+    return out
+
+
+EDGES.update(_width_edges())
 
 
 def cases():

@@ -45,6 +45,7 @@ import pytest
 import torch
 
 import _depth
+import _widths
 
 pytestmark = pytest.mark.gpu
 
@@ -84,6 +85,11 @@ ENGINES = {
 DEPTH_ENGINES = ("h1_roles", "h1_rows", "h1_pairs", "h5_roles", "h5_pairs", "h5_stage", "q5_pi1_roles", "q5_pi1_rows",
                  "h1_256_roles")
 ENGINES.update({k: (dict(_depth.CASES[k][0], capacity=64),) + _depth.CASES[k][1:] for k in DEPTH_ENGINES})
+# layer widths off the 8-column grid (tests/_widths.py): [50, 33] on every family, a hidden layer of one unit, one
+# past 256 (a 17th column tile) and [299, 401] on the stage path: the forward epilogues' n < N at a ragged last tile
+# and the packed copies at odd K and N
+WIDTH_ENGINES = ("odd_roles", "odd_rows", "odd_pairs", "odd_stage", "tiny_roles", "w257_roles", "w401_stage")
+ENGINES.update({k: (dict(_widths.CASES[k][0], capacity=64),) + _widths.CASES[k][1:] for k in WIDTH_ENGINES})
 ACTS = {"relu": dict(),
         "tanh": dict(pi_act="tanh", pi_out_act="tanh", log_std_min=-0.5, log_std_max=0.5, action_scale=2.5)}
 CASES = [(name, "relu") for name in ENGINES] + [(name, "tanh") for name in ("roles_pad", "pairs_pad", "stage_pad")]

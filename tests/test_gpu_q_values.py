@@ -16,6 +16,7 @@ import pytest
 import torch
 
 import _depth
+import _widths
 
 pytestmark = pytest.mark.gpu
 
@@ -63,6 +64,10 @@ SHAPES = {
 DEPTH_SHAPES = ("h1_roles", "h1_rows", "h1_pairs", "h5_roles", "h5_rows", "h5_pairs", "h5_stage",
                 "q1_pi3_roles", "q1_pi3_rows", "q1_pi3_pairs", "q5_pi1_roles", "q5_pi1_rows", "q5_pi1_pairs")
 SHAPES.update({k: (dict(_depth.CASES[k][0], capacity=64),) + _depth.CASES[k][1:] for k in DEPTH_SHAPES})
+# critics at layer widths off the 8-column grid (tests/_widths.py): [33, 50] on every family, [7, 1] (a hidden layer
+# of one unit, a K = 1 output layer), [257, 31] and [401, 299] on the stage path
+WIDTH_SHAPES = ("odd_roles", "odd_rows", "odd_pairs", "odd_stage", "tiny_roles", "w257_roles", "w401_stage")
+SHAPES.update({k: (dict(_widths.CASES[k][0], capacity=64),) + _widths.CASES[k][1:] for k in WIDTH_SHAPES})
 ACTS = {"relu": dict(), "gelu_tanh": dict(q_act="gelu", q_out_act="tanh")}
 ROWS = (1, 16, 17, 33)  # one row, a full tile, a ragged tile, three tiles
 

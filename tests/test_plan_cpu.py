@@ -331,6 +331,44 @@ def test_depths_1_to_5_are_planned_on_the_expected_path(shape, kv, path, precisi
     assert _plan(_depth.SHAPES[shape], precision, **kv) == (0, path)
 
 
+# ---------------------------------------------------------------- layer widths off the 8-column grid (tests/_widths.py)
+def _width_paths():
+    """(id, shape name, overrides, the planner's path): every shape of the
+    width matrix as the engine plans it by default, and every case of the GPU
+    matrix on its override."""
+    import _widths
+
+    default = {"odd": "roles", "edge": "roles", "tiny": "roles", "h100": "roles", "w257": "roles", "odd3": "roles",
+               "odd_b1100": "pairs", "w401": "wide", "obs1": "roles", "obs31": "roles", "obs33": "roles"}
+    assert sorted(default) == sorted(_widths.SHAPES)
+    t = [(f"{s}/default", s, {}, p) for s, p in sorted(default.items())]
+    for case, (shape, lay, family) in sorted(_widths.CASES.items()):
+        kv = {k: E.LAYOUTS[v] if k == "layout" else int(v) for k, v in (lay or {}).items()}
+        t.append((f"case/{case}", _widths.SHAPE_OF[case], kv, PATH_OF[family]))
+    return t
+
+
+@pytest.mark.parametrize("precision", ["fp32", "bf16"])
+@pytest.mark.parametrize("shape,kv,path", [p[1:] for p in _width_paths()], ids=[p[0] for p in _width_paths()])
+def test_odd_widths_are_planned_on_the_expected_path(shape, kv, path, precision):
+    import _widths
+
+    assert _plan(_widths.SHAPES[shape], precision, **kv) == (0, path)
+    rc, msg = _create(_cfg_of(_widths.SHAPES[shape], precision), **kv)
+    assert rc == SAC_E_HIP and "internal" not in msg, (shape, kv, rc, msg)
+
+
+@pytest.mark.parametrize("precision", ["fp32", "bf16"])
+def test_pair_tiles_are_refused_one_past_256(precision):
+    """layout = pairs at [257, 31] | [31, 257]: 257 pads to 288 columns, and
+    the pair tiles' LDS layout does not fit; the override fails in the planner
+    and names the cause, it does not fall back."""
+    import _widths
+
+    rc, msg = _plan(_widths.SHAPES["w257"], precision, layout=3)
+    assert rc == SAC_E_INVALID and "pairs (the pair-tile LDS layout or record does not fit)" in msg, (rc, msg)
+
+
 @pytest.mark.parametrize("precision", ["fp32", "bf16"])
 def test_stage_path_override_is_ignored_at_one_hidden_layer(precision):
     """stage_path = 1 where a net has one hidden layer: the same plan as
