@@ -255,75 +255,73 @@ int sac_engine_clear_status(sac_engine *e, void *stream);
 /* Phase kernel names as they appear in rocprofv3 kernel traces. */
 const char *sac_phase_kernel_name(int32_t phase);
 
-/* ---- device-resident probe environments (sac/envs.py on the device) -------
- * N copies of one probe environment stepped in lockstep with SAME-STEP
- * autoreset, exactly as sac.vector_env.SyncVectorEnv drives the host classes:
- * an environment whose episode ended is reset inside the step, and the
- * transition of a step is (obs, action, reward, final_obs, terminated |
- * truncated).  Every probe takes ONE action component (act_dim = 1).  Values
- * sac/envs.py keeps as Python floats are doubles here, so the fp32-rounded
+/* ---- device-resident environments (sac/envs.py and sac/control_envs.py on the device)
+ * N copies of one environment stepped in lockstep with SAME-STEP autoreset,
+ * exactly as sac.vector_env.SyncVectorEnv drives the host classes: an
+ * environment whose episode ended is reset inside the step, and the transition
+ * of a step is (obs, action, reward, final_obs, terminated | truncated).  Values
+ * the host classes keep as Python floats are doubles here, so the fp32-rounded
  * observations and rewards are the host's.
+ *
+ * Per-kind widths (the macros below the enum; sac_envs.pos / .vel are
+ * component-major blocks [rows][num_envs] of doubles):
+ *                          SAC_ENV_ACT_DIM  SAC_ENV_OBS_DIM   SAC_ENV_POS_ROWS  SAC_ENV_VEL_ROWS
+ *   the probes (0..3)             1         1 (kind 2: any)          1          0 (vel may be NULL)
+ *   SAC_ENV_PENDULUM              1               3                  1                 1
+ *   SAC_ENV_REACHER               2              10                  4                 2
+ *   SAC_ENV_CARTPOLE              1               4                  2                 2
+ * Codes 4..7, 9..15 and 17..31 are not assigned.
  *
  * RNG (Philox4x32-10, key = seed, counter (t, env row, which << 16 | block)):
  * which = 2 the action noise of sac_rollout_step (key = the engine's seed,
  * block = action pair, Box-Muller as the training draws, which use 0 / 1);
  * which = 3 the observation a SAC_ENV_RANDOM_OBS environment steps to at t,
- * which = 4 its reset observation at t (key = the environment seed; four
- * draws per block, u = (word >> 8) * 2^-24, obs = 2u - 1).  The initial reset
- * is t = 0; the k-th step (k = 0, 1, ...) is t = k + 1.
+ * which = 4 a reset draw at t (key = the environment seed; four draws per
+ * block, u = (word >> 8) * 2^-24): the reset observation 2u - 1 of
+ * SAC_ENV_RANDOM_OBS, block by block, and the reset state of a control task,
+ * which is block 0's uniforms u0..u3 in double.  The initial reset is t = 0; the
+ * k-th step (k = 0, 1, ...) is t = k + 1.
  *
- * SAC_ENV_PENDULUM is the one kind that is a control task, not a probe: the
- * classic pendulum swing-up (sac/control_envs.py PendulumEnv; g = 10, m = l =
- * 1, speed limit 8).  State (th, thdot) in float64 (sac_envs.pos / .vel), one
- * torque component clipped to [action_low, action_high], observation
- * (cos th, sin th, thdot) in fp32 (obs_dim = 3).  With u the clipped action and
- * an = ((th + pi) mod 2 pi) - pi, a step gives reward -(an^2 + 0.1 thdot^2 +
- * 0.001 u^2) of the PRE-step state, thdot' = clip(thdot + (15 sin th + 3 u) dt,
- * -8, 8), th' = th + thdot' dt; never terminated, truncated at max_steps.
- * RNG: which = 4, block 0 at vector step t gives the reset state an episode
- * truncated at t restarts from (t = 0: the initial reset; key = the environment
- * seed): th = pi (2 u0 - 1), thdot = 2 u1 - 1 in double, u0 / u1 the block's
- * first two uniforms.  Codes 4..7 are not assigned.
+ * The probes (sac/envs.py; see the enum).  One action component, one
+ * observation (SAC_ENV_RANDOM_OBS: its obs_dim argument).
  *
- * SAC_ENV_REACHER is the one kind with TWO action components: a planar two-link
- * arm reaching for a target (sac/control_envs.py ReacherEnv; links L1 = L2 =
- * 0.1, GAIN = 10, DAMP = 2, CTRL_COST = 0.1, target half side 0.14).  The joints
- * are decoupled first-order rotors, all in float64: with u_j the j-th action
- * clipped to [action_low, action_high], dx = (L1 cos th1 + L2 cos(th1 + th2)) -
- * tx and dy the same with sin and ty, a step gives reward -sqrt(dx^2 + dy^2) -
- * 0.1 (u0^2 + u1^2) of the PRE-step state, w_j' = w_j + (10 u_j - 2 w_j) dt,
- * th_j' = th_j + w_j' dt; never terminated, truncated at max_steps.  The
- * observation is fp32 (cos th1, cos th2, sin th1, sin th2, tx, ty, w1, w2, dx,
- * dy) of the new state (obs_dim = 10).  State: sac_envs.pos is [4][num_envs]
- * doubles (th1, th2, tx, ty; row-major by component), sac_envs.vel is
- * [2][num_envs] doubles (w1, w2).  RNG: which = 4, block 0 at vector step t is
- * the reset draw, its four uniforms exactly one block: tx = 0.14 (2 u0 - 1), ty
- * = 0.14 (2 u1 - 1), th1 = pi (2 u2 - 1), th2 = pi (2 u3 - 1) in double, w = 0.
- * Codes 9..15 are not assigned.
+ * The control tasks (sac/control_envs.py).  Each keeps its state in float64,
+ * clips every action component to [action_low, action_high], observes the NEW
+ * state in fp32, is truncated at max_steps, and restarts an episode that ended
+ * at t from the reset draw of t.
  *
- * SAC_ENV_CARTPOLE is the one kind that ends by FAILURE: the classic balancing
- * cart-pole (sac/control_envs.py CartPoleEnv; G = 9.8, M_CART = 1, M_POLE = 0.1,
- * HALF_LEN = 0.5, FORCE_MAG = 10, X_LIMIT = 2.4, TH_LIMIT = 12 degrees, all
- * compile-time constants).  State (x, xdot, th, thdot) in float64, one force
- * component: with u the action clipped to [action_low, action_high], F = 10 u,
- * c = cos th, s = sin th, M = 1.1, temp = (F + 0.05 thdot^2 s) / M, thacc =
- * (G s - c temp) / (0.5 (4/3 - 0.1 c^2 / M)), xacc = temp - 0.05 thacc c / M, an
+ * SAC_ENV_PENDULUM: the classic pendulum swing-up (PendulumEnv; g = 10, m = l =
+ * 1, speed limit 8).  State (th, thdot): pos (th), vel (thdot).  With u the
+ * clipped torque and an = ((th + pi) mod 2 pi) - pi, a step gives reward -(an^2
+ * + 0.1 thdot^2 + 0.001 u^2) of the PRE-step state, thdot' = clip(thdot + (15
+ * sin th + 3 u) dt, -8, 8), th' = th + thdot' dt; never terminated.
+ * Observation (cos th, sin th, thdot).  Reset: th = pi (2 u0 - 1), thdot = 2 u1
+ * - 1.
+ *
+ * SAC_ENV_REACHER: a planar two-link arm reaching for a target (ReacherEnv;
+ * links L1 = L2 = 0.1, GAIN = 10, DAMP = 2, CTRL_COST = 0.1, target half side
+ * 0.14).  State (th1, th2, w1, w2, tx, ty): pos (th1, th2, tx, ty), vel (w1,
+ * w2).  The joints are decoupled first-order rotors: with u_j the j-th clipped
+ * torque, dx = (L1 cos th1 + L2 cos(th1 + th2)) - tx and dy the same with sin
+ * and ty, a step gives reward -sqrt(dx^2 + dy^2) - 0.1 (u0^2 + u1^2) of the
+ * PRE-step state, w_j' = w_j + (10 u_j - 2 w_j) dt, th_j' = th_j + w_j' dt;
+ * never terminated.  Observation (cos th1, cos th2, sin th1, sin th2, tx, ty,
+ * w1, w2, dx, dy).  Reset: tx = 0.14 (2 u0 - 1), ty = 0.14 (2 u1 - 1), th1 = pi
+ * (2 u2 - 1), th2 = pi (2 u3 - 1), w = 0.
+ *
+ * SAC_ENV_CARTPOLE: the classic balancing cart-pole (CartPoleEnv; G = 9.8,
+ * M_CART = 1, M_POLE = 0.1, HALF_LEN = 0.5, FORCE_MAG = 10, X_LIMIT = 2.4,
+ * TH_LIMIT = 12 degrees, all compile-time constants).  State (x, xdot, th,
+ * thdot): pos (x, th), vel (xdot, thdot).  With u the clipped action, F = 10 u,
+ * c = cos th, s = sin th, M = 1.1, temp = (F + 0.05 thdot^2 s) / M, thacc = (G s
+ * - c temp) / (0.5 (4/3 - 0.1 c^2 / M)), xacc = temp - 0.05 thacc c / M, an
  * explicit Euler step x' = x + dt xdot, xdot' = xdot + dt xacc, th' = th + dt
  * thdot, thdot' = thdot + dt thacc.  Reward 1.0 on every step; terminated when
- * |x'| > X_LIMIT or |th'| > TH_LIMIT, truncated at max_steps (independently:
- * both may be set).  The observation is fp32 (x, xdot, th, thdot) of the new
- * state (obs_dim = 4).  State: sac_envs.pos is [2][num_envs] doubles (x, th),
- * sac_envs.vel is [2][num_envs] doubles (xdot, thdot).  RNG: which = 4, block 0
- * at vector step t is the reset draw, its four uniforms exactly one block: x,
- * xdot, th, thdot = 0.05 (2 u_k - 1) in double, k = 0..3.  sin th and cos th
+ * |x'| > X_LIMIT or |th'| > TH_LIMIT, independently of truncation: both may be
+ * set, and rows end at different steps.  Observation (x, xdot, th, thdot).
+ * Reset: x, xdot, th, thdot = 0.05 (2 u_k - 1), k = 0..3.  sin th and cos th
  * feed back into the state, so the device's trajectory follows the host class's
- * to a few float64 ulps, not to the bit.  Codes 17..31 are not assigned.
- *
- * Per-kind widths          actions  obs_dim   pos doubles / env   vel doubles / env
- *   the probes (0..3)         1     1 (2: any)       1              - (may be NULL)
- *   SAC_ENV_PENDULUM          1        3             1                    1
- *   SAC_ENV_REACHER           2       10             4                    2
- *   SAC_ENV_CARTPOLE          1        4             2                    2         */
+ * to a few float64 ulps, not to the bit. */
 enum sac_env_kind {
   SAC_ENV_CONSTANT_REWARD = 0,  /* envs.py ConstantRewardEnv: r = reward, terminated at max_steps */
   SAC_ENV_QUADRATIC_ACTION = 1, /* QuadraticActionRewardEnv: r = -(clip(a) - target)^2 in fp32 */
@@ -334,28 +332,32 @@ enum sac_env_kind {
   SAC_ENV_CARTPOLE = 32         /* control_envs.py CartPoleEnv: balance, +1 per step, ends by failure, obs_dim 4 */
 };
 
-/* Action components an environment of `kind` takes: the act_dim its replay buffer and engine must have. */
+/* The width table above.  SAC_ENV_ACT_DIM: action components, the act_dim the replay buffer and the engine must
+ * have.  SAC_ENV_OBS_DIM: the obs_dim the kind fixes; 0 where it is the caller's (SAC_ENV_RANDOM_OBS).
+ * SAC_ENV_POS_ROWS / SAC_ENV_VEL_ROWS: rows of sac_envs.pos / .vel. */
 #define SAC_ENV_ACT_DIM(kind) ((kind) == SAC_ENV_REACHER ? 2 : 1)
+#define SAC_ENV_OBS_DIM(kind)                                                                         \
+  ((kind) == SAC_ENV_PENDULUM ? 3 : (kind) == SAC_ENV_REACHER ? 10 : (kind) == SAC_ENV_CARTPOLE ? 4 : \
+   (kind) == SAC_ENV_RANDOM_OBS ? 0 : 1)
+#define SAC_ENV_POS_ROWS(kind) ((kind) == SAC_ENV_REACHER ? 4 : (kind) == SAC_ENV_CARTPOLE ? 2 : 1)
+#define SAC_ENV_VEL_ROWS(kind) \
+  ((kind) == SAC_ENV_REACHER || (kind) == SAC_ENV_CARTPOLE ? 2 : (kind) == SAC_ENV_PENDULUM ? 1 : 0)
 
 /* The constructor arguments of the sac/envs.py class of `kind` (the others are
  * ignored); action bounds are rounded to fp32 as its Box stores them. */
 typedef struct sac_env_config {
   int32_t kind;                 /* enum sac_env_kind */
   int32_t num_envs;
-  int32_t obs_dim;              /* 1, except SAC_ENV_RANDOM_OBS (its obs_dim argument), SAC_ENV_PENDULUM (3),
-                                   SAC_ENV_REACHER (10) and SAC_ENV_CARTPOLE (4) */
+  int32_t obs_dim;              /* SAC_ENV_OBS_DIM(kind); SAC_ENV_RANDOM_OBS: its obs_dim argument */
   int32_t max_steps;
   double reward;                              /* SAC_ENV_CONSTANT_REWARD */
   double target;                              /* SAC_ENV_QUADRATIC_ACTION */
-  double action_low, action_high;             /* SAC_ENV_QUADRATIC_ACTION, SAC_ENV_POINT_MASS, SAC_ENV_PENDULUM and
-                                                 SAC_ENV_REACHER (-max_torque, max_torque; every component),
-                                                 SAC_ENV_CARTPOLE (-max_action, max_action) */
+  double action_low, action_high;             /* SAC_ENV_QUADRATIC_ACTION, SAC_ENV_POINT_MASS and the control
+                                                 tasks (the host class's bound, every component) */
   double threshold;                           /* SAC_ENV_RANDOM_OBS */
   double start_pos, goal_pos, dt, step_penalty, goal_reward, goal_tolerance;  /* SAC_ENV_POINT_MASS; dt also
-                                                                                 SAC_ENV_PENDULUM, SAC_ENV_REACHER,
-                                                                                 SAC_ENV_CARTPOLE */
-  uint64_t seed;                /* observation draws of SAC_ENV_RANDOM_OBS, reset draws of SAC_ENV_PENDULUM,
-                                   SAC_ENV_REACHER and SAC_ENV_CARTPOLE */
+                                                                                 the control tasks */
+  uint64_t seed;                /* observation draws of SAC_ENV_RANDOM_OBS, reset draws of the control tasks */
 } sac_env_config;
 
 /* One cell of the episode record: written by every environment on every step. */
@@ -371,21 +373,19 @@ typedef struct sac_envs {
   float *obs;                   /* [num_envs][obs_dim] current observations */
   int32_t *step;                /* [num_envs] step in the episode (envs.py current_step) */
   int32_t *ep_length;           /* [num_envs] length of the running episode */
-  double *pos;                  /* [num_envs] SAC_ENV_POINT_MASS position; SAC_ENV_PENDULUM angle th;
-                                   SAC_ENV_REACHER [4][num_envs]: th1, th2, tx, ty; SAC_ENV_CARTPOLE
-                                   [2][num_envs]: x, th */
+  double *pos;                  /* [SAC_ENV_POS_ROWS(kind)][num_envs]: SAC_ENV_POINT_MASS position; a control
+                                   task's pos components, in the order of its section above */
   double *ep_return;            /* [num_envs] return of the running episode */
   sac_env_episode *episodes;    /* [ring_steps][num_envs] dense ring indexed by t % ring_steps and env row;
                                    NULL: no record (sac_envs_step only) */
   int64_t ring_steps;
-  double *vel;                  /* [num_envs] SAC_ENV_PENDULUM angular velocity thdot; SAC_ENV_REACHER
-                                   [2][num_envs]: w1, w2; SAC_ENV_CARTPOLE [2][num_envs]: xdot, thdot; may be NULL
-                                   for the probes */
+  double *vel;                  /* [SAC_ENV_VEL_ROWS(kind)][num_envs]: a control task's vel components; may be
+                                   NULL for the probes */
 } sac_envs;
 
 /* Reset every environment: step and episode counters to 0, the initial
- * observation (draws of SAC_ENV_RANDOM_OBS, SAC_ENV_PENDULUM, SAC_ENV_REACHER and
- * SAC_ENV_CARTPOLE: which = 4, t = 0, key `seed`).
+ * observation (draws of SAC_ENV_RANDOM_OBS and the control tasks: which = 4, t = 0,
+ * key `seed`).
  * Replaces: SyncVectorEnv.reset (sac/vector_env.py:39-46). */
 int sac_envs_reset(const sac_envs *envs, uint64_t seed, void *stream);
 

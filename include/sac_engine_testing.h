@@ -67,7 +67,7 @@ int sac_debug_rollout_eps_device(uint64_t seed, uint64_t t, int32_t n, int32_t a
  * output word k % 4: u = (word >> 8) * 2^-24, obs = 2u - 1 in [-1, 1). */
 int sac_debug_env_obs_host(uint64_t seed, uint64_t t, int32_t which, int32_t n, int32_t obs_dim, float *out);
 /* One step of SAC_ENV_PENDULUM on the host: the inline dynamics the device
- * kernels call (csrc/sac_envs.h pendulum_dynamics), compiled for the host, so
+ * kernels call (csrc/sac_envs.h EnvTask<ENV_CLASS_PENDULUM>::dynamics), compiled for the host, so
  * sin / cos are the host libm's.  cfg supplies action_low, action_high, dt and
  * max_steps (kind must be SAC_ENV_PENDULUM); state = (th, thdot) is advanced in
  * place; `step` is the step in the episode before this one.  Outputs: the
@@ -81,7 +81,7 @@ int sac_debug_env_step_host(const sac_env_config *cfg, double state[2], int32_t 
  * two uniforms of sac_debug_env_obs_host's which = 4 block 0. */
 int sac_debug_env_reset_host(uint64_t seed, uint64_t t, int32_t row, double state_out[2]);
 /* One step of SAC_ENV_REACHER on the host: the inline dynamics the device
- * kernels call (csrc/sac_envs.h reacher_dynamics), compiled for the host, so
+ * kernels call (csrc/sac_envs.h EnvTask<ENV_CLASS_REACHER>::dynamics), compiled for the host, so
  * sin / cos / sqrt are the host libm's.  cfg supplies action_low, action_high,
  * dt and max_steps (kind must be SAC_ENV_REACHER); state = (th1, th2, w1, w2,
  * tx, ty), the order of ReacherEnv.state, is advanced in place; `step` is the
@@ -97,7 +97,7 @@ int sac_debug_reacher_step_host(const sac_env_config *cfg, double state[6], int3
  * (tx, ty) = 0.14 (2 u - 1) of its first and second. */
 int sac_debug_reacher_reset_host(uint64_t seed, uint64_t t, int32_t row, double state_out[6]);
 /* One step of SAC_ENV_CARTPOLE on the host: the inline dynamics the device
- * kernels call (csrc/sac_envs.h cartpole_dynamics), compiled for the host, so
+ * kernels call (csrc/sac_envs.h EnvTask<ENV_CLASS_CARTPOLE>::dynamics), compiled for the host, so
  * sin / cos are the host libm's.  cfg supplies action_low, action_high, dt and
  * max_steps (kind must be SAC_ENV_CARTPOLE); state = (x, xdot, th, thdot), the
  * order of CartPoleEnv.state, is advanced in place; `step` is the step in the

@@ -321,20 +321,14 @@ static int validate(const sac_engine_config* c) {
   return SAC_OK;
 }
 
-// The rollout kernels' instantiation for a kind class (sac_envs.h EnvClass)
+// The rollout kernels' instantiation for the class of a kind (sac_envs.h with_env_class)
 template <typename T>
-static auto rollout_kernel(int kc) {
-  return kc == ENV_CLASS_CARTPOLE   ? sac_rollout_step_kernel<T, ENV_CLASS_CARTPOLE>
-         : kc == ENV_CLASS_REACHER  ? sac_rollout_step_kernel<T, ENV_CLASS_REACHER>
-         : kc == ENV_CLASS_PENDULUM ? sac_rollout_step_kernel<T, ENV_CLASS_PENDULUM>
-                                    : sac_rollout_step_kernel<T, ENV_CLASS_PROBES>;
+static auto rollout_kernel(int kind) {
+  return with_env_class(kind, [](auto kc) { return sac_rollout_step_kernel<T, decltype(kc)::value>; });
 }
 template <typename T>
-static auto rollout_dev_kernel(int kc) {
-  return kc == ENV_CLASS_CARTPOLE   ? sac_rollout_step_dev_kernel<T, ENV_CLASS_CARTPOLE>
-         : kc == ENV_CLASS_REACHER  ? sac_rollout_step_dev_kernel<T, ENV_CLASS_REACHER>
-         : kc == ENV_CLASS_PENDULUM ? sac_rollout_step_dev_kernel<T, ENV_CLASS_PENDULUM>
-                                    : sac_rollout_step_dev_kernel<T, ENV_CLASS_PROBES>;
+static auto rollout_dev_kernel(int kind) {
+  return with_env_class(kind, [](auto kc) { return sac_rollout_step_dev_kernel<T, decltype(kc)::value>; });
 }
 
 template <typename T>
@@ -346,9 +340,9 @@ static void set_lds_attrs(size_t bytes) {
   (void)hipFuncSetAttribute((const void*)sac_actor<T, false>, hipFuncAttributeMaxDynamicSharedMemorySize, b);
   (void)hipFuncSetAttribute((const void*)sac_actor<T, true>, hipFuncAttributeMaxDynamicSharedMemorySize, b);
   (void)hipFuncSetAttribute((const void*)sac_policy_act_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, b);
-  for (int kc = ENV_CLASS_PROBES; kc <= ENV_CLASS_CARTPOLE; ++kc) {
-    (void)hipFuncSetAttribute((const void*)rollout_kernel<T>(kc), hipFuncAttributeMaxDynamicSharedMemorySize, b);
-    (void)hipFuncSetAttribute((const void*)rollout_dev_kernel<T>(kc), hipFuncAttributeMaxDynamicSharedMemorySize, b);
+  for (int kind : ENV_CLASS_KINDS) {
+    (void)hipFuncSetAttribute((const void*)rollout_kernel<T>(kind), hipFuncAttributeMaxDynamicSharedMemorySize, b);
+    (void)hipFuncSetAttribute((const void*)rollout_dev_kernel<T>(kind), hipFuncAttributeMaxDynamicSharedMemorySize, b);
   }
   (void)hipFuncSetAttribute((const void*)sac_q_values_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, b);
   (void)hipFuncSetAttribute((const void*)sac_target_critic_split<T>, hipFuncAttributeMaxDynamicSharedMemorySize, b);
@@ -514,22 +508,22 @@ static int check_replay(sac_engine* e, const sac_replay* rb) {
 static int check_envs(const sac_envs* ev, bool need_ring) {
   if (!ev) return fail(SAC_E_INVALID, "null environments");
   const sac_env_config& c = ev->cfg;
-  const bool pendulum = c.kind == SAC_ENV_PENDULUM, reacher = c.kind == SAC_ENV_REACHER;
-  const bool cartpole = c.kind == SAC_ENV_CARTPOLE;
-  if ((c.kind < SAC_ENV_CONSTANT_REWARD || c.kind > SAC_ENV_POINT_MASS) && !pendulum && !reacher && !cartpole)
+  // a control task's enumerator (sac_envs.h EnvTask), NULL for the probes and for an unknown kind
+  const char* task = with_env_class(c.kind, [](auto kc) -> const char* {
+    if constexpr (decltype(kc)::value != ENV_CLASS_PROBES) return EnvTask<decltype(kc)::value>::NAME;
+    return nullptr;
+  });
+  if ((c.kind < SAC_ENV_CONSTANT_REWARD || c.kind > SAC_ENV_POINT_MASS) && !task)
     return fail(SAC_E_INVALID, "unknown environment kind " + std::to_string(c.kind));
   if (c.num_envs < 1) return fail(SAC_E_INVALID, "num_envs >= 1");
   if (c.max_steps < 1) return fail(SAC_E_INVALID, "max_steps >= 1");
-  if (pendulum && c.obs_dim != SAC_PENDULUM_OBS_DIM)
-    return fail(SAC_E_INVALID, "obs_dim must be 3 for SAC_ENV_PENDULUM");
-  if (reacher && c.obs_dim != SAC_REACHER_OBS_DIM)
-    return fail(SAC_E_INVALID, "obs_dim must be 10 for SAC_ENV_REACHER");
-  if (cartpole && c.obs_dim != SAC_CARTPOLE_OBS_DIM)
-    return fail(SAC_E_INVALID, "obs_dim must be 4 for SAC_ENV_CARTPOLE");
-  if (!pendulum && !reacher && !cartpole && (c.kind == SAC_ENV_RANDOM_OBS ? (c.obs_dim < 1 || c.obs_dim > 4 * 65536) : c.obs_dim != 1))
+  const int obs_dim = SAC_ENV_OBS_DIM(c.kind);  // 0: the caller's
+  if (task && c.obs_dim != obs_dim)
+    return fail(SAC_E_INVALID, "obs_dim must be " + std::to_string(obs_dim) + " for " + task);
+  if (!task && (obs_dim ? c.obs_dim != obs_dim : (c.obs_dim < 1 || c.obs_dim > 4 * 65536)))
     return fail(SAC_E_INVALID, "obs_dim must be 1 (SAC_ENV_RANDOM_OBS: 1..262144)");
   if (!ev->obs || !ev->step || !ev->ep_length || !ev->pos || !ev->ep_return ||
-      ((pendulum || reacher || cartpole) && !ev->vel))
+      (SAC_ENV_VEL_ROWS(c.kind) && !ev->vel))
     return fail(SAC_E_INVALID, "null environment state");
   if (need_ring ? (!ev->episodes || ev->ring_steps < 1) : (ev->episodes && ev->ring_steps < 1))
     return fail(SAC_E_INVALID, "episode ring needs episodes != NULL and ring_steps >= 1");
@@ -563,6 +557,29 @@ static int check_plan(const sac_engine* e) {
                           ", built " + std::to_string(e->hostB.size()) + " / " + std::to_string(e->hostD.size());
     return fail(SAC_E_INVALID, m);
   }
+  return SAC_OK;
+}
+
+// What the control tasks' sac_debug_*_step_host / *_reset_host exports share, behind each one's own null
+// checks; `terminated` may be NULL
+template <int KC>
+static int task_step_host(const std::string& who, const sac_env_config* cfg, double* state, int32_t step,
+                          const float* action, float* obs_out, double* reward, int32_t* terminated,
+                          int32_t* truncated) {
+  using Task = EnvTask<KC>;
+  if (cfg->kind != Task::KIND) return fail(SAC_E_INVALID, who + ": kind must be " + Task::NAME);
+  if (cfg->max_steps < 1 || step < 0) return fail(SAC_E_INVALID, who + ": max_steps >= 1 and step >= 0");
+  EnvOut o;
+  Task::dynamics(state, action, *cfg, obs_out, o);
+  *reward = o.reward;
+  if (terminated) *terminated = o.terminated ? 1 : 0;
+  *truncated = step + 1 >= cfg->max_steps ? 1 : 0;
+  return SAC_OK;
+}
+template <int KC>
+static int task_reset_host(uint64_t seed, uint64_t t, int32_t row, double* state_out) {
+  if (!state_out || row < 0) return fail(SAC_E_INVALID, "need row >= 0 and state_out != NULL");
+  EnvTask<KC>::reset_draw(seed, t, (uint32_t)row, state_out);
   return SAC_OK;
 }
 
@@ -942,8 +959,8 @@ int sac_rollout_step(sac_engine* e, const sac_envs* envs, const sac_replay* rb, 
   const int64_t new_pos = (pos_host + n) % cap;
   const int blocks = (int)((n + SAC_ROWS - 1) / SAC_ROWS);
   hipStream_t s = (hipStream_t)stream;
-  const int kc = env_class(envs->cfg.kind);
-  auto kernel = e->cfg.precision == SAC_PREC_BF16 ? rollout_kernel<bf16>(kc) : rollout_kernel<float>(kc);
+  const int kind = envs->cfg.kind;
+  auto kernel = e->cfg.precision == SAC_PREC_BF16 ? rollout_kernel<bf16>(kind) : rollout_kernel<float>(kind);
   kernel<<<blocks, SAC_THREADS, e->lds_bytes, s>>>(e->d, *envs, *rb, pos_host, new_size, new_pos, t, deterministic ? 1 : 0,
                                                    store ? 1 : 0);
   HIPCHK(hipGetLastError());
@@ -956,8 +973,8 @@ static int launch_rollout_dev(sac_engine* e, const sac_envs* envs, const sac_rep
   const int blocks = (envs->cfg.num_envs + SAC_ROWS - 1) / SAC_ROWS;
   const int64_t* cur = cursor + 4 * parity;
   int64_t* nxt = cursor + 4 * (parity ^ 1);
-  const int kc = env_class(envs->cfg.kind);
-  auto kernel = e->cfg.precision == SAC_PREC_BF16 ? rollout_dev_kernel<bf16>(kc) : rollout_dev_kernel<float>(kc);
+  const int kind = envs->cfg.kind;
+  auto kernel = e->cfg.precision == SAC_PREC_BF16 ? rollout_dev_kernel<bf16>(kind) : rollout_dev_kernel<float>(kind);
   kernel<<<blocks, SAC_THREADS, e->lds_bytes, s>>>(e->d, *envs, *rb, cur, nxt, deterministic, store);
   HIPCHK(hipGetLastError());
   return SAC_OK;
@@ -1090,52 +1107,36 @@ int sac_debug_env_step_host(const sac_env_config* cfg, double state[2], int32_t 
                             double* reward, int32_t* truncated) {
   if (!cfg || !state || !obs_out || !reward || !truncated)
     return fail(SAC_E_INVALID, "need cfg, state, obs_out, reward and truncated != NULL");
-  if (cfg->kind != SAC_ENV_PENDULUM) return fail(SAC_E_INVALID, "env_step_host: kind must be SAC_ENV_PENDULUM");
-  if (cfg->max_steps < 1 || step < 0) return fail(SAC_E_INVALID, "env_step_host: max_steps >= 1 and step >= 0");
-  *reward = pendulum_dynamics(state[0], state[1], action, cfg->action_low, cfg->action_high, cfg->dt, obs_out);
-  *truncated = step + 1 >= cfg->max_steps ? 1 : 0;
-  return SAC_OK;
+  return task_step_host<ENV_CLASS_PENDULUM>("env_step_host", cfg, state, step, &action, obs_out, reward, nullptr,
+                                            truncated);
 }
 
 int sac_debug_env_reset_host(uint64_t seed, uint64_t t, int32_t row, double state_out[2]) {
-  if (!state_out || row < 0) return fail(SAC_E_INVALID, "need row >= 0 and state_out != NULL");
-  pendulum_reset_draw(seed, t, (uint32_t)row, state_out[0], state_out[1]);
-  return SAC_OK;
+  return task_reset_host<ENV_CLASS_PENDULUM>(seed, t, row, state_out);
 }
 
 int sac_debug_reacher_step_host(const sac_env_config* cfg, double state[6], int32_t step, const float action[2],
                                 float obs_out[10], double* reward, int32_t* truncated) {
   if (!cfg || !state || !action || !obs_out || !reward || !truncated)
     return fail(SAC_E_INVALID, "need cfg, state, action, obs_out, reward and truncated != NULL");
-  if (cfg->kind != SAC_ENV_REACHER) return fail(SAC_E_INVALID, "reacher_step_host: kind must be SAC_ENV_REACHER");
-  if (cfg->max_steps < 1 || step < 0) return fail(SAC_E_INVALID, "reacher_step_host: max_steps >= 1 and step >= 0");
-  *reward = reacher_dynamics(state, action[0], action[1], cfg->action_low, cfg->action_high, cfg->dt, obs_out);
-  *truncated = step + 1 >= cfg->max_steps ? 1 : 0;
-  return SAC_OK;
+  return task_step_host<ENV_CLASS_REACHER>("reacher_step_host", cfg, state, step, action, obs_out, reward, nullptr,
+                                           truncated);
 }
 
 int sac_debug_reacher_reset_host(uint64_t seed, uint64_t t, int32_t row, double state_out[6]) {
-  if (!state_out || row < 0) return fail(SAC_E_INVALID, "need row >= 0 and state_out != NULL");
-  reacher_reset_draw(seed, t, (uint32_t)row, state_out);
-  return SAC_OK;
+  return task_reset_host<ENV_CLASS_REACHER>(seed, t, row, state_out);
 }
 
 int sac_debug_cartpole_step_host(const sac_env_config* cfg, double state[4], int32_t step, const float action[1],
                                  float obs_out[4], double* reward, int32_t* terminated, int32_t* truncated) {
   if (!cfg || !state || !action || !obs_out || !reward || !terminated || !truncated)
     return fail(SAC_E_INVALID, "need cfg, state, action, obs_out, reward, terminated and truncated != NULL");
-  if (cfg->kind != SAC_ENV_CARTPOLE) return fail(SAC_E_INVALID, "cartpole_step_host: kind must be SAC_ENV_CARTPOLE");
-  if (cfg->max_steps < 1 || step < 0) return fail(SAC_E_INVALID, "cartpole_step_host: max_steps >= 1 and step >= 0");
-  *terminated = cartpole_dynamics(state, action[0], cfg->action_low, cfg->action_high, cfg->dt, obs_out) ? 1 : 0;
-  *reward = 1.0;
-  *truncated = step + 1 >= cfg->max_steps ? 1 : 0;
-  return SAC_OK;
+  return task_step_host<ENV_CLASS_CARTPOLE>("cartpole_step_host", cfg, state, step, action, obs_out, reward,
+                                            terminated, truncated);
 }
 
 int sac_debug_cartpole_reset_host(uint64_t seed, uint64_t t, int32_t row, double state_out[4]) {
-  if (!state_out || row < 0) return fail(SAC_E_INVALID, "need row >= 0 and state_out != NULL");
-  cartpole_reset_draw(seed, t, (uint32_t)row, state_out);
-  return SAC_OK;
+  return task_reset_host<ENV_CLASS_CARTPOLE>(seed, t, row, state_out);
 }
 
 int sac_replay_push(const sac_replay* rb, const float* rows, int64_t n, int64_t size_host, int64_t pos_host,

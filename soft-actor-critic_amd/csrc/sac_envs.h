@@ -1,22 +1,30 @@
-// sac_envs.h — the probe environments of sac/envs.py and the Pendulum swing-up
-// two-link reacher and balancing cart-pole of sac/control_envs.py on the
-// device, and the fused rollout step (act -> step -> store in one launch).
+// sac_envs.h — the environments of sac/envs.py (the probes) and sac/control_envs.py
+// (the control tasks) on the device, and the fused rollout step (act -> step ->
+// store in one launch).
 //
-//   * pendulum_dynamics: one step of the swing-up in float64, host-callable;
-//   * reacher_dynamics: one step of the reacher (two action components), likewise;
-//   * cartpole_dynamics: one step of the cart-pole (the kind that terminates by failure), likewise;
-//   * env_step: ONE statement of the environments' dynamics, with the semantics
+//   class (EnvClass)       kinds                    described by
+//   ENV_CLASS_PROBES       SAC_ENV_* 0..3           the switch in env_step (one class on purpose)
+//   ENV_CLASS_PENDULUM     SAC_ENV_PENDULUM         EnvTask<ENV_CLASS_PENDULUM>
+//   ENV_CLASS_REACHER      SAC_ENV_REACHER          EnvTask<ENV_CLASS_REACHER>
+//   ENV_CLASS_CARTPOLE     SAC_ENV_CARTPOLE         EnvTask<ENV_CLASS_CARTPOLE>
+//
+//   * EnvTask<KC>: everything the kernels know about one control task: its widths,
+//     where each float64 state component lives, its observation, dynamics and
+//     reset draw (host-callable: the C ABI exports the same inline code);
+//   * task_load / task_store / env_step_task / task_reset: the code every task
+//     shares, written once over an EnvTask;
+//   * env_step<KC>: ONE statement of the environments' dynamics, with the semantics
 //     sac.vector_env.SyncVectorEnv gives the host classes (same-step autoreset;
 //     the transition is (obs, action, reward, final_obs, terminated | truncated)).
-//     Whatever sac/envs.py keeps as a Python float is a double here, so the
+//     Whatever the host classes keep as a Python float is a double here, so the
 //     fp32-rounded observations and rewards are the host's bit for bit;
+//   * with_env_class: the one map from a kind to its class;
 //   * sac_envs_step_kernel: N environments stepped with the caller's actions;
 //   * sac_rollout_step_kernel<T, KC>: sibling of sac_policy_act_kernel<T>
 //     (same workgroup shape, LDS layout and mlp_forward call); the thread that
 //     owns environment row i samples its action, steps the environment and
-//     writes the transition into the replay ring.  Compiled once per kind class
-//     KC (the probes, the pendulum, the reacher, the cart-pole); the host picks by the
-//     environments' kind;
+//     writes the transition into the replay ring.  Compiled once per class KC, so
+//     that no class carries another's code; the host picks by the environments' kind;
 //   * sac_rollout_step_dev_kernel<T, KC>: the same body with (size, pos,
 //     t) read from a two-slot cursor in device memory, so whole loop iterations
 //     replay from one hipGraph (sac_engine_loop_graph).
@@ -26,20 +34,14 @@
 // every episode-ring cell by its own row: no atomics, no hand-offs, nothing
 // depends on the order workgroups run in.
 #pragma once
+#include <type_traits>
+
 #include "../../include/sac_engine.h"
 #include "sac_phases.h"
 
-// Action components an environment of `kind` takes: 1 (envs.py: every probe's action_space has shape
-// (1,), and so has the pendulum's) except the reacher's 2.
+// Action components an environment of `kind` takes
 __host__ __device__ inline int env_act_dim(int kind) { return SAC_ENV_ACT_DIM(kind); }
-// The rollout kernels are compiled once per kind class, so no class holds another's code.
 enum EnvClass { ENV_CLASS_PROBES = 0, ENV_CLASS_PENDULUM = 1, ENV_CLASS_REACHER = 2, ENV_CLASS_CARTPOLE = 3 };
-inline int env_class(int kind) {
-  return kind == SAC_ENV_PENDULUM   ? ENV_CLASS_PENDULUM
-         : kind == SAC_ENV_REACHER  ? ENV_CLASS_REACHER
-         : kind == SAC_ENV_CARTPOLE ? ENV_CLASS_CARTPOLE
-                                    : ENV_CLASS_PROBES;
-}
 // Philox `which` values of the rollout (0 / 1 are the training draws)
 #define ENV_WHICH_NOISE 2u  // action noise of a rollout step, key = engine seed
 #define ENV_WHICH_STEP 3u   // observation an environment steps to at t, key = env seed
@@ -61,306 +63,279 @@ __host__ __device__ inline float env_uniform_obs(float u) { return 2.0f * u - 1.
 // np.clip on float32: min(max(x, lo), hi) with NaN passed through
 __host__ __device__ inline float clip_f32(float x, float lo, float hi) { return x < lo ? lo : (x > hi ? hi : x); }
 
-// ---- Pendulum swing-up (sac/control_envs.py PendulumEnv) --------------------
-// State (th, thdot) in float64; g = 10, m = l = 1, so 3 g / (2 l) = 15 and
-// 3 / (m l^2) = 3 exactly.  Every operation below is the host class's, in its
-// order (the library is built with -ffp-contract=off: no fused multiply-adds).
-#define SAC_PENDULUM_OBS_DIM 3
-#define SAC_PENDULUM_MAX_SPEED 8.0
-#define SAC_PI 3.141592653589793
-
-// Python's ((th + pi) % (2 pi)) - pi: the angle in [-pi, pi)
-__host__ __device__ inline double pendulum_angle(double th) {
-  double an = fmod(th + SAC_PI, 2.0 * SAC_PI);
-  if (an < 0.0) an += 2.0 * SAC_PI;
-  return an - SAC_PI;
-}
-
-// The observation of a state, in fp32
-__host__ __device__ inline void pendulum_obs(double th, double thdot, float obs[SAC_PENDULUM_OBS_DIM]) {
-  obs[0] = (float)cos(th);
-  obs[1] = (float)sin(th);
-  obs[2] = (float)thdot;
-}
-
-// One step from (th, thdot) with action a: the reward of the PRE-step state,
-// the new state in place and its observation (cos th', sin th', thdot') in fp32.
-__host__ __device__ inline double pendulum_dynamics(double& th, double& thdot, float a, double action_low,
-                                                    double action_high, double dt, float obs[SAC_PENDULUM_OBS_DIM]) {
-  const double u = (double)clip_f32(a, (float)action_low, (float)action_high);
-  const double an = pendulum_angle(th);
-  const double reward = -(an * an + 0.1 * thdot * thdot + 0.001 * u * u);
-  double v = thdot + (15.0 * sin(th) + 3.0 * u) * dt;
-  v = v < -SAC_PENDULUM_MAX_SPEED ? -SAC_PENDULUM_MAX_SPEED : (v > SAC_PENDULUM_MAX_SPEED ? SAC_PENDULUM_MAX_SPEED : v);
-  th = th + v * dt;
-  thdot = v;
-  pendulum_obs(th, thdot, obs);
-  return reward;
-}
-
-// The reset draw of env row `row` at vector step t: th ~ U[-pi, pi), thdot ~
-// U[-1, 1) from the first two uniforms of the row's ENV_WHICH_RESET block 0.
-__host__ __device__ inline void pendulum_reset_draw(uint64_t seed, uint64_t t, uint32_t row, double& th,
-                                                    double& thdot) {
-  float u[4];
-  philox_uniform4(seed, t, row, ENV_WHICH_RESET, 0, u);
-  th = SAC_PI * (2.0 * (double)u[0] - 1.0);
-  thdot = 2.0 * (double)u[1] - 1.0;
-}
-
-// ---- Two-link reacher (sac/control_envs.py ReacherEnv) ----------------------
-// State s = (th1, th2, w1, w2, tx, ty) in float64, the order of ReacherEnv.state.
-// Sine and cosine enter the reward and the observation only, never the state:
-// the state trajectory is the host's bit for bit whatever library they come from.
-#define SAC_REACHER_OBS_DIM 10
-#define SAC_REACHER_L1 0.1
-#define SAC_REACHER_L2 0.1
-#define SAC_REACHER_GAIN 10.0
-#define SAC_REACHER_DAMP 2.0
-#define SAC_REACHER_CTRL_COST 0.1
-#define SAC_REACHER_TARGET_HALF_SIDE 0.14
-
-// Fingertip minus target
-__host__ __device__ inline void reacher_tip(const double s[6], double& dx, double& dy) {
-  dx = (SAC_REACHER_L1 * cos(s[0]) + SAC_REACHER_L2 * cos(s[0] + s[1])) - s[4];
-  dy = (SAC_REACHER_L1 * sin(s[0]) + SAC_REACHER_L2 * sin(s[0] + s[1])) - s[5];
-}
-
-// The observation of a state, in fp32
-__host__ __device__ inline void reacher_obs(const double s[6], float obs[SAC_REACHER_OBS_DIM]) {
-  double dx, dy;
-  reacher_tip(s, dx, dy);
-  obs[0] = (float)cos(s[0]);
-  obs[1] = (float)cos(s[1]);
-  obs[2] = (float)sin(s[0]);
-  obs[3] = (float)sin(s[1]);
-  obs[4] = (float)s[4];
-  obs[5] = (float)s[5];
-  obs[6] = (float)s[2];
-  obs[7] = (float)s[3];
-  obs[8] = (float)dx;
-  obs[9] = (float)dy;
-}
-
-// One step from s with actions (a0, a1): the reward of the PRE-step state, the
-// new state in place and its observation in fp32.
-__host__ __device__ inline double reacher_dynamics(double s[6], float a0, float a1, double action_low,
-                                                   double action_high, double dt, float obs[SAC_REACHER_OBS_DIM]) {
-  const double u0 = (double)clip_f32(a0, (float)action_low, (float)action_high);
-  const double u1 = (double)clip_f32(a1, (float)action_low, (float)action_high);
-  double dx, dy;
-  reacher_tip(s, dx, dy);
-  const double reward = -sqrt(dx * dx + dy * dy) - SAC_REACHER_CTRL_COST * (u0 * u0 + u1 * u1);
-  s[2] = s[2] + (SAC_REACHER_GAIN * u0 - SAC_REACHER_DAMP * s[2]) * dt;
-  s[3] = s[3] + (SAC_REACHER_GAIN * u1 - SAC_REACHER_DAMP * s[3]) * dt;
-  s[0] = s[0] + s[2] * dt;
-  s[1] = s[1] + s[3] * dt;
-  reacher_obs(s, obs);
-  return reward;
-}
-
-// The reset draw of env row `row` at vector step t: the four uniforms of the
-// row's ENV_WHICH_RESET block 0 give the target in the square of half side 0.14
-// and both angles in [-pi, pi); the arm starts at rest.
-__host__ __device__ inline void reacher_reset_draw(uint64_t seed, uint64_t t, uint32_t row, double s[6]) {
-  float u[4];
-  philox_uniform4(seed, t, row, ENV_WHICH_RESET, 0, u);
-  s[4] = SAC_REACHER_TARGET_HALF_SIDE * (2.0 * (double)u[0] - 1.0);
-  s[5] = SAC_REACHER_TARGET_HALF_SIDE * (2.0 * (double)u[1] - 1.0);
-  s[0] = SAC_PI * (2.0 * (double)u[2] - 1.0);
-  s[1] = SAC_PI * (2.0 * (double)u[3] - 1.0);
-  s[2] = 0.0;
-  s[3] = 0.0;
-}
-
-// Row i's state in the component-major blocks ev.pos [4][N] (th1, th2, tx, ty) and ev.vel [2][N] (w1, w2)
-__device__ __forceinline__ void reacher_load(const sac_envs& ev, int i, double s[6]) {
-  const size_t n = (size_t)ev.cfg.num_envs;
-  s[0] = ev.pos[i];
-  s[1] = ev.pos[n + i];
-  s[2] = ev.vel[i];
-  s[3] = ev.vel[n + i];
-  s[4] = ev.pos[2 * n + i];
-  s[5] = ev.pos[3 * n + i];
-}
-__device__ __forceinline__ void reacher_store(const sac_envs& ev, int i, const double s[6]) {
-  const size_t n = (size_t)ev.cfg.num_envs;
-  ev.pos[i] = s[0];
-  ev.pos[n + i] = s[1];
-  ev.vel[i] = s[2];
-  ev.vel[n + i] = s[3];
-  ev.pos[2 * n + i] = s[4];
-  ev.pos[3 * n + i] = s[5];
-}
-
-// ---- Balancing cart-pole (sac/control_envs.py CartPoleEnv) ------------------
-// State s = (x, xdot, th, thdot) in float64, the order of CartPoleEnv.state.
-// Every operation is the host class's, in its order.  sin th and cos th feed
-// back into the state, so the trajectory follows the host's to the library's
-// few float64 ulps, not to the bit.
-#define SAC_CARTPOLE_OBS_DIM 4
-#define SAC_CARTPOLE_G 9.8
-#define SAC_CARTPOLE_M_CART 1.0
-#define SAC_CARTPOLE_M_POLE 0.1
-#define SAC_CARTPOLE_HALF_LEN 0.5
-#define SAC_CARTPOLE_FORCE_MAG 10.0
-#define SAC_CARTPOLE_X_LIMIT 2.4
-#define SAC_CARTPOLE_TH_LIMIT (12.0 * 2.0 * SAC_PI / 360.0)
-#define SAC_CARTPOLE_RESET_HALF_SIDE 0.05
-
-// The observation of a state, in fp32
-__host__ __device__ inline void cartpole_obs(const double s[4], float obs[SAC_CARTPOLE_OBS_DIM]) {
-  for (int k = 0; k < SAC_CARTPOLE_OBS_DIM; ++k) obs[k] = (float)s[k];
-}
-
-// One Euler step from s with action a: the new state in place, its observation
-// in fp32; returns terminated (the new state is outside a limit).  The reward
-// is 1.0 on every step, the failing one included.
-__host__ __device__ inline bool cartpole_dynamics(double s[4], float a, double action_low, double action_high,
-                                                  double dt, float obs[SAC_CARTPOLE_OBS_DIM]) {
-  const double u = (double)clip_f32(a, (float)action_low, (float)action_high);
-  const double x = s[0], xdot = s[1], th = s[2], thdot = s[3];
-  const double F = SAC_CARTPOLE_FORCE_MAG * u, c = cos(th), sn = sin(th);
-  const double M = SAC_CARTPOLE_M_CART + SAC_CARTPOLE_M_POLE;
-  const double temp = (F + SAC_CARTPOLE_M_POLE * SAC_CARTPOLE_HALF_LEN * thdot * thdot * sn) / M;
-  const double thacc =
-      (SAC_CARTPOLE_G * sn - c * temp) / (SAC_CARTPOLE_HALF_LEN * (4.0 / 3.0 - SAC_CARTPOLE_M_POLE * c * c / M));
-  const double xacc = temp - SAC_CARTPOLE_M_POLE * SAC_CARTPOLE_HALF_LEN * thacc * c / M;
-  s[0] = x + dt * xdot;
-  s[1] = xdot + dt * xacc;
-  s[2] = th + dt * thdot;
-  s[3] = thdot + dt * thacc;
-  cartpole_obs(s, obs);
-  return fabs(s[0]) > SAC_CARTPOLE_X_LIMIT || fabs(s[2]) > SAC_CARTPOLE_TH_LIMIT;
-}
-
-// The reset draw of env row `row` at vector step t: the four uniforms of the
-// row's ENV_WHICH_RESET block 0 give x, xdot, th, thdot in [-0.05, 0.05).
-__host__ __device__ inline void cartpole_reset_draw(uint64_t seed, uint64_t t, uint32_t row, double s[4]) {
-  float u[4];
-  philox_uniform4(seed, t, row, ENV_WHICH_RESET, 0, u);
-  for (int k = 0; k < 4; ++k) s[k] = SAC_CARTPOLE_RESET_HALF_SIDE * (2.0 * (double)u[k] - 1.0);
-}
-
-// Row i's state in the component-major blocks ev.pos [2][N] (x, th) and ev.vel [2][N] (xdot, thdot)
-__device__ __forceinline__ void cartpole_load(const sac_envs& ev, int i, double s[4]) {
-  const size_t n = (size_t)ev.cfg.num_envs;
-  s[0] = ev.pos[i];
-  s[1] = ev.vel[i];
-  s[2] = ev.pos[n + i];
-  s[3] = ev.vel[n + i];
-}
-__device__ __forceinline__ void cartpole_store(const sac_envs& ev, int i, const double s[4]) {
-  const size_t n = (size_t)ev.cfg.num_envs;
-  ev.pos[i] = s[0];
-  ev.vel[i] = s[1];
-  ev.pos[n + i] = s[2];
-  ev.vel[n + i] = s[3];
-}
-
 struct EnvOut {
   double reward;  // as the host class returns it (probe 1's fp32 reward widened, as float(r) does)
   bool terminated, truncated;
 };
 
-// The pendulum's step of env_step: state (th, thdot) in ev.pos / ev.vel, three
-// observation components, no termination, truncation at max_steps; a truncated
-// row takes its reset draw of this t as its current state and observation.
+// ---- The control tasks -------------------------------------------------------
+// EnvTask<KC> describes the task of class KC:
+//   KIND, NAME           its sac_env_kind and that enumerator's spelling;
+//   OBS, ACT             observation and action components;
+//   NS                   float64 state components, in the order of the host class's .state;
+//   POS_ROWS, VEL_ROWS   rows of the component-major blocks sac_envs.pos [POS_ROWS][N] and .vel [VEL_ROWS][N];
+//   home(k)              where state component k lives: a row of .vel or of .pos;
+//   obs(s, o)            the fp32 observation of a state;
+//   dynamics(s, a, cfg, obs_out, out)   one step from s with actions a[ACT]: the new state in place, its
+//                        observation, and out.reward / out.terminated;
+//   reset_draw(seed, t, row, s)   the state row `row` restarts from at vector step t, from the four uniforms
+//                        of the row's ENV_WHICH_RESET block 0.
+// Every operation is the host class's, in its order (the library is built with
+// -ffp-contract=off: no fused multiply-adds).
+template <int KC>
+struct EnvTask;
+struct EnvHome {
+  int vel, row;  // row `row` of sac_envs.vel (vel = 1) or of sac_envs.pos (vel = 0)
+};
+#define SAC_PI 3.141592653589793
+
+// The probes share one class and have no description; their one action component is all the rollout asks.
+template <>
+struct EnvTask<ENV_CLASS_PROBES> {
+  static constexpr int ACT = 1;
+};
+
+// Pendulum swing-up (sac/control_envs.py PendulumEnv).  State (th, thdot); g =
+// 10, m = l = 1, so 3 g / (2 l) = 15 and 3 / (m l^2) = 3 exactly.
+template <>
+struct EnvTask<ENV_CLASS_PENDULUM> {
+  static constexpr int KIND = SAC_ENV_PENDULUM, OBS = 3, ACT = 1, NS = 2, POS_ROWS = 1, VEL_ROWS = 1;
+  static constexpr const char* NAME = "SAC_ENV_PENDULUM";
+  static constexpr double MAX_SPEED = 8.0;
+  static constexpr EnvHome home(int k) { return EnvHome{k, 0}; }
+
+  // Python's ((th + pi) % (2 pi)) - pi: the angle in [-pi, pi)
+  __host__ __device__ static inline double angle(double th) {
+    double an = fmod(th + SAC_PI, 2.0 * SAC_PI);
+    if (an < 0.0) an += 2.0 * SAC_PI;
+    return an - SAC_PI;
+  }
+  __host__ __device__ static inline void obs(const double s[NS], float o[OBS]) {
+    o[0] = (float)cos(s[0]);
+    o[1] = (float)sin(s[0]);
+    o[2] = (float)s[1];
+  }
+  // The reward is the PRE-step state's; never terminated.
+  __host__ __device__ static inline void dynamics(double s[NS], const float a[ACT], const sac_env_config& c,
+                                                  float obs_out[OBS], EnvOut& out) {
+    const double u = (double)clip_f32(a[0], (float)c.action_low, (float)c.action_high);
+    const double an = angle(s[0]);
+    out.reward = -(an * an + 0.1 * s[1] * s[1] + 0.001 * u * u);
+    out.terminated = false;
+    double v = s[1] + (15.0 * sin(s[0]) + 3.0 * u) * c.dt;
+    v = v < -MAX_SPEED ? -MAX_SPEED : (v > MAX_SPEED ? MAX_SPEED : v);
+    s[0] = s[0] + v * c.dt;
+    s[1] = v;
+    obs(s, obs_out);
+  }
+  // th ~ U[-pi, pi), thdot ~ U[-1, 1) from the block's first two uniforms
+  __host__ __device__ static inline void reset_draw(uint64_t seed, uint64_t t, uint32_t row, double s[NS]) {
+    float u[4];
+    philox_uniform4(seed, t, row, ENV_WHICH_RESET, 0, u);
+    s[0] = SAC_PI * (2.0 * (double)u[0] - 1.0);
+    s[1] = 2.0 * (double)u[1] - 1.0;
+  }
+};
+
+// Two-link reacher (sac/control_envs.py ReacherEnv).  State (th1, th2, w1, w2,
+// tx, ty).  Sine and cosine enter the reward and the observation only, never the
+// state: the state trajectory is the host's bit for bit whatever library they
+// come from.
+template <>
+struct EnvTask<ENV_CLASS_REACHER> {
+  static constexpr int KIND = SAC_ENV_REACHER, OBS = 10, ACT = 2, NS = 6, POS_ROWS = 4, VEL_ROWS = 2;
+  static constexpr const char* NAME = "SAC_ENV_REACHER";
+  static constexpr double L1 = 0.1, L2 = 0.1, GAIN = 10.0, DAMP = 2.0, CTRL_COST = 0.1, TARGET_HALF_SIDE = 0.14;
+  // pos: th1, th2, tx, ty; vel: w1, w2
+  static constexpr EnvHome home(int k) { return k < 2 ? EnvHome{0, k} : k < 4 ? EnvHome{1, k - 2} : EnvHome{0, k - 2}; }
+
+  // Fingertip minus target
+  __host__ __device__ static inline void tip(const double s[NS], double& dx, double& dy) {
+    dx = (L1 * cos(s[0]) + L2 * cos(s[0] + s[1])) - s[4];
+    dy = (L1 * sin(s[0]) + L2 * sin(s[0] + s[1])) - s[5];
+  }
+  __host__ __device__ static inline void obs(const double s[NS], float o[OBS]) {
+    double dx, dy;
+    tip(s, dx, dy);
+    o[0] = (float)cos(s[0]);
+    o[1] = (float)cos(s[1]);
+    o[2] = (float)sin(s[0]);
+    o[3] = (float)sin(s[1]);
+    o[4] = (float)s[4];
+    o[5] = (float)s[5];
+    o[6] = (float)s[2];
+    o[7] = (float)s[3];
+    o[8] = (float)dx;
+    o[9] = (float)dy;
+  }
+  // The reward is the PRE-step state's; never terminated.
+  __host__ __device__ static inline void dynamics(double s[NS], const float a[ACT], const sac_env_config& c,
+                                                  float obs_out[OBS], EnvOut& out) {
+    const double u0 = (double)clip_f32(a[0], (float)c.action_low, (float)c.action_high);
+    const double u1 = (double)clip_f32(a[1], (float)c.action_low, (float)c.action_high);
+    double dx, dy;
+    tip(s, dx, dy);
+    out.reward = -sqrt(dx * dx + dy * dy) - CTRL_COST * (u0 * u0 + u1 * u1);
+    out.terminated = false;
+    s[2] = s[2] + (GAIN * u0 - DAMP * s[2]) * c.dt;
+    s[3] = s[3] + (GAIN * u1 - DAMP * s[3]) * c.dt;
+    s[0] = s[0] + s[2] * c.dt;
+    s[1] = s[1] + s[3] * c.dt;
+    obs(s, obs_out);
+  }
+  // The target in the square of half side 0.14, both angles in [-pi, pi); the arm starts at rest.
+  __host__ __device__ static inline void reset_draw(uint64_t seed, uint64_t t, uint32_t row, double s[NS]) {
+    float u[4];
+    philox_uniform4(seed, t, row, ENV_WHICH_RESET, 0, u);
+    s[4] = TARGET_HALF_SIDE * (2.0 * (double)u[0] - 1.0);
+    s[5] = TARGET_HALF_SIDE * (2.0 * (double)u[1] - 1.0);
+    s[0] = SAC_PI * (2.0 * (double)u[2] - 1.0);
+    s[1] = SAC_PI * (2.0 * (double)u[3] - 1.0);
+    s[2] = 0.0;
+    s[3] = 0.0;
+  }
+};
+
+// Balancing cart-pole (sac/control_envs.py CartPoleEnv).  State (x, xdot, th,
+// thdot).  sin th and cos th feed back into the state, so the trajectory follows
+// the host's to the library's few float64 ulps, not to the bit.
+template <>
+struct EnvTask<ENV_CLASS_CARTPOLE> {
+  static constexpr int KIND = SAC_ENV_CARTPOLE, OBS = 4, ACT = 1, NS = 4, POS_ROWS = 2, VEL_ROWS = 2;
+  static constexpr const char* NAME = "SAC_ENV_CARTPOLE";
+  static constexpr double G = 9.8, M_CART = 1.0, M_POLE = 0.1, HALF_LEN = 0.5, FORCE_MAG = 10.0, X_LIMIT = 2.4,
+                          TH_LIMIT = 12.0 * 2.0 * SAC_PI / 360.0, RESET_HALF_SIDE = 0.05;
+  // pos: x, th; vel: xdot, thdot
+  static constexpr EnvHome home(int k) { return EnvHome{k & 1, k >> 1}; }
+
+  __host__ __device__ static inline void obs(const double s[NS], float o[OBS]) {
+    for (int k = 0; k < OBS; ++k) o[k] = (float)s[k];
+  }
+  // One Euler step; terminated: the new state is outside a limit.  The reward
+  // is 1.0 on every step, the failing one included.
+  __host__ __device__ static inline void dynamics(double s[NS], const float a[ACT], const sac_env_config& cfg,
+                                                  float obs_out[OBS], EnvOut& out) {
+    const double dt = cfg.dt;
+    const double u = (double)clip_f32(a[0], (float)cfg.action_low, (float)cfg.action_high);
+    const double x = s[0], xdot = s[1], th = s[2], thdot = s[3];
+    const double F = FORCE_MAG * u, c = cos(th), sn = sin(th);
+    const double M = M_CART + M_POLE;
+    const double temp = (F + M_POLE * HALF_LEN * thdot * thdot * sn) / M;
+    const double thacc = (G * sn - c * temp) / (HALF_LEN * (4.0 / 3.0 - M_POLE * c * c / M));
+    const double xacc = temp - M_POLE * HALF_LEN * thacc * c / M;
+    s[0] = x + dt * xdot;
+    s[1] = xdot + dt * xacc;
+    s[2] = th + dt * thdot;
+    s[3] = thdot + dt * thacc;
+    obs(s, obs_out);
+    out.terminated = fabs(s[0]) > X_LIMIT || fabs(s[2]) > TH_LIMIT;
+    out.reward = 1.0;
+  }
+  // x, xdot, th, thdot in [-0.05, 0.05)
+  __host__ __device__ static inline void reset_draw(uint64_t seed, uint64_t t, uint32_t row, double s[NS]) {
+    float u[4];
+    philox_uniform4(seed, t, row, ENV_WHICH_RESET, 0, u);
+    for (int k = 0; k < 4; ++k) s[k] = RESET_HALF_SIDE * (2.0 * (double)u[k] - 1.0);
+  }
+};
+
+// Rows of .vel (vel = 1) or .pos (vel = 0) the map of a task names: one past its highest
+template <typename Task>
+constexpr int task_rows(int vel) {
+  int rows = 0;
+  for (int k = 0; k < Task::NS; ++k)
+    if (Task::home(k).vel == vel && Task::home(k).row >= rows) rows = Task::home(k).row + 1;
+  return rows;
+}
+// Every description agrees with the width table of include/sac_engine.h and with its own map
+template <typename Task>
+constexpr bool task_matches_header() {
+  return Task::OBS == SAC_ENV_OBS_DIM(Task::KIND) && Task::ACT == SAC_ENV_ACT_DIM(Task::KIND) &&
+         Task::POS_ROWS == SAC_ENV_POS_ROWS(Task::KIND) && Task::VEL_ROWS == SAC_ENV_VEL_ROWS(Task::KIND) &&
+         Task::POS_ROWS == task_rows<Task>(0) && Task::VEL_ROWS == task_rows<Task>(1);
+}
+static_assert(task_matches_header<EnvTask<ENV_CLASS_PENDULUM>>(), "the pendulum's widths");
+static_assert(task_matches_header<EnvTask<ENV_CLASS_REACHER>>(), "the reacher's widths");
+static_assert(task_matches_header<EnvTask<ENV_CLASS_CARTPOLE>>(), "the cart-pole's widths");
+
+// The one map from a kind to its class: f(std::integral_constant<int, KC>) with KC the class of `kind`
+// (whatever is no task's kind is a probe's).
+template <typename F>
+__host__ __device__ __forceinline__ decltype(auto) with_env_class(int kind, F&& f) {
+  if (kind == SAC_ENV_PENDULUM) return f(std::integral_constant<int, ENV_CLASS_PENDULUM>{});
+  if (kind == SAC_ENV_REACHER) return f(std::integral_constant<int, ENV_CLASS_REACHER>{});
+  if (kind == SAC_ENV_CARTPOLE) return f(std::integral_constant<int, ENV_CLASS_CARTPOLE>{});
+  return f(std::integral_constant<int, ENV_CLASS_PROBES>{});
+}
+// One kind of every class, for what must touch every instantiation
+constexpr int ENV_CLASS_KINDS[] = {SAC_ENV_POINT_MASS, SAC_ENV_PENDULUM, SAC_ENV_REACHER, SAC_ENV_CARTPOLE};
+
+// Row i's state from / to the component-major blocks ev.pos and ev.vel, in state component order
+template <typename Task>
+__device__ __forceinline__ void task_load(const sac_envs& ev, int i, double s[Task::NS]) {
+  const size_t n = (size_t)ev.cfg.num_envs;
+#pragma unroll
+  for (int k = 0; k < Task::NS; ++k) s[k] = (Task::home(k).vel ? ev.vel : ev.pos)[Task::home(k).row * n + i];
+}
+template <typename Task>
+__device__ __forceinline__ void task_store(const sac_envs& ev, int i, const double s[Task::NS]) {
+  const size_t n = (size_t)ev.cfg.num_envs;
+#pragma unroll
+  for (int k = 0; k < Task::NS; ++k) (Task::home(k).vel ? ev.vel : ev.pos)[Task::home(k).row * n + i] = s[k];
+}
+
+// A control task's step of env_step: truncation at max_steps, independent of
+// the task's own termination; a row that ended either way takes its reset draw
+// of this t as its current state and observation.
 // Inlined: a noinline call costs the rollout kernels 192 B of scratch per lane
 // (profiles/pendulum_rollout_resources.txt).
-__device__ __forceinline__ EnvOut env_step_pendulum(const sac_envs& ev, int i, uint64_t t, float action,
-                                                    float* final_obs) {
+template <typename Task>
+__device__ __forceinline__ EnvOut env_step_task(const sac_envs& ev, int i, uint64_t t, const float* act,
+                                                float* final_obs) {
   const sac_env_config& c = ev.cfg;
   const int step = ev.step[i] + 1;
-  float* cur = ev.obs + (size_t)i * SAC_PENDULUM_OBS_DIM;
-  double th = ev.pos[i], thdot = ev.vel[i];
-  float fo[SAC_PENDULUM_OBS_DIM];
+  float* cur = ev.obs + (size_t)i * Task::OBS;
+  double s[Task::NS];
+  task_load<Task>(ev, i, s);
+  float fo[Task::OBS];
   EnvOut o;
-  o.reward = pendulum_dynamics(th, thdot, action, c.action_low, c.action_high, c.dt, fo);
-  o.terminated = false;
-  o.truncated = step >= c.max_steps;
-  if (final_obs)
-    for (int k = 0; k < SAC_PENDULUM_OBS_DIM; ++k) final_obs[k] = fo[k];
-  if (o.truncated) {
-    pendulum_reset_draw(c.seed, t, (uint32_t)i, th, thdot);
-    pendulum_obs(th, thdot, fo);
-  }
-  for (int k = 0; k < SAC_PENDULUM_OBS_DIM; ++k) cur[k] = fo[k];
-  ev.step[i] = o.truncated ? 0 : step;
-  ev.pos[i] = th;
-  ev.vel[i] = thdot;
-  return o;
-}
-
-// The reacher's step of env_step: as the pendulum's, with two action components, ten observation
-// components and the state of reacher_load.
-__device__ __forceinline__ EnvOut env_step_reacher(const sac_envs& ev, int i, uint64_t t, float a0, float a1,
-                                                   float* final_obs) {
-  const sac_env_config& c = ev.cfg;
-  const int step = ev.step[i] + 1;
-  float* cur = ev.obs + (size_t)i * SAC_REACHER_OBS_DIM;
-  double s[6];
-  reacher_load(ev, i, s);
-  float fo[SAC_REACHER_OBS_DIM];
-  EnvOut o;
-  o.reward = reacher_dynamics(s, a0, a1, c.action_low, c.action_high, c.dt, fo);
-  o.terminated = false;
-  o.truncated = step >= c.max_steps;
-  if (final_obs)
-    for (int k = 0; k < SAC_REACHER_OBS_DIM; ++k) final_obs[k] = fo[k];
-  if (o.truncated) {
-    reacher_reset_draw(c.seed, t, (uint32_t)i, s);
-    reacher_obs(s, fo);
-  }
-  for (int k = 0; k < SAC_REACHER_OBS_DIM; ++k) cur[k] = fo[k];
-  ev.step[i] = o.truncated ? 0 : step;
-  reacher_store(ev, i, s);
-  return o;
-}
-
-// The cart-pole's step of env_step: the one kind whose rows end by failure, each at its own step;
-// terminated and truncated are independent, and a row that ended either way takes its reset draw of
-// this t.
-__device__ __forceinline__ EnvOut env_step_cartpole(const sac_envs& ev, int i, uint64_t t, float action,
-                                                    float* final_obs) {
-  const sac_env_config& c = ev.cfg;
-  const int step = ev.step[i] + 1;
-  float* cur = ev.obs + (size_t)i * SAC_CARTPOLE_OBS_DIM;
-  double s[4];
-  cartpole_load(ev, i, s);
-  float fo[SAC_CARTPOLE_OBS_DIM];
-  EnvOut o;
-  o.terminated = cartpole_dynamics(s, action, c.action_low, c.action_high, c.dt, fo);
-  o.reward = 1.0;
+  Task::dynamics(s, act, c, fo, o);
   o.truncated = step >= c.max_steps;
   const bool done = o.terminated || o.truncated;
   if (final_obs)
-    for (int k = 0; k < SAC_CARTPOLE_OBS_DIM; ++k) final_obs[k] = fo[k];
+    for (int k = 0; k < Task::OBS; ++k) final_obs[k] = fo[k];
   if (done) {
-    cartpole_reset_draw(c.seed, t, (uint32_t)i, s);
-    cartpole_obs(s, fo);
+    Task::reset_draw(c.seed, t, (uint32_t)i, s);
+    Task::obs(s, fo);
   }
-  for (int k = 0; k < SAC_CARTPOLE_OBS_DIM; ++k) cur[k] = fo[k];
+  for (int k = 0; k < Task::OBS; ++k) cur[k] = fo[k];
   ev.step[i] = done ? 0 : step;
-  cartpole_store(ev, i, s);
+  task_store<Task>(ev, i, s);
   return o;
 }
 
-// One step of environment row i at vector step t with the action's first
-// component `action` (and its second, a1, for the one kind that takes two).
-// Writes the observation stepped to into final_obs[obs_dim] (unless NULL), the
-// environment's new current observation (the reset observation where the
-// episode ended) into ev.obs, and its step counter / position.
+// A control task's part of sac_envs_reset_kernel: the reset draw of t = 0, its observation, the state
+template <typename Task>
+__device__ __forceinline__ void task_reset(const sac_envs& ev, int i, uint64_t seed, float* cur) {
+  double s[Task::NS];
+  Task::reset_draw(seed, 0, (uint32_t)i, s);
+  Task::obs(s, cur);
+  task_store<Task>(ev, i, s);
+}
+
+// One step of environment row i at vector step t with the action components
+// act[ACT of the class].  Writes the observation stepped to into
+// final_obs[obs_dim] (unless NULL), the environment's new current observation
+// (the reset observation where the episode ended) into ev.obs, and its step
+// counter / state.
 // KC is the kind class (EnvClass), decided by the launch: the rollout kernels are
-// compiled once per class, so the probes' kernels hold none of the pendulum's, the
-// reacher's or the cart-pole's code (behind a run-time branch the pendulum cost them 16 more
-// spilled SGPRs and 1-2 % per launch).
+// compiled once per class, so no class's kernels hold another's code (behind a
+// run-time branch the pendulum cost the probes 16 more spilled SGPRs and 1-2 %
+// per launch).
 template <int KC>
-__device__ __forceinline__ EnvOut env_step(const sac_envs& ev, int i, uint64_t t, float action, float a1,
-                                           float* final_obs) {
-  if (KC == ENV_CLASS_PENDULUM) return env_step_pendulum(ev, i, t, action, final_obs);
-  if (KC == ENV_CLASS_REACHER) return env_step_reacher(ev, i, t, action, a1, final_obs);
-  if (KC == ENV_CLASS_CARTPOLE) return env_step_cartpole(ev, i, t, action, final_obs);
+__device__ __forceinline__ EnvOut env_step(const sac_envs& ev, int i, uint64_t t, const float* act, float* final_obs) {
+  if constexpr (KC != ENV_CLASS_PROBES) return env_step_task<EnvTask<KC>>(ev, i, t, act, final_obs);
+  const float action = act[0];
   const sac_env_config& c = ev.cfg;
   const int O = c.obs_dim;
   const int step = ev.step[i] + 1;
@@ -454,30 +429,17 @@ __global__ void sac_envs_reset_kernel(sac_envs ev, uint64_t seed) {
       for (int k = 0; k < 4; ++k)
         if (4 * b + k < O) cur[4 * b + k] = env_uniform_obs(u[k]);
     }
-  } else if (c.kind != SAC_ENV_PENDULUM && c.kind != SAC_ENV_REACHER && c.kind != SAC_ENV_CARTPOLE) {
+  } else if (!SAC_ENV_VEL_ROWS(c.kind)) {
     cur[0] = c.kind == SAC_ENV_POINT_MASS ? (float)c.start_pos : 0.f;
   }
   ev.step[i] = 0;
   ev.ep_length[i] = 0;
-  if (c.kind == SAC_ENV_CARTPOLE) {
-    double s[4];
-    cartpole_reset_draw(seed, 0, (uint32_t)i, s);
-    cartpole_obs(s, cur);
-    cartpole_store(ev, i, s);
-  } else if (c.kind == SAC_ENV_REACHER) {
-    double s[6];
-    reacher_reset_draw(seed, 0, (uint32_t)i, s);
-    reacher_obs(s, cur);
-    reacher_store(ev, i, s);
-  } else if (c.kind == SAC_ENV_PENDULUM) {
-    double th, thdot;
-    pendulum_reset_draw(seed, 0, (uint32_t)i, th, thdot);
-    pendulum_obs(th, thdot, cur);
-    ev.pos[i] = th;
-    ev.vel[i] = thdot;
-  } else {
-    ev.pos[i] = c.kind == SAC_ENV_POINT_MASS ? c.start_pos : 0.0;
-  }
+  with_env_class(c.kind, [&](auto kc) {
+    if constexpr (decltype(kc)::value != ENV_CLASS_PROBES)
+      task_reset<EnvTask<decltype(kc)::value>>(ev, i, seed, cur);
+    else
+      ev.pos[i] = c.kind == SAC_ENV_POINT_MASS ? c.start_pos : 0.0;
+  });
   ev.ep_return[i] = 0.0;
 }
 
@@ -488,18 +450,10 @@ __global__ void sac_envs_step_kernel(sac_envs ev, const float* __restrict__ acti
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= ev.cfg.num_envs) return;
   const int O = ev.cfg.obs_dim;
-  const int A = env_act_dim(ev.cfg.kind);
-  const float a = actions[(size_t)i * A];
+  const float* act = actions + (size_t)i * env_act_dim(ev.cfg.kind);
   float* fin = final_obs + (size_t)i * O;
-  EnvOut o;
-  if (ev.cfg.kind == SAC_ENV_REACHER)
-    o = env_step<ENV_CLASS_REACHER>(ev, i, t, a, actions[(size_t)i * A + 1], fin);
-  else if (ev.cfg.kind == SAC_ENV_CARTPOLE)
-    o = env_step<ENV_CLASS_CARTPOLE>(ev, i, t, a, 0.f, fin);
-  else if (ev.cfg.kind == SAC_ENV_PENDULUM)
-    o = env_step<ENV_CLASS_PENDULUM>(ev, i, t, a, 0.f, fin);
-  else
-    o = env_step<ENV_CLASS_PROBES>(ev, i, t, a, 0.f, fin);
+  const EnvOut o =
+      with_env_class(ev.cfg.kind, [&](auto kc) { return env_step<decltype(kc)::value>(ev, i, t, act, fin); });
   env_account(ev, i, t, o);
   for (int k = 0; k < O; ++k) obs[(size_t)i * O + k] = ev.obs[(size_t)i * O + k];
   reward[i] = (float)o.reward;
@@ -547,7 +501,9 @@ __device__ __forceinline__ void rollout_step_body(const EngineDev* __restrict__ 
     const int64_t slot = (pos + i) % rb.capacity;
     if (store)
       for (int k = 0; k < O; ++k) rb.obs[slot * rs.obs + k] = ev.obs[(size_t)i * O + k];
-    float a0 = 0.f, a1 = 0.f;  // what the environment takes: registers, not a re-read of the replay row
+    // what the environment takes: registers, not a re-read of the replay row (so never indexed by a run-time j)
+    constexpr int NA = EnvTask<KC>::ACT;
+    float act[NA] = {};
     for (int p = 0; 2 * p < A; ++p) {
       float e2[2] = {0.f, 0.f};
       if (!deterministic) philox_normal2(E.seed, t, (uint32_t)i, ENV_WHICH_NOISE, (uint32_t)p, e2[0], e2[1]);
@@ -565,12 +521,13 @@ __device__ __forceinline__ void rollout_step_body(const EngineDev* __restrict__ 
           const float z = mu + e * sd;
           a = tanhf(z) * scale;
         }
-        if (j == 0) a0 = a;
-        if (KC == ENV_CLASS_REACHER && j == 1) a1 = a;
+#pragma unroll
+        for (int k = 0; k < NA; ++k)
+          if (j == k) act[k] = a;
         if (store) rb.act[slot * rs.act + j] = a;
       }
     }
-    const EnvOut eo = env_step<KC>(ev, i, t, a0, a1, store ? rb.next_obs + slot * rs.obs : nullptr);
+    const EnvOut eo = env_step<KC>(ev, i, t, act, store ? rb.next_obs + slot * rs.obs : nullptr);
     env_account(ev, i, t, eo);
     if (store) {
       rb.rew[slot * rs.one] = (float)eo.reward;
@@ -586,7 +543,7 @@ __device__ __forceinline__ void rollout_step_body(const EngineDev* __restrict__ 
 
 // One workgroup per SAC_ROWS environments; (size, pos, t) are host arguments,
 // new_size / new_pos computed by the host as sac_replay_push does.  KC:
-// env_class(ev.cfg.kind) (the host picks the instantiation).
+// the class of ev.cfg.kind (the host picks the instantiation: with_env_class).
 template <typename T, int KC>
 __global__ void __launch_bounds__(SAC_THREADS) sac_rollout_step_kernel(const EngineDev* __restrict__ Ep, sac_envs ev,
                                                                       sac_replay rb, int64_t pos, int64_t new_size,

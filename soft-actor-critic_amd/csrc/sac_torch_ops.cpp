@@ -28,10 +28,10 @@
 // act_dim, row_stride, off_obs, off_act, off_rew, off_next_obs, off_done]
 // (offsets in floats from storage.data_ptr(); row_stride 0 = struct-of-arrays).
 // Environment state (envs_*, rollout_step): `obs` [N][O] fp32, `counters`
-// int32 [2][N] (step in episode, episode length), `dstate` float64 [2][N]
-// (position, episode return; the pendulum: [3][N], angle, episode return,
-// angular velocity; the reacher: [7][N], th1, th2, tx, ty, episode return, w1,
-// w2; the cart-pole: [5][N], x, th, episode return, xdot, thdot), `ring` float64 [S][N][2] (the sac_env_episode
+// int32 [2][N] (step in episode, episode length), `dstate` float64
+// [SAC_ENV_POS_ROWS + 1 + SAC_ENV_VEL_ROWS][N] (the kind's sac_envs.pos rows,
+// the episode return, its sac_envs.vel rows: include/sac_engine.h has the
+// widths and each task's components), `ring` float64 [S][N][2] (the sac_env_episode
 // cells: return, then length and ended as two int32); `icfg` = [kind, num_envs,
 // obs_dim, max_steps], `params` = the 11 doubles of sac_env_config in order.
 // Engine state: `engine` is the sac_engine* handle (int64) from
@@ -348,10 +348,8 @@ sac_envs make_envs(const at::Tensor& obs, const at::Tensor& counters, const at::
   TORCH_CHECK(icfg.size() == 4, "icfg must be [kind, num_envs, obs_dim, max_steps]");
   TORCH_CHECK(params.size() == 11, "params must hold the 11 doubles of sac_env_config");
   const int64_t N = icfg[1], O = icfg[2];
-  const bool pendulum = icfg[0] == SAC_ENV_PENDULUM, reacher = icfg[0] == SAC_ENV_REACHER;
-  const bool cartpole = icfg[0] == SAC_ENV_CARTPOLE;
   // the kind's sac_envs.pos / .vel
-  const int64_t pos_rows = reacher ? 4 : (cartpole ? 2 : 1), vel_rows = reacher || cartpole ? 2 : (pendulum ? 1 : 0);
+  const int64_t pos_rows = SAC_ENV_POS_ROWS(icfg[0]), vel_rows = SAC_ENV_VEL_ROWS(icfg[0]);
   TORCH_CHECK(N >= 1 && N <= INT32_MAX && O >= 1 && O <= INT32_MAX, "num_envs and obs_dim must be >= 1");
   check_f32(obs, "env obs");
   TORCH_CHECK(obs.dim() == 2 && obs.size(0) == N && obs.size(1) == O, "env obs must be [num_envs][obs_dim]");

@@ -18,19 +18,21 @@ Two ways to step:
   the write into the replay ring), the step of ``SAC.run_device_training_loop``.
 
 The only randomness is ``RandomObsBinaryRewardEnv``'s observations and the
-reset states of ``PendulumEnv``, ``ReacherEnv`` and ``CartPoleEnv``: Philox draws keyed by the seed given to
+reset states of the control tasks: Philox draws keyed by the seed given to
 ``reset`` with counter (vector step, env row), so a run is reproducible
 whatever order the workgroups run in (the host classes draw from numpy's
-generator instead: same distribution, other numbers).  The pendulum's float64
-arithmetic is the host class's in the same order; its ``sin`` / ``cos`` are the
-device library's, so its fp32 observations and rewards may differ from the
-host's in the last bit.  The same holds for the reacher, whose state never
-takes a sine or cosine in: its (angles, speeds, target) are the host class's
-bit for bit.  The reacher is the one kind with two action components:
-``act_dim`` is the host class's action space's, per kind.  The cart-pole is the
-one kind whose episodes end by failure, at different steps in different rows;
-``sin`` / ``cos`` feed back into its state, which therefore follows the host
-class's to a few float64 ulps, not to the bit.
+generator instead: same distribution, other numbers).  ``obs_dim`` and
+``act_dim`` are the host class's spaces', per kind (``include/sac_engine.h``
+has the table).  A control task's float64 arithmetic is the host class's in the
+same order; its ``sin`` / ``cos`` are the device library's, so its fp32
+observations and rewards may differ from the host's in the last bit.  Per task:
+
+* ``PendulumEnv``: one torque, never terminated;
+* ``ReacherEnv``: two torques; its state never takes a sine or cosine in, so
+  its (angles, speeds, target) are the host class's bit for bit;
+* ``CartPoleEnv``: one force; episodes end by failure, at different steps in
+  different rows; ``sin`` / ``cos`` feed back into its state, which therefore
+  follows the host class's to a few float64 ulps, not to the bit.
 
 Episode statistics: every step writes each env's running (return, length,
 ended) into a dense ring ``[ring_steps][N]`` indexed by ``t % ring_steps``;
@@ -62,7 +64,8 @@ KINDS = {
     "reacher": (16, control_envs.ReacherEnv),
     "cartpole": (32, control_envs.CartPoleEnv),
 }
-# rows of the float64 state tensor per kind: the kind's position block, the episode return, its velocity block
+# rows of the float64 state tensor of a control task: its position block, the episode return, its velocity block
+# (include/sac_engine.h: SAC_ENV_POS_ROWS + 1 + SAC_ENV_VEL_ROWS, which has each block's components)
 _DSTATE_ROWS = {"pendulum": 3, "reacher": 7, "cartpole": 5}
 _BY_CLASS = {cls.__name__: name for name, (_, cls) in KINDS.items()}
 _BY_CODE = {code: name for name, (code, _) in KINDS.items()}
@@ -98,6 +101,11 @@ def kind_name(kind_or_name) -> str:
         raise ValueError(f"unknown device environment {kind_or_name!r} (one of "
                          f"{sorted(set(KINDS) - _CLASS_OR_CODE_ONLY)}, a host class, its name or a kind code)")
     return name
+
+
+def dstate_rows(kind: str) -> int:
+    """Rows of the float64 state tensor of a kind; a probe has its position and the episode return."""
+    return _DSTATE_ROWS.get(kind, 2)
 
 
 class DeviceVectorEnv:
@@ -148,9 +156,7 @@ class DeviceVectorEnv:
             raise ValueError("ring_steps must be >= 1")
         self.obs = torch.zeros(N, self.obs_dim, dtype=torch.float32, device=dev)
         self.counters = torch.zeros(2, N, dtype=torch.int32, device=dev)   # step in episode, episode length
-        # position (the pendulum: angle), episode return; the pendulum adds its angular velocity.  The reacher:
-        # th1, th2, tx, ty, episode return, w1, w2.  The cart-pole: x, th, episode return, xdot, thdot
-        self.dstate = torch.zeros(_DSTATE_ROWS.get(self.kind, 2), N, dtype=torch.float64, device=dev)
+        self.dstate = torch.zeros(dstate_rows(self.kind), N, dtype=torch.float64, device=dev)
         self.ring = torch.zeros(self.ring_steps, N, 2, dtype=torch.float64, device=dev)
         self.seed = 0
         self.t = 0  # vector steps taken since the last reset; step k (0-based) is RNG step t = k + 1

@@ -17,52 +17,23 @@ Device against device (fused step against step kernel and policy_act, graph
 against stepwise) is bit for bit."""
 import ctypes
 import math
+from functools import partial
 
 import numpy as np
 import pytest
 import torch
 
+import _control
+from _control import DEV, raw, twin_of, within_one_ulp
+
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda"
 u64, i32, vp = ctypes.c_uint64, ctypes.c_int32, ctypes.c_void_p
 f64p = ctypes.POINTER(ctypes.c_double)
 
 
-def _cfg(hidden=(40, 72), precision="fp32", capacity=1000, batch=32, warming=64, seed=3, log_episodes=False,
-         log_q=False):
-    hidden = list(hidden)
-    return {
-        "sac": {"gamma": 0.99, "tau": 0.005, "alpha": 0.2, "auto_entropy_tuning": True, "actor_lr": 3e-4,
-                "critic_lr": 3e-4, "alpha_lr": 3e-4},
-        "q_net": {"hidden_sizes": hidden, "hidden_layers_act": "relu", "output_activation": "identity"},
-        "policy_net": {"hidden_sizes": hidden, "hidden_layers_act": "relu", "output_activation": "identity",
-                       "log_std_min": -20, "log_std_max": 2, "action_scale": 1.0},
-        "buffer": {"capacity": capacity},
-        "train": {"gradient_steps_per_update": 1, "update_frequency": 1, "seed": seed, "batch_size": batch,
-                  "warming_steps": warming, "device": "cuda", "precision": precision, "graph_chunk": 4},
-        "logger": {"enabled": False, "env_name": "reacher", "agent_name": "SAC", "log_episode_stats": log_episodes,
-                   "log_q_values": log_q, "save_model": {"enabled": False, "path": None}},
-    }
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def raw(t):
-    return t.detach().contiguous().view(torch.uint8).cpu()
-
-
-def within_one_ulp(dev, host, what):
-    """dev fp32 within one fp32 ulp of host fp32, elementwise; returns the number of non-identical elements."""
-    dev, host = np.asarray(dev, np.float32), np.asarray(host, np.float32)
-    err = np.abs(dev.astype(np.float64) - host.astype(np.float64))
-    ok = err <= np.spacing(np.abs(host)).astype(np.float64)
-    n_diff = int(np.sum(bits(dev) != bits(host)))
-    print(f"{what}: {n_diff} of {dev.size} not identical, max |err| {err.max():.3e}, beyond 1 ulp {int(np.sum(~ok))}")
-    assert np.all(ok), f"{what}: {int(np.sum(~ok))} of {dev.size} beyond 1 ulp (max |err| {err.max():.3e})"
-    return n_diff
+_cfg = partial(_control.cfg, "reacher")
+make_agent = partial(_control.make_agent, _cfg, "ReacherEnv")
 
 
 @pytest.fixture(scope="module")
@@ -171,32 +142,6 @@ def test_step_matches_host_class(lib):
 
 
 # ---------------------------------------------------------------- 2. the fused rollout step
-def make_agent(N, max_steps=5, precision="fp32", layout="records", **cfg_kw):
-    from sac.agent import SAC
-    from sac.control_envs import ReacherEnv
-    from sac.device_envs import DeviceVectorEnv
-    from sac.replay_buffer import ReplayBuffer
-
-    cfg = _cfg(precision=precision, **cfg_kw)
-    dv = DeviceVectorEnv.from_env(ReacherEnv(max_steps=max_steps), N, device=DEV)
-    agent = SAC(dv, cfg)  # _set_seed resets the envs with train.seed
-    if layout != "records":
-        agent.replay_buffer = ReplayBuffer(cfg["buffer"]["capacity"], device=agent.device, layout=layout)
-    return agent, dv
-
-
-def twin_of(dv):
-    """Another DeviceVectorEnv in dv's state: stepping it with the stored actions is the step kernel's answer."""
-    from sac.control_envs import ReacherEnv
-    from sac.device_envs import DeviceVectorEnv
-
-    tw = DeviceVectorEnv.from_env(ReacherEnv(max_steps=dv.max_steps), dv.num_envs, device=DEV)
-    tw.seed, tw.t, tw._reset_done = dv.seed, dv.t, True
-    for name in ("obs", "counters", "dstate", "ring"):
-        getattr(tw, name).copy_(getattr(dv, name))
-    return tw
-
-
 @pytest.mark.parametrize("precision", ["fp32", "bf16"])
 @pytest.mark.parametrize("layout", ["records", "soa"])
 def test_fused_rollout_matches_step_kernel_and_policy_act(lib, layout, precision):

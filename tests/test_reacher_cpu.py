@@ -319,6 +319,30 @@ def test_kind_code_matches_header_and_python_tables():
             kind_name(unassigned)
 
 
+def test_width_macros_match_the_python_tables_and_the_host_spaces(tmp_path):
+    """include/sac_engine.h's width table, compiled as C, against what DeviceVectorEnv allocates and the host
+    classes' spaces, for every kind.  SAC_ENV_OBS_DIM is 0 where the obs_dim is the caller's."""
+    from sac.device_envs import KINDS, dstate_rows
+
+    src = ['#include <stdio.h>', '#include "sac_engine.h"', "int main(void) {"]
+    for code, _ in KINDS.values():
+        src.append(f'printf("%d %d %d %d\\n", (int)SAC_ENV_OBS_DIM({code}), (int)SAC_ENV_ACT_DIM({code}), '
+                   f'(int)SAC_ENV_POS_ROWS({code}), (int)SAC_ENV_VEL_ROWS({code}));')
+    src.append("return 0; }")
+    c = tmp_path / "widths.c"
+    c.write_text("\n".join(src))
+    exe = tmp_path / "widths"
+    subprocess.run(["gcc", "-std=c99", "-I", INCLUDE, str(c), "-o", str(exe)], check=True)
+    lines = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines()
+    assert len(lines) == len(KINDS) == 7
+    for (name, (code, cls)), line in zip(KINDS.items(), lines):
+        obs, act, pos_rows, vel_rows = (int(v) for v in line.split())
+        host = cls()
+        assert pos_rows + 1 + vel_rows == dstate_rows(name), name
+        assert act == int(np.prod(host.action_space.shape)), name
+        assert obs == (0 if name == "random_obs_binary" else int(np.prod(host.observation_space.shape))), name
+
+
 # ---------------------------------------------------------------- 4. the host class
 def test_spaces_and_constructor():
     from sac.control_envs import ReacherEnv
