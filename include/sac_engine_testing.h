@@ -46,6 +46,23 @@ int sac_debug_sample_indices_host(int64_t size, int32_t batch, uint64_t seed, ui
  * (models.py:83: eps of rsample).  Counter (step, b, which << 16 | j / 2), key
  * seed; Box-Muller gives dims 2p and 2p + 1. */
 int sac_debug_eps_host(uint64_t seed, uint64_t step, int32_t batch, int32_t act_dim, float *out);
+/* Host evaluation of csrc/sac_math.h, the acting head, target, seed and min-Q
+ * arithmetic that sac_policy_act_kernel, the rollout step and the stage path
+ * call, compiled for the host (so exp / tanh / log1p are the host libm's).
+ * in[SAC_HEAD_NIN][n] holds n independent elements, row k = input k;
+ * out[SAC_HEAD_NOUT][n] receives, per element: head_act(mu, lsr, e) (LS = the
+ * clamped log sigma, ACT_Z, ACT_ACT), head_act_mean (ACT_MEAN), head_act_lp and
+ * head_corr (ACT_LP, ACT_CORR: one action dim's log pi terms); Y = td_target(r,
+ * d, gamma, q1, q2, alpha, lp) with q1, q2 as the target critics and lp as
+ * log pi'; critic_seed(q1, Y, B) (SEED_D, SEED); minq_weights(q1, q2, -1 / B)
+ * (MINQ, W1, W2) and PI_TERM = alpha lp - MINQ. */
+enum { SAC_HEAD_IN_MU, SAC_HEAD_IN_LSR, SAC_HEAD_IN_E, SAC_HEAD_IN_Q1, SAC_HEAD_IN_Q2, SAC_HEAD_IN_R, SAC_HEAD_IN_D,
+       SAC_HEAD_IN_LP, SAC_HEAD_NIN };
+enum { SAC_HEAD_LS, SAC_HEAD_ACT_Z, SAC_HEAD_ACT_ACT, SAC_HEAD_ACT_MEAN, SAC_HEAD_ACT_LP, SAC_HEAD_ACT_CORR,
+       SAC_HEAD_Y, SAC_HEAD_SEED_D, SAC_HEAD_SEED, SAC_HEAD_MINQ, SAC_HEAD_W1, SAC_HEAD_W2, SAC_HEAD_PI_TERM,
+       SAC_HEAD_NOUT };
+int sac_debug_head_host(int32_t n, const float *in, float lo, float hi, float scale, float gamma, float alpha,
+                        int32_t B, float *out);
 /* The same draws computed on the device (out: device [2][batch][act_dim]). */
 int sac_debug_eps_device(uint64_t seed, uint64_t step, int32_t batch, int32_t act_dim, float *out, void *stream);
 /* Polls a hand-off wait makes before it gives up and sets the timeout flag

@@ -106,7 +106,7 @@ enum Act { ACT_ID = 0, ACT_RELU = 1, ACT_TANH = 2, ACT_ELU = 3, ACT_LEAKY = 4, A
 #define INV_SQRT2 0.70710678118654752440f
 #define INV_SQRT_2PI 0.39894228040143267794f
 
-__device__ __forceinline__ float act_fwd(int a, float p) {
+__host__ __device__ __forceinline__ float act_fwd(int a, float p) {
   switch (a) {
     case ACT_RELU: return p > 0.f ? p : 0.f;
     case ACT_TANH: return tanhf(p);
@@ -120,7 +120,7 @@ __device__ __forceinline__ float act_fwd(int a, float p) {
 
 // d act(p)/dp * g, torch backward formulas (threshold_backward on the result,
 // tanh_backward on the result, elu/selu backward on the input, exact gelu).
-__device__ __forceinline__ float act_bwd(int a, float p, float g) {
+__host__ __device__ __forceinline__ float act_bwd(int a, float p, float g) {
   switch (a) {
     case ACT_RELU: return p > 0.f ? g : 0.f;
     case ACT_TANH: { const float h = tanhf(p); return g * (1.f - h * h); }
@@ -134,14 +134,6 @@ __device__ __forceinline__ float act_bwd(int a, float p, float g) {
     case ACT_SELU: return p > 0.f ? g * SELU_SCALE : g * SELU_SCALE * SELU_ALPHA * expf(p);
     default: return g;
   }
-}
-
-// torch softplus(beta=1, threshold=20) and its derivative
-__device__ __forceinline__ float softplus20(float x) { return x > 20.f ? x : log1pf(expf(x)); }
-__device__ __forceinline__ float softplus20_grad(float x) {
-  if (x > 20.f) return 1.f;
-  const float z = expf(x);
-  return z / (z + 1.f);
 }
 
 // ----------------------------------------------------------------------------- RNG

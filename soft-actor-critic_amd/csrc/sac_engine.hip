@@ -33,6 +33,8 @@
 
 #define SAC_VERSION "sac-mi355x 0.1.0"
 
+#include "sac_device.h"
+#include "sac_math.h"
 #include "sac_phases.h"
 #include "sac_split.h"
 #include "sac_wide.h"
@@ -1252,6 +1254,29 @@ int sac_debug_eps_host(uint64_t seed, uint64_t step, int32_t batch, int32_t act_
   for (int which = 0; which < 2; ++which)
     for (int b = 0; b < batch; ++b)
       for (int p = 0; p < (act_dim + 1) / 2; ++p) eps_pair(seed, step, b, which, p, batch, act_dim, out);
+  return SAC_OK;
+}
+
+// sac_math.h compiled for the host, one element i < n at a time (include/sac_engine_testing.h)
+int sac_debug_head_host(int32_t n, const float* in, float lo, float hi, float scale, float gamma, float alpha,
+                        int32_t B, float* out) {
+  if (!in || !out || n < 1 || B < 1) return fail(SAC_E_INVALID, "need n >= 1, B >= 1, in != NULL, out != NULL");
+  for (int32_t i = 0; i < n; ++i) {
+    auto I = [&](int k) { return in[(size_t)k * n + i]; };
+    auto O = [&](int k) -> float& { return out[(size_t)k * n + i]; };
+    const float mu = I(SAC_HEAD_IN_MU), e = I(SAC_HEAD_IN_E);
+    const float q1 = I(SAC_HEAD_IN_Q1), q2 = I(SAC_HEAD_IN_Q2), lp = I(SAC_HEAD_IN_LP);
+    const HeadAct a = head_act(mu, I(SAC_HEAD_IN_LSR), e, lo, hi, scale);
+    O(SAC_HEAD_LS) = a.ls, O(SAC_HEAD_ACT_Z) = a.z, O(SAC_HEAD_ACT_ACT) = a.act;
+    O(SAC_HEAD_ACT_MEAN) = head_act_mean(mu, scale);
+    O(SAC_HEAD_ACT_LP) = head_act_lp(e, a.ls), O(SAC_HEAD_ACT_CORR) = head_corr(a.z);
+    const float y = td_target(I(SAC_HEAD_IN_R), I(SAC_HEAD_IN_D), gamma, q1, q2, alpha, lp);
+    const CriticSeed cs = critic_seed(q1, y, B);
+    O(SAC_HEAD_Y) = y, O(SAC_HEAD_SEED_D) = cs.d, O(SAC_HEAD_SEED) = cs.seed;
+    const MinQ w = minq_weights(q1, q2, -1.0f / (float)B);
+    O(SAC_HEAD_MINQ) = w.m, O(SAC_HEAD_W1) = w.w1, O(SAC_HEAD_W2) = w.w2;
+    O(SAC_HEAD_PI_TERM) = pi_loss_term(alpha, lp, w.m);
+  }
   return SAC_OK;
 }
 

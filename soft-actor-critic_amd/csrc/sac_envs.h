@@ -512,15 +512,8 @@ __device__ __forceinline__ void rollout_step_body(const EngineDev* __restrict__ 
         const int j = 2 * p + q;
         if (j >= A) break;
         float a;
-        if (deterministic) {
-          a = tanhf(o[j]) * scale;
-        } else {  // the head arithmetic of sac_policy_act_kernel
-          const float mu = o[j], lsr = o[A + j], e = e2[q];
-          const float ls = lsr < lo ? lo : (lsr > hi ? hi : lsr);
-          const float sd = expf(ls);
-          const float z = mu + e * sd;
-          a = tanhf(z) * scale;
-        }
+        if (deterministic) a = head_act_mean(o[j], scale);  // the acting head of sac_math.h, as sac_policy_act_kernel
+        else a = head_act(o[j], o[A + j], e2[q], lo, hi, scale).act;
 #pragma unroll
         for (int k = 0; k < NA; ++k)
           if (j == k) act[k] = a;

@@ -5,6 +5,7 @@
 #include <utility>
 
 #include "sac_device.h"
+#include "sac_math.h"
 
 #define SAC_DEV_LAYERS 6  // Linear layers per network supported by the kernels
 
@@ -732,11 +733,6 @@ __device__ __forceinline__ lf* mlp_backward(const AS_C NetDev& net, const lf* Go
   __syncthreads();
   return G;
 }
-
-#define LOG2F 0.69314718055994530942f
-#define HALF_LOG_2PI 0.91893853320467274178f
-
-__device__ __forceinline__ float fmin_nan(float a, float b) { return (a != a) ? a : (a < b ? a : b); }
 
 // Unit-seed backward of a critic (phase A): Gout [R][ldo] holds d(out pre-act)
 // for a seed of 1 per row; writes U_l = d(pre-act of hidden layer l) for every
@@ -2414,18 +2410,14 @@ __global__ void __launch_bounds__(SAC_THREADS) sac_policy_act_kernel(const Engin
     float lp_sum = 0.f, corr_sum = 0.f;
     for (int j = 0; j < A; ++j) {
       if (!eps) {
-        action[(size_t)b * A + j] = tanhf(o[j]) * scale;
+        action[(size_t)b * A + j] = head_act_mean(o[j], scale);
         continue;
       }
       const float mu = o[j], lsr = o[A + j], e = eps[(size_t)b * A + j];
-      const float ls = lsr < lo ? lo : (lsr > hi ? hi : lsr);
-      const float sd = expf(ls);
-      const float z = mu + e * sd;
-      action[(size_t)b * A + j] = tanhf(z) * scale;
-      // (z - mu)^2 / (2 sd^2) = e^2 / 2 and log sd = ls, taken from e and ls themselves: z - mu
-      // loses e * sd to rounding once sd is far below |mu| (at the lower clamp, sd = e^-20, all of it)
-      lp_sum += -0.5f * e * e - ls - HALF_LOG_2PI;
-      corr_sum += 2.f * ((LOG2F - z) - softplus20(-2.f * z));
+      const HeadAct ha = head_act(mu, lsr, e, lo, hi, scale);
+      action[(size_t)b * A + j] = ha.act;
+      lp_sum += head_act_lp(e, ha.ls);
+      corr_sum += head_corr(ha.z);
     }
     if (eps && log_pi) log_pi[b] = lp_sum - corr_sum;
   }

@@ -215,10 +215,10 @@ __device__ __forceinline__ void wide_rowpro(const AS_C EngineDev& E, const AS_C 
         const float t1 = act_fwd(qt1.out_act, a1 + GPC(float, qt1.l[qt1.L - 1].bias)[0]);
         const float t2 = act_fwd(qt2.out_act, a2 + GPC(float, qt2.l[qt2.L - 1].bias)[0]);
         const float qp = aq + GPC(float, q.l[q.L - 1].bias)[0];
-        y = ldh(W.R + lr) + (E.gamma * (1.f - ldh(W.Dn + lr))) * (fmin_nan(t1, t2) - alpha32 * ldh(W.LP2 + lr));
-        const float d = act_fwd(q.out_act, qp) - y;
-        sq = d * d;
-        seed = (2.0f / (float)B) * d;
+        y = td_target(ldh(W.R + lr), ldh(W.Dn + lr), E.gamma, t1, t2, alpha32, ldh(W.LP2 + lr));
+        const CriticSeed cs = critic_seed(act_fwd(q.out_act, qp), y, B);
+        sq = cs.d * cs.d;
+        seed = cs.seed;
         if (q.out_act != ACT_ID) seed = act_bwd(q.out_act, qp, seed);
       }
       Dl[tid * WLDD] = seed;
@@ -267,15 +267,13 @@ __device__ __forceinline__ void wide_rowpro(const AS_C EngineDev& E, const AS_C 
         }
       const float p1 = a1 + GPC(float, q1.l[q1.L - 1].bias)[0], p2 = a2 + GPC(float, q2.l[q2.L - 1].bias)[0];
       const float o1 = act_fwd(q1.out_act, p1), o2 = act_fwd(q2.out_act, p2);
-      const float m = fmin_nan(o1, o2);
-      const float gm = v ? -1.0f / (float)B : 0.f;
-      float g1 = (o1 == o2) ? gm * 0.5f : (o1 > o2 ? 0.f : gm);
-      float g2 = (o1 == o2) ? gm * 0.5f : (o1 < o2 ? 0.f : gm);
+      const MinQ w = minq_weights(o1, o2, v ? -1.0f / (float)B : 0.f);
+      float g1 = w.w1, g2 = w.w2;
       if (q1.out_act != ACT_ID) g1 = act_bwd(q1.out_act, p1, g1);
       if (q2.out_act != ACT_ID) g2 = act_bwd(q2.out_act, p2, g2);
       Dl[tid * WLDD] = jb.qi ? g2 : g1;
       if (cb == 0 && jb.qi == 0) {
-        float term = v ? alpha32 * GPC(float, E.lp_st)[par * E.Br + lr] - m : 0.f;
+        float term = v ? pi_loss_term(alpha32, GPC(float, E.lp_st)[par * E.Br + lr], w.m) : 0.f;
 #pragma unroll
         for (int o = 1; o < 16; o <<= 1) term += __shfl_xor(term, o, 64);
         const int rt = lr >> 4;
