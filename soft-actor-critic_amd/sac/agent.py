@@ -47,6 +47,7 @@ import torch
 import torch.optim as optim
 
 from . import _engine as E
+from .copy_behind import PendingCopies, copy_ring_cells
 from .engine import SacEngine
 from .models import PolicyNetwork, QNetwork
 from .replay_buffer import ReplayBuffer, Transition
@@ -236,7 +237,7 @@ class QValueLog:
         self.dev = torch.empty(self.cap, 2, dtype=torch.float32, device=agent.device)
         self.fill = 0
         self.steps = []
-        self.pending = []
+        self.pending = PendingCopies()
 
     def record(self, states: Any, actions: Any, first_step: int) -> None:
         """Q of rows (states[i], actions[i]) logged at step first_step + i."""
@@ -260,36 +261,53 @@ class QValueLog:
         self.fill += n
         if self.fill >= self.every:
             self._flush()
-        self._drain(block=False)
+        if self.pending:
+            self.pending.consume(False, self._deliver)
 
     def _flush(self) -> None:
         if not self.fill:
             return
-        cuda = self.dev.is_cuda
-        host = torch.empty(self.fill, 2, dtype=torch.float32, pin_memory=cuda)
-        host.copy_(self.dev[:self.fill], non_blocking=cuda)
-        ev = None
-        if cuda:
-            ev = torch.cuda.Event()
-            ev.record()
         # later record() writes to self.dev queue behind this copy on the stream
-        self.pending.append((ev, host, self.steps))
+        self.pending.push(*copy_ring_cells(self.dev, 0, self.fill), self.steps)
         self.steps, self.fill = [], 0
 
-    def _drain(self, block: bool) -> None:
-        while self.pending:
-            ev, host, steps = self.pending[0]
-            if ev is not None:
-                if not block and not ev.query():
-                    return
-                ev.synchronize()
-            for (q1, q2), st in zip(host.tolist(), steps):
-                self.logger.log_q_values(q1, q2, st)
-            self.pending.pop(0)
+    def _deliver(self, host, steps) -> None:
+        for (q1, q2), st in zip(host.tolist(), steps):
+            self.logger.log_q_values(q1, q2, st)
 
     def finish(self) -> None:
         self._flush()
-        self._drain(block=True)
+        self.pending.consume(True, self._deliver)
+
+
+class EpisodeStats:
+    """What a training loop keeps about finished episodes (agent.py:331-336,
+    391-404): ``count`` of them, ``avg`` return over the last 100 (nan before
+    the first) and the ``best`` such average.  ``episode(ret, length)`` is
+    called once per finished episode, in the order the loop sees them end:
+    it appends to the window, updates ``avg`` then ``best``, logs the episode
+    to ``logger`` (None: not logged) under index ``count``, prints the
+    reference's line if ``print_rewards``, and only then counts it."""
+
+    def __init__(self, logger=None, print_rewards: bool = False):
+        self.logger, self.print_rewards = logger, print_rewards
+        self.window = deque(maxlen=100)
+        self.avg, self.best, self.count = float("nan"), -float("inf"), 0
+
+    def episode(self, ret: float, length: int) -> None:
+        self.window.append(ret)
+        self.avg = float(np.mean(self.window))
+        self.best = max(self.best, self.avg)
+        if self.logger is not None:
+            self.logger.log_episode_metrics(episode_idx=self.count, reward=ret, length=length)
+        if self.print_rewards:
+            print(f"Episode {self.count}, Return: {ret:.2f}, Average Return(last 100 episodes): {self.avg:.2f}")
+        self.count += 1
+
+    def counters(self, env_steps: int, gradient_steps: int) -> Dict[str, float]:
+        """The host counters a loop's ``callback`` is given."""
+        return {"env_steps": env_steps, "gradient_steps": gradient_steps, "episodes": self.count,
+                "avg_return": self.avg}
 
 
 class SAC:
@@ -600,23 +618,53 @@ class SAC:
         eng.sync_params()
 
     # ------------------------------------------------------------------ loops
+    def _episode_stats(self, active_logger, print_rewards: bool) -> EpisodeStats:
+        """logger.log_episode_stats: whether finished episodes go to the logger."""
+        log = active_logger is not None and self.config["logger"]["log_episode_stats"]
+        return EpisodeStats(active_logger if log else None, print_rewards)
+
+    def _run_due(self, due: int, loss_log: Optional[LossLog], env_steps: int) -> int:
+        """Run the ``due`` gradient steps of a vector step that ended at env
+        step ``env_steps``, if ``can_update()`` holds, and let the loss log look
+        at them.  Returns the number of gradient steps run (``due`` or 0)."""
+        if not (self.can_update() and due):
+            return 0
+        self._run_updates(due)
+        if loss_log is not None:
+            loss_log.after_updates(env_steps)
+        return due
+
+    def _finish_loop(self, active_logger, stats: EpisodeStats, pending: tuple, **counters) -> Dict[str, float]:
+        """The end of every training loop, in this order: raise if a hand-off
+        timed out (an invalid run is not reported); ``finish`` each of
+        ``pending`` (drains and logs, None skipped), which blocks and may still
+        add episodes to ``stats``; build the metrics, ``counters`` after the
+        episode statistics; ``log_hparams``.  Returns the metrics."""
+        if self.engine is not None:
+            self.engine.check()
+        for log in pending:
+            if log is not None:
+                log.finish()
+        metrics = {"total_episodes": stats.count, "best_avg_return": stats.best, "final_avg_return": stats.avg,
+                   **counters}
+        if active_logger is not None:
+            active_logger.log_hparams(self.config, metrics)
+        return metrics
+
     def run_training_loop(self, num_episodes: int, logger=None, tqdm_disable: bool = False,
                           print_rewards: bool = False) -> Dict[str, float]:
         active_logger = logger or self.logger
-        total_episodes = total_steps = 0
-        returns_window = deque(maxlen=100)
-        best_avg_return = -float("inf")
-        avg_return = float("nan")
+        total_steps = 0
+        stats = self._episode_stats(active_logger, print_rewards)
         tr = self.config["train"]
         update_every = tr.get("update_frequency", 1)
         n_grad = tr.get("gradient_steps_per_update", 1)
         loss_log = self._loss_log(active_logger)
         q_log = self._q_log(active_logger)
-        for episode in _tqdm(range(num_episodes), disable=tqdm_disable):
+        for _ in _tqdm(range(num_episodes), disable=tqdm_disable):
             state, _ = self.env.reset()
             done = False
             episode_return = 0.0
-            total_episodes += 1
             episode_steps = 0
             while not done:
                 action = self.select_action(state)
@@ -633,24 +681,8 @@ class SAC:
                         loss_log.after_updates(total_steps)
                 if q_log is not None:  # Q(s', a) of this env step (agent.py:370-376), no host sync
                     q_log.record(state, action, total_steps)
-            returns_window.append(episode_return)
-            avg_return = float(np.mean(returns_window))
-            best_avg_return = max(best_avg_return, avg_return)
-            if active_logger is not None and self.config["logger"]["log_episode_stats"]:
-                active_logger.log_episode_metrics(episode_idx=episode, reward=episode_return, length=episode_steps)
-            if print_rewards:
-                print(f"Episode {episode}, Return: {episode_return:.2f}, "
-                      f"Average Return(last 100 episodes): {avg_return:.2f}")
-        if self.engine is not None:
-            self.engine.check()
-        if loss_log is not None:
-            loss_log.finish()
-        if q_log is not None:
-            q_log.finish()
-        metrics = {"total_episodes": total_episodes, "best_avg_return": best_avg_return,
-                   "final_avg_return": avg_return}
-        if active_logger is not None:
-            active_logger.log_hparams(self.config, metrics)
+            stats.episode(episode_return, episode_steps)
+        metrics = self._finish_loop(active_logger, stats, (loss_log, q_log))
         if self.config["logger"]["save_model"]["enabled"]:
             save_path = self.config["logger"]["save_model"]["path"]
             if save_path is None:
@@ -703,11 +735,8 @@ class SAC:
         obs, _ = env.reset(seed=seed)
         ep_ret = np.zeros(N, np.float64)
         ep_len = np.zeros(N, np.int64)
-        returns_window = deque(maxlen=100)
-        best_avg_return = -float("inf")
-        avg_return = float("nan")
-        total_steps = total_episodes = grad_steps = 0
-        log_episodes = active_logger is not None and self.config["logger"]["log_episode_stats"]
+        stats = self._episode_stats(active_logger, print_rewards)
+        total_steps = grad_steps = 0
         loss_log = self._loss_log(active_logger)
         q_log = self._q_log(active_logger)
         pbar = _tqdm(range((int(total_env_steps) + N - 1) // N), disable=tqdm_disable)
@@ -719,45 +748,22 @@ class SAC:
             self.store_transitions(obs, actions, rewards, info["final_obs"], dones)
             old = total_steps
             total_steps += N
-            due = due_updates_gated(old, total_steps, len_before, self.replay_buffer.capacity,
-                                    tr["warming_steps"], update_every, n_grad)
-            if self.can_update() and due:
-                self._run_updates(due)
-                grad_steps += due
-                if loss_log is not None:
-                    loss_log.after_updates(total_steps)
+            grad_steps += self._run_due(due_updates_gated(old, total_steps, len_before, self.replay_buffer.capacity,
+                                                          tr["warming_steps"], update_every, n_grad),
+                                        loss_log, total_steps)
             if q_log is not None:  # env step old + 1 + i logs Q(s'_i, a_i) under the critics after this vector step
                 q_log.record(info["final_obs"], actions, old + 1)
             ep_ret += rewards
             ep_len += 1
             for i in np.nonzero(dones)[0]:
-                returns_window.append(float(ep_ret[i]))
-                avg_return = float(np.mean(returns_window))
-                best_avg_return = max(best_avg_return, avg_return)
-                if log_episodes:
-                    active_logger.log_episode_metrics(episode_idx=total_episodes, reward=float(ep_ret[i]),
-                                                      length=int(ep_len[i]))
-                if print_rewards:
-                    print(f"Episode {total_episodes}, Return: {ep_ret[i]:.2f}, "
-                          f"Average Return(last 100 episodes): {avg_return:.2f}")
-                total_episodes += 1
+                stats.episode(float(ep_ret[i]), int(ep_len[i]))
                 ep_ret[i] = 0.0
                 ep_len[i] = 0
             obs = next_obs
             if callback is not None:
-                callback({"env_steps": total_steps, "gradient_steps": grad_steps, "episodes": total_episodes,
-                          "avg_return": avg_return})
-        if self.engine is not None:
-            self.engine.check()  # a timed-out hand-off invalidates the run: raise, do not report it
-        if loss_log is not None:
-            loss_log.finish()
-        if q_log is not None:
-            q_log.finish()
-        metrics = {"total_episodes": total_episodes, "best_avg_return": best_avg_return,
-                   "final_avg_return": avg_return, "total_env_steps": total_steps, "gradient_steps": grad_steps}
-        if active_logger is not None:
-            active_logger.log_hparams(self.config, metrics)
-        return metrics
+                callback(stats.counters(total_steps, grad_steps))
+        return self._finish_loop(active_logger, stats, (loss_log, q_log), total_env_steps=total_steps,
+                                 gradient_steps=grad_steps)
 
     def _device_env(self, vec_env: Any, what: str):
         from .device_envs import DeviceVectorEnv
@@ -785,8 +791,8 @@ class SAC:
         Episode returns and lengths are accumulated on the device and written
         to the envs' episode ring; every ``drain_every`` vector steps the new
         cells are copied to pinned memory behind the launches and consumed once
-        the copy has landed (``sac.device_envs.EpisodeDrain``, the ``QValueLog``
-        pattern), and after the last step the rest is consumed blocking.  So
+        the copy has landed (``sac.device_envs.EpisodeDrain``, on the copies
+        of ``sac.copy_behind``), and after the last step the rest is consumed blocking.  So
         the returned metrics and the logged episodes are exact and in the
         order the host loop sees them, (vector step, env row); but the
         ``episodes`` and ``avg_return`` a ``callback`` sees inside the loop may
@@ -857,50 +863,46 @@ class SAC:
         n_grad = tr.get("gradient_steps_per_update", 1)
         N = env.num_envs
         env.reset(seed=seed)
-        returns_window = deque(maxlen=100)
-        st = {"episodes": 0, "best": -float("inf"), "avg": float("nan")}
+        stats = self._episode_stats(active_logger, print_rewards)
         total_steps = grad_steps = 0
-        log_episodes = active_logger is not None and self.config["logger"]["log_episode_stats"]
         loss_log = self._loss_log(active_logger)
-
-        def on_episode(ret: float, length: int) -> None:
-            returns_window.append(ret)
-            st["avg"] = float(np.mean(returns_window))
-            st["best"] = max(st["best"], st["avg"])
-            if log_episodes:
-                active_logger.log_episode_metrics(episode_idx=st["episodes"], reward=ret, length=length)
-            if print_rewards:
-                print(f"Episode {st['episodes']}, Return: {ret:.2f}, "
-                      f"Average Return(last 100 episodes): {st['avg']:.2f}")
-            st["episodes"] += 1
-
-        drain = EpisodeDrain(env, on_episode, drain_every)
+        drain = EpisodeDrain(env, stats.episode, drain_every)
         q_log = None
         if device_q_values and active_logger is not None and self.config["logger"]["log_q_values"]:
             # with the graph, cell = RNG step % S on both paths: the graph's kernel indexes its cell that way
             q_log = DeviceQValueLog(eng, self.replay_buffer, N, active_logger, drain_every,
                                     first_cell=env.t + 1 if K else 0)
         vec_steps = (int(total_env_steps) + N - 1) // N
+        rb, cap, warming = self.replay_buffer, self.replay_buffer.capacity, tr["warming_steps"]
+
+        def step(due: int) -> None:
+            """One vector step issued from the host, with ``due`` gradient steps after it."""
+            nonlocal total_steps, grad_steps
+            if q_log is not None:
+                rb.flush()  # rows pushed from the host go in first: they move the write slot
+            first_slot = rb._pos  # the step's N rows go to ring slots first_slot + i
+            eng.rollout_step(env, rb)
+            total_steps += N
+            grad_steps += self._run_due(due, loss_log, total_steps)
+            if q_log is not None:  # env step first + i logs Q(s'_i, a_i) under the critics after this vector step
+                q_log.after_step(first_slot, total_steps - N + 1)
 
         def report() -> None:
             drain.after_step()
             if callback is not None:
-                callback({"env_steps": total_steps, "gradient_steps": grad_steps, "episodes": st["episodes"],
-                          "avg_return": st["avg"]})
+                callback(stats.counters(total_steps, grad_steps))
 
         if K:
             cursor, policy, seeded, done = eng.loop_cursor(), GraphBlockPolicy(), False, 0
-            batch, cap = tr["batch_size"], self.replay_buffer.capacity
+            batch = tr["batch_size"]
             while done < vec_steps:
-                counts = plan_graph_block(total_steps, len(self.replay_buffer), cap, tr["warming_steps"],
-                                          update_every, n_grad, N, K)
-                if vec_steps - done >= K and graph_block_ready(counts, len(self.replay_buffer), cap,
-                                                               tr["warming_steps"], batch, N) \
+                counts = plan_graph_block(total_steps, len(rb), cap, warming, update_every, n_grad, N, K)
+                if vec_steps - done >= K and graph_block_ready(counts, len(rb), cap, warming, batch, N) \
                         and policy.admit(counts):
                     if not seeded:  # the last block moved the host mirrors only
-                        eng.seed_cursor(cursor, env, self.replay_buffer)
+                        eng.seed_cursor(cursor, env, rb)
                         seeded = True
-                    eng.loop_graph(env, self.replay_buffer, cursor, counts, 1, None if q_log is None else q_log.ring)
+                    eng.loop_graph(env, rb, cursor, counts, 1, None if q_log is None else q_log.ring)
                     if q_log is not None:
                         q_log.after_graph(K, total_steps + 1)
                     total_steps += K * N
@@ -910,55 +912,16 @@ class SAC:
                     done += K
                 else:
                     seeded = False
-                    for due in counts[:min(K, vec_steps - done)]:
-                        if q_log is not None:
-                            self.replay_buffer.flush()
-                        first_slot = self.replay_buffer._pos
-                        eng.rollout_step(env, self.replay_buffer)
-                        old = total_steps
-                        total_steps += N
-                        if self.can_update() and due:
-                            self._run_updates(due)
-                            grad_steps += due
-                            if loss_log is not None:
-                                loss_log.after_updates(total_steps)
-                        if q_log is not None:
-                            q_log.after_step(first_slot, old + 1)
+                    for due in counts[:vec_steps - done]:
+                        step(due)
                         done += 1
                 report()
-            vec_steps = 0  # all taken
-        for _ in range(vec_steps):
-            len_before = len(self.replay_buffer)
-            if q_log is not None:
-                self.replay_buffer.flush()  # rows pushed from the host go in first: they move the write slot
-            first_slot = self.replay_buffer._pos  # the step's N rows go to ring slots first_slot + i
-            eng.rollout_step(env, self.replay_buffer)
-            old = total_steps
-            total_steps += N
-            due = due_updates_gated(old, total_steps, len_before, self.replay_buffer.capacity,
-                                    tr["warming_steps"], update_every, n_grad)
-            if self.can_update() and due:
-                self._run_updates(due)
-                grad_steps += due
-                if loss_log is not None:
-                    loss_log.after_updates(total_steps)
-            if q_log is not None:  # env step old + 1 + i logs Q(s'_i, a_i) under the critics after this vector step
-                q_log.after_step(first_slot, old + 1)
-            drain.after_step()
-            if callback is not None:
-                callback({"env_steps": total_steps, "gradient_steps": grad_steps, "episodes": st["episodes"],
-                          "avg_return": st["avg"]})
-        eng.check()  # a timed-out hand-off invalidates the run: raise, do not report it
-        drain.finish()
-        if loss_log is not None:
-            loss_log.finish()
-        if q_log is not None:
-            q_log.finish()
-        metrics = {"total_episodes": st["episodes"], "best_avg_return": st["best"],
-                   "final_avg_return": st["avg"], "total_env_steps": total_steps, "gradient_steps": grad_steps}
-        if active_logger is not None:
-            active_logger.log_hparams(self.config, metrics)
-        return metrics
+        else:
+            for _ in range(vec_steps):
+                step(due_updates_gated(total_steps, total_steps + N, len(rb), cap, warming, update_every, n_grad))
+                report()
+        return self._finish_loop(active_logger, stats, (drain, loss_log, q_log), total_env_steps=total_steps,
+                                 gradient_steps=grad_steps)
 
     def evaluate_device(self, num_episodes: Optional[int] = None, vec_env: Any = None,
                         episodes_per_env: Optional[int] = None) -> float:
@@ -977,39 +940,33 @@ class SAC:
         if (num_episodes is None) == (episodes_per_env is None):
             raise ValueError("evaluate_device takes exactly one of num_episodes and episodes_per_env")
         env = self._device_env(vec_env, "evaluate_device")
-        if episodes_per_env is not None:
+        per_row = episodes_per_env is not None
+        if per_row:
             k = int(episodes_per_env)
             if k < 1:
                 raise ValueError("episodes_per_env must be >= 1")
-            eng = self._engine()
-            env.reset()
-            episodes: list = []
-            ended = [0] * env.num_envs
-
-            def at(t, row, ret, length):
-                episodes.append((t, row, ret))
-                ended[row] += 1
-
-            drain = EpisodeDrain(env, None, env.ring_steps, on_episode_at=at)
-            chunk = max(1, min(env.ring_steps, env.max_steps))
-            while min(ended) < k:  # every row ends an episode at least once per max_steps vector steps
-                for _ in range(chunk):
-                    eng.rollout_step(env, self.replay_buffer, deterministic=True, store=False)
-                drain.finish()
-            return float(np.mean(first_episodes_per_row(episodes, env.num_envs, k)))
-        if num_episodes < 1:
+        elif num_episodes < 1:
             raise ValueError("num_episodes must be >= 1")
         eng = self._engine()
         env.reset()
-        returns: list = []
-        drain = EpisodeDrain(env, lambda ret, length: returns.append(ret), env.ring_steps)
-        # every env ends an episode at least once per max_steps vector steps
-        chunk = max(1, min(env.ring_steps, env.max_steps * ((num_episodes + env.num_envs - 1) // env.num_envs)))
-        while len(returns) < num_episodes:
+        episodes: list = []  # (vector step, env row, return) in the order they ended
+        ended = [0] * env.num_envs
+
+        def at(t, row, ret, length):
+            episodes.append((t, row, ret))
+            ended[row] += 1
+
+        drain = EpisodeDrain(env, None, env.ring_steps, on_episode_at=at)
+        # every row ends an episode at least once per max_steps vector steps
+        rounds = 1 if per_row else (num_episodes + env.num_envs - 1) // env.num_envs
+        chunk = max(1, min(env.ring_steps, env.max_steps * rounds))
+        while (min(ended) < k) if per_row else (len(episodes) < num_episodes):
             for _ in range(chunk):
                 eng.rollout_step(env, self.replay_buffer, deterministic=True, store=False)
             drain.finish()
-        return float(np.mean(returns[:num_episodes]))
+        if per_row:
+            return float(np.mean(first_episodes_per_row(episodes, env.num_envs, k)))
+        return float(np.mean([ret for _, _, ret in episodes[:num_episodes]]))
 
     def eval_agent(self, num_episodes: int, render_mode: Optional[str] = None, tqdm_disable: bool = False,
                    print_returns: bool = False, writer=None) -> float:

@@ -53,6 +53,7 @@ import torch
 from . import _engine as E
 from . import control_envs
 from . import envs as host_envs
+from .copy_behind import PendingCopies, copy_ring_cells
 
 # kind name -> (sac_env_kind, host class); the names of sac/train_replicas.py
 KINDS = {
@@ -203,18 +204,7 @@ class DeviceVectorEnv:
         n = t_last - t_first + 1
         if n < 1 or n > self.ring_steps:
             raise ValueError(f"episode_cells: {n} steps do not fit the ring of {self.ring_steps}")
-        host = torch.empty(n, self.num_envs, 2, dtype=torch.float64, pin_memory=True)
-        a, b = t_first % self.ring_steps, t_last % self.ring_steps
-        with torch.cuda.device(self.device):
-            if a <= b:
-                host.copy_(self.ring[a:b + 1], non_blocking=True)
-            else:  # the range wraps the ring
-                k = self.ring_steps - a
-                host[:k].copy_(self.ring[a:], non_blocking=True)
-                host[k:].copy_(self.ring[:b + 1], non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record()
-        return host, ev
+        return copy_ring_cells(self.ring, t_first, n)
 
     @staticmethod
     def decode_cells(host) -> Tuple[List[float], List[int]]:
@@ -255,7 +245,7 @@ def first_episodes_per_row(episodes, num_envs: int, k: int) -> List[float]:
 
 class EpisodeDrain:
     """Finished episodes of a ``DeviceVectorEnv`` in ``(t, i)`` order without
-    per-step host traffic (the ``QValueLog`` pattern of sac/agent.py): every
+    per-step host traffic (the copies of ``sac.copy_behind``): every
     ``every`` vector steps ``after_step`` queues one pinned copy of the new ring
     cells behind the launches and hands finished copies to ``on_episode(ret,
     length)``; ``finish`` waits for the rest.  ``on_episode_at(t, row, ret,
@@ -266,38 +256,33 @@ class EpisodeDrain:
         self.envs, self.on_episode, self.on_episode_at = envs, on_episode, on_episode_at
         self.every = max(1, min(int(every), envs.ring_steps))
         self.copied_to = envs.t  # last RNG step whose cells were queued
-        self.pending: List[tuple] = []
+        self.pending = PendingCopies()
 
     def _queue(self) -> None:
         t = self.envs.t
         if t > self.copied_to:
-            self.pending.append(self.envs.episode_cells(self.copied_to + 1, t) + (self.copied_to + 1,))
+            self.pending.push(*self.envs.episode_cells(self.copied_to + 1, t), self.copied_to + 1)
             self.copied_to = t
 
-    def _consume(self, block: bool) -> None:
-        while self.pending:
-            host, ev, t_first = self.pending[0]
-            if not block and not ev.query():
-                return
-            ev.synchronize()
-            rets, lengths = DeviceVectorEnv.decode_cells(host)
-            if self.on_episode is not None:
-                for ret, length in zip(rets, lengths):
-                    self.on_episode(ret, length)
-            if self.on_episode_at is not None:
-                for dt, row, ret, length in zip(*DeviceVectorEnv.decode_cell_positions(host), rets, lengths):
-                    self.on_episode_at(t_first + dt, row, ret, length)
-            self.pending.pop(0)
+    def _deliver(self, host, t_first: int) -> None:
+        rets, lengths = DeviceVectorEnv.decode_cells(host)
+        if self.on_episode is not None:
+            for ret, length in zip(rets, lengths):
+                self.on_episode(ret, length)
+        if self.on_episode_at is not None:
+            for dt, row, ret, length in zip(*DeviceVectorEnv.decode_cell_positions(host), rets, lengths):
+                self.on_episode_at(t_first + dt, row, ret, length)
 
     def after_step(self) -> None:
         if self.envs.t - self.copied_to >= self.every:
             self._queue()
-        self._consume(block=False)
+        if self.pending:
+            self.pending.consume(False, self._deliver)
 
     def finish(self) -> None:
         """Blocking: every episode that ended up to now."""
         self._queue()
-        self._consume(block=True)
+        self.pending.consume(True, self._deliver)
 
 
 class DeviceQValueLog:
@@ -337,7 +322,7 @@ class DeviceQValueLog:
         self.t = 0          # cells written
         self.copied_to = 0  # cells queued for copy
         self.first_steps: List[int] = []  # first env step of the cells not yet queued
-        self.pending: List[tuple] = []
+        self.pending = PendingCopies()
 
     def after_step(self, first_slot: int, first_step: int) -> None:
         """The rollout step wrote its N rows at ring slots ``first_slot + i``
@@ -346,9 +331,7 @@ class DeviceQValueLog:
                                     out=self.ring[(self.first_cell + self.t) % self.ring_steps])
         self.t += 1
         self.first_steps.append(int(first_step))
-        if self.t - self.copied_to >= self.every:
-            self._queue()
-        self._consume(block=False)
+        self._poll()
 
     def after_graph(self, k_steps: int, first_step: int) -> None:
         """A loop graph just queued ``k_steps`` vector steps that write the
@@ -357,46 +340,32 @@ class DeviceQValueLog:
         for j in range(int(k_steps)):
             self.first_steps.append(int(first_step) + j * self.num_envs)
         self.t += int(k_steps)
+        self._poll()
+
+    def _poll(self) -> None:
         if self.t - self.copied_to >= self.every:
             self._queue()
-        self._consume(block=False)
+        if self.pending:
+            self.pending.consume(False, self._deliver)
 
     def _queue(self) -> None:
         n = self.t - self.copied_to
         if n < 1:
             return
-        S = self.ring_steps
-        host = torch.empty(n, self.num_envs, 2, dtype=torch.float32, pin_memory=True)
-        a, b = (self.first_cell + self.copied_to) % S, (self.first_cell + self.t - 1) % S
-        with torch.cuda.device(self.engine.device):
-            if a <= b:
-                host.copy_(self.ring[a:b + 1], non_blocking=True)
-            else:  # the range wraps the ring
-                k = S - a
-                host[:k].copy_(self.ring[a:], non_blocking=True)
-                host[k:].copy_(self.ring[:b + 1], non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record()
         # later launches into these cells queue behind this copy on the stream
-        self.pending.append((host, ev, self.first_steps))
+        self.pending.push(*copy_ring_cells(self.ring, self.first_cell + self.copied_to, n), self.first_steps)
         self.first_steps = []
         self.copied_to = self.t
 
-    def _consume(self, block: bool) -> None:
-        while self.pending:
-            host, ev, firsts = self.pending[0]
-            if not block and not ev.query():
-                return
-            ev.synchronize()
-            for cell, first in zip(host.tolist(), firsts):
-                for i, (q1, q2) in enumerate(cell):
-                    self.logger.log_q_values(q1, q2, first + i)
-            self.pending.pop(0)
+    def _deliver(self, host, firsts: List[int]) -> None:
+        for cell, first in zip(host.tolist(), firsts):
+            for i, (q1, q2) in enumerate(cell):
+                self.logger.log_q_values(q1, q2, first + i)
 
     def finish(self) -> None:
         """Blocking: every value recorded up to now."""
         self._queue()
-        self._consume(block=True)
+        self.pending.consume(True, self._deliver)
 
 
 __all__ = ["DeviceVectorEnv", "DeviceQValueLog", "EpisodeDrain", "KINDS", "first_episodes_per_row", "kind_name"]
