@@ -475,6 +475,33 @@ __device__ __forceinline__ V keep_v(V x) {
   return x;
 }
 
+// store_T's element values from a gemm_hf / epi0 epilogue's registers (fp32):
+// a[i] is the lane's value of row 4 g + i (g = lane >> 4) of column col (every
+// lane of the wave is in the epilogue), and the stash is [k][Bp],
+// batch-contiguous, so the lane's four rows are the 16 bytes at dst + col Bp +
+// col0 + 4 g: no LDS re-read and no barrier in front of the store.  The four
+// lanes that hold one k-row's 64 B are 16 lanes apart, though, and each would
+// go out as a 16-B write of its own, as store_T's do; the lanes exchange rows
+// first (one cross-lane move per row) so that four ADJACENT lanes hold the 64 B:
+// one wave instruction is 16 k-rows x one 64-B write.  The writes' size is what
+// measured (profiles/ab_stash_from_registers_items.txt), not the LDS pass.
+// Masked as store_T masks: a row >= nvalid or a column that holds no data
+// (!kvalid) is written as +0.f, not skipped (the dW reductions sum every padded
+// column).  A plain store, and no wait: nothing in the launch reads a stash.
+__device__ __forceinline__ void store_acc_T(void* dst_, int Bp, int col0, int col, const float (&a)[4], int nvalid,
+                                            bool kvalid) {
+  const int lane = threadIdx.x & 63;
+  const int rb = (lane >> 4) << 2;
+  u32x4 v;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) v[i] = __float_as_uint((kvalid && rb + i < nvalid) ? a[i] : 0.f);
+  // lane d takes the four rows of lane (d >> 2) + 16 (d & 3): k-row (d >> 2)'s 64 B lie in 4 adjacent lanes
+  const int src = ((lane >> 2) + ((lane & 3) << 4)) << 2;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) v[i] = (unsigned)__builtin_amdgcn_ds_bpermute(src, (int)v[i]);
+  *(AS_G u32x4*)(GP(float, dst_) + (size_t)(col - (lane & 15) + (lane >> 2)) * Bp + col0 + ((lane & 3) << 2)) = v;
+}
+
 // ---------------------------------------------------------------------------- phase A
 template <typename T>
 __device__ __forceinline__ void target_critic_split_body(const EngineDev* __restrict__ Ep, const sac_replay& rb,
@@ -637,6 +664,22 @@ __device__ __forceinline__ void target_critic_split_body(const EngineDev* __rest
   }
   x_direct = x_direct && staged;  // a stale record: the gather and build_x below overwrite Xb
   if (!h1_issued) ht_issue<T, 1, NCH_H, false, true>(h1, w1);
+  // fp32 with a ReLU / identity hidden activation (uniform): the stashes leave from registers
+  const bool ind_early = sizeof(T) == 4 && (net.hid_act == ACT_RELU || net.hid_act == ACT_ID);
+  if constexpr (sizeof(T) == 4) {
+    // The critics' layer-2 unit-seed dY^T is the valid-row indicator (row 0: 1
+    // for a valid batch row; the padded rows: 0).  It depends on nvalid alone,
+    // so half 0 writes it here, behind the record's and the weights' loads,
+    // instead of through LDS at the end of the role (store_T's values).
+    if ((role == 3 || role == 4) && h == 0 && ind_early)
+      for (int i = tid; i < L2.Np * (R / 4); i += SAC_THREADS) {
+        const int k = i / (R / 4), rb = (i % (R / 4)) * 4;
+        u32x4 v;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) v[q] = __float_as_uint((k == 0 && k < L2.N && rb + q < nvalid) ? 1.f : 0.f);
+        *(AS_G u32x4*)(GP(float, L2.GT) + (size_t)k * Bp + r0 + rb) = v;
+      }
+  }
   // layer 2's k-split slice (layer 2 runs after the hand-off for the target
   // critics, and at the end of pi(s')'s chain): held from here
   GemmW w2n = gw_sub<T>(L2.Wc, L2.Kp, 0, L2.Np, h * HHr, HHr, nullptr, 0);
@@ -758,22 +801,38 @@ __device__ __forceinline__ void target_critic_split_body(const EngineDev* __rest
   // written by layer 1's epilogue (w2l: W2's element of the lane's column).
   int l2_pub = 0;
   bool l2_keep = false;
+  // uniform: the transposed stashes are stored from the GEMM epilogues' registers
+  // (store_acc_T): reg_st the ones the next GEMM reads from LDS as well, reg_fin a role's last
+  const bool reg_st = ind_early, reg_fin = ind_early;
   AS_G uint64_t* l2_g = nullptr;
   bool mk_u1 = false;
   float w2l = 0.f;
   auto forward01 = [&](bool keepP, bool stXT, bool pi_actor, auto&& after_l1, bool l0_done = false) {
     // layer 0: X [R][Kp0] -> P0 / H0 [R][H] (l0_done: the caller computed H0)
     const int act = net.hid_act;
+    // the X^T stashes of layers 1 and 2 (and the critics' U1^T) from the
+    // epilogues' registers (store_acc_T; uniform): fp32 with a ReLU / identity
+    // hidden activation.  Otherwise (an activation pass rewrites H0 / H1
+    // behind the epilogue; bf16) store_T reads them back from LDS.
+    const bool st_reg = reg_st && stXT;
+    const bool st_reg0 = st_reg && h == 0 && !l0_done;
+    void* const xt1 = (T*)L1.XT + (pi_actor ? par * L1.xt_par : 0);
+    void* const xt2 = (T*)L2.XT + (pi_actor ? par * L2.xt_par : 0) + (size_t)h * HH * Bp;
+    void* const gt1 = (T*)L1.GT + (size_t)h * HH * Bp;
     auto epi0 = [&](int j, int col, const f32x4& acc) {
       const bool nv = col < L0.N;
       const float bn = h0.b[j];
+      float hv[4];
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int r = (((threadIdx.x & 63) >> 4) << 2) + i;
         const float p = nv ? acc[i] + bn : 0.f;
         if (keepP) P0[r * ldp0 + col] = p;
-        H0[r * ld + col] = act == ACT_RELU ? (p > 0.f ? p : 0.f) : p;
+        hv[i] = act == ACT_RELU ? (p > 0.f ? p : 0.f) : p;
+        H0[r * ld + col] = hv[i];
       }
+      if constexpr (sizeof(T) == 4)
+        if (st_reg0) store_acc_T(xt1, Bp, r0, col, hv, nvalid, col < L1.K);
     };
     if (!l0_done) {
       // Kp0 = 32 / 64 (uniform): every chunk held, the fixed-shape step; wider: held chunks, then the stream
@@ -792,23 +851,30 @@ __device__ __forceinline__ void target_critic_split_body(const EngineDev* __rest
       float* ps = L0.pstash + (size_t)r0 * L0.Np;
       for (int i = tid; i < R * L0.Np; i += SAC_THREADS) st_f<false>(ps + i, P0[(i / L0.Np) * ldp0 + i % L0.Np]);
     }
-    if (stXT && h == 0)
-      store_T<T, R>(H0, ld, L1.Kp, L1.K, (T*)L1.XT + (pi_actor ? par * L1.xt_par : 0), Bp, r0, nvalid, nullptr);
+    if (stXT && h == 0 && !st_reg0) store_T<T, R>(H0, ld, L1.Kp, L1.K, xt1, Bp, r0, nvalid, nullptr);
     STAMP(2);
     if (sizeof(T) == 4 && !kh2.ok) ks_issue<T, KsHeld<T>::MAXC, false>(kh2, w2n);  // fp32: under layer 1 (target critics: before the poll)
     // layer 1, this half: H0 -> P1 / H1 [R][HH]
     gemm_hf<T, 1, NCH_H, 0>(H0, ld, w1.NT, h1, [&](int j, int col, const f32x4& acc) {
       const float bn = h1.b[j];
+      float hv[4], uv[4];
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int r = (((threadIdx.x & 63) >> 4) << 2) + i;
         const float p = acc[i] + bn;
+        uv[i] = act == ACT_RELU ? (p > 0.f ? w2l : 0.f) : w2l;
         if (mk_u1)
-          U1[r * ldu1 + col] = act == ACT_RELU ? (p > 0.f ? w2l : 0.f) : w2l;
+          U1[r * ldu1 + col] = uv[i];
         else if (keepP)
           P1[r * ldp1 + col] = p;
-        H1[r * ldh1 + col] = act == ACT_RELU ? (p > 0.f ? p : 0.f) : p;
+        hv[i] = act == ACT_RELU ? (p > 0.f ? p : 0.f) : p;
+        H1[r * ldh1 + col] = hv[i];
       }
+      if constexpr (sizeof(T) == 4)
+        if (st_reg) {  // this half's rows of layer 2's X^T, and the critics' unit seed U1^T (layer 1's dY^T)
+          store_acc_T(xt2, Bp, r0, col, hv, nvalid, true);
+          if (mk_u1) store_acc_T(gt1, Bp, r0, col, uv, nvalid, true);
+        }
     });
     after_l1();  // layer 1's held weights are dead from here
     if (act != ACT_RELU && act != ACT_ID) act_pass_fwd<R>(H1, ldh1, HHr >> 4, act);
@@ -817,9 +883,8 @@ __device__ __forceinline__ void target_critic_split_body(const EngineDev* __rest
       float* ps = L1.pstash + (size_t)r0 * L1.Np + h * HH;
       for (int i = tid; i < R * HH; i += SAC_THREADS) st_f<false>(ps + (i / HH) * L1.Np + i % HH, P1[(i / HH) * ldp1 + i % HH]);
     }
-    if (stXT)  // layer 2's input, this half's rows of X^T
-      store_T<T, R>(H1, ldh1, HH, HH, (T*)L2.XT + (pi_actor ? par * L2.xt_par : 0) + (size_t)h * HH * Bp, Bp, r0,
-                       nvalid, nullptr);
+    if (stXT && !st_reg)  // layer 2's input, this half's rows of X^T
+      store_T<T, R>(H1, ldh1, HH, HH, xt2, Bp, r0, nvalid, nullptr);
     STAMP(3);
     // layer 2, this half's partial sum: outB [R][Np2]
     auto epi2 = [&](int r, int col, float s) {
@@ -1039,17 +1104,24 @@ __device__ __forceinline__ void target_critic_split_body(const EngineDev* __rest
       gemm_hf<T, 2, NCH_HH, NT_H>(U1, ldu1, 0, ht1, relu ? P0 : nullptr, ldp0,
                                   [&](int j, int col, const f32x4& acc, const float (&p)[4]) {
         const bool kv = col < L1.K;
+        float uv[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const int r = (((threadIdx.x & 63) >> 4) << 2) + i;
           float v = kv ? acc[i] : 0.f;
           if (relu && !(p[i] > 0.f)) v = 0.f;
-          Xb[r * ld + col] = v;  // U0 partial
+          uv[i] = v;
+          if (!reg_fin) Xb[r * ld + col] = v;  // U0 partial
         }
+        // the role's last stash: nothing reads it from LDS, so it goes out from here
+        if constexpr (sizeof(T) == 4)
+          if (reg_fin) store_acc_T(L0.GT, 2 * Bp, h * Bp + r0, col, uv, nvalid, col < L0.N);
       });
-      if (net.hid_act != ACT_RELU && net.hid_act != ACT_ID)
-        act_pass_bwd<R>(Xb, ld, P0, ldp0, L1.Kp >> 4, L1.K, net.hid_act);
-      __syncthreads();
+      if (!reg_fin) {  // uniform
+        if (net.hid_act != ACT_RELU && net.hid_act != ACT_ID)
+          act_pass_bwd<R>(Xb, ld, P0, ldp0, L1.Kp >> 4, L1.K, net.hid_act);
+        __syncthreads();
+      }
     }
     STAMP(16);
     // the role does not wait for y.  It stores every layer's UNIT-seed dY^T
@@ -1059,9 +1131,12 @@ __device__ __forceinline__ void target_critic_split_body(const EngineDev* __rest
     // here and the scaled value once more in phase B, within the bf16 mode's
     // tolerances; round 5, VERDICT r04 item 2a -- before, the bf16 critics
     // waited for y and stored seed-scaled rows.)
-    store_T<T, R>(U1, ldu1, HH, HH, (T*)L1.GT + (size_t)h * HH * Bp, Bp, r0, nvalid, nullptr);
-    store_T<T, R>(Xb, ld, L0.Np, L0.N, L0.GT, 2 * Bp, h * Bp + r0, nvalid, nullptr);
-    if (h == 0) {
+    // In fp32 with a ReLU / identity hidden activation all three are out by
+    // now: layer 1's from its forward epilogue, layer 0's from the dX epilogue
+    // above, layer 2's at role entry.
+    if (!(reg_st && mk_u1)) store_T<T, R>(U1, ldu1, HH, HH, (T*)L1.GT + (size_t)h * HH * Bp, Bp, r0, nvalid, nullptr);
+    if (!reg_fin) store_T<T, R>(Xb, ld, L0.Np, L0.N, L0.GT, 2 * Bp, h * Bp + r0, nvalid, nullptr);
+    if (h == 0 && !ind_early) {
       lf* g2 = outB;  // this half's q partial went out as a granule above
       for (int i = tid; i < R * 32; i += SAC_THREADS) g2[(i / 32) * ldo + i % 32] = (i % 32) == 0 ? 1.f : 0.f;
       __syncthreads();
@@ -1551,14 +1626,22 @@ __device__ __forceinline__ void actor_split_body(const EngineDev* __restrict__ E
   // dY1 (this half) = act'(P1) * (dOut W2[:, half])
   const int act = pi.hid_act;
   const bool relu = act == ACT_RELU;  // the masks P1 / P0 go to registers ahead of each dX chain (gemm_hf)
+  // dY1^T and dY0^T from the epilogues' registers (store_acc_T; uniform): fp32, a ReLU /
+  // identity hidden activation (no act_pass_bwd behind the epilogue) and no bias partials
+  const bool reg1 = sizeof(T) == 4 && (relu || act == ACT_ID) && !dbp1;
+  const bool reg0 = sizeof(T) == 4 && (relu || act == ACT_ID) && !dbp0;
   auto epi2 = [&](int j, int col, const f32x4& acc, const float (&p)[4]) {
+    float dv[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int r = (((threadIdx.x & 63) >> 4) << 2) + i;
       float v = acc[i];
       if (relu && !(p[i] > 0.f)) v = 0.f;
+      dv[i] = v;
       U1[r * ldu1 + col] = v;
     }
+    if constexpr (sizeof(T) == 4)
+      if (reg1) store_acc_T(gt1, Bp, r0, col, dv, nvalid, true);
   };
   if (NCH_32 == 1 || np2 == KC)  // uniform: the chunks of dOut that hold data, one or (fp32, 2A > 16) two
     gemm_hf<T, 1, 1, HH / 16>(goutB, ldo, 0, ht2, relu ? P1 : nullptr, ldp1, epi2);
@@ -1566,18 +1649,26 @@ __device__ __forceinline__ void actor_split_body(const EngineDev* __restrict__ E
     gemm_hf<T, 1, NCH_32, HH / 16>(goutB, ldo, 0, ht2, relu ? P1 : nullptr, ldp1, epi2);
   if (act != ACT_RELU && act != ACT_ID) act_pass_bwd<R>(U1, ldu1, P1, ldp1, HH >> 4, HH, act);
   __syncthreads();
-  store_T<T, R>(U1, ldu1, HH, HH, gt1, Bp, r0, nvalid, dbp1, nullptr, SPLIT_H);
-  // dY0 partial = act'(P0) * (dY1 W1[half])
+  if (!reg1) store_T<T, R>(U1, ldu1, HH, HH, gt1, Bp, r0, nvalid, dbp1, nullptr, SPLIT_H);
+  // dY0 partial = act'(P0) * (dY1 W1[half]): the role's last stash, which nothing reads from LDS
   gemm_hf<T, 2, NCH_HH, NT_H>(U1, ldu1, 0, ht1, relu ? P0 : nullptr, ldp0,
                               [&](int j, int col, const f32x4& acc, const float (&p)[4]) {
+    float dv[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {  // every column is one of layer 1's K = H inputs
       const int r = (((threadIdx.x & 63) >> 4) << 2) + i;
       float v = acc[i];
       if (relu && !(p[i] > 0.f)) v = 0.f;
-      Xb[r * ld + col] = v;
+      dv[i] = v;
+      if (!reg0) Xb[r * ld + col] = v;
     }
+    if constexpr (sizeof(T) == 4)
+      if (reg0) store_acc_T(gt0, WP * Bp, h * Bp + r0, col, dv, nvalid, true);
   });
+  if (reg0) {  // uniform
+    STAMP(35);
+    return;
+  }
   if (act != ACT_RELU && act != ACT_ID) act_pass_bwd<R>(Xb, ld, P0, ldp0, SPLIT_H >> 4, SPLIT_H, act);
   __syncthreads();
   store_T<T, R>(Xb, ld, SPLIT_H, SPLIT_H, gt0, WP * Bp, h * Bp + r0, nvalid, dbp0);
