@@ -752,6 +752,24 @@ __device__ __forceinline__ void critic_unit_backward(const AS_C EngineDev& E, co
   }
 }
 
+// ============================================================================ granule primitives
+// A data-tagged granule is one 8-B agent-scope word {value, epoch}: what the
+// role hand-offs (GranKind, below) and the update tiles' batch parts are built
+// from.  Every producer stores with gran_put; every poll tests the epoch with
+// gran_fresh, and a bounded spin that gives up calls sync_timeout.
+// SYNC_STAGED (u64 at words 4-5): step whose phase A last used a staged batch record
+enum SyncWord { SYNC_EPOCH = 0, SYNC_TIMEOUT = 1, SYNC_STAGED = 4, SYNC_CDONE = 64, SYNC_FLAGS = 128 };
+__device__ __forceinline__ void gran_put(AS_G uint64_t* g, float v, uint32_t ep) {
+  const uint64_t x = (uint64_t)__float_as_uint(v) | ((uint64_t)ep << 32);
+  __hip_atomic_store((uint64_t*)g, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ bool gran_fresh(uint64_t x, uint32_t ep) { return (uint32_t)(x >> 32) == ep; }
+__device__ __forceinline__ float gran_value(uint64_t x) { return __uint_as_float((uint32_t)x); }
+// a producer never ran: flag the error for the host (sac_engine_read_status), do not hang
+__device__ __forceinline__ void sync_timeout(const AS_C EngineDev& E) {
+  __hip_atomic_store((uint32_t*)GP(uint32_t, E.sync) + SYNC_TIMEOUT, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 // ============================================================================ phases B / D
 __device__ __forceinline__ float adam_elem(float& p, float& m, float& v, float g, float w1, float b2, float w2,
                                            float bc2s, float eps, float neg_step) {
@@ -766,19 +784,17 @@ __device__ __forceinline__ float adam_elem(float& p, float& m, float& v, float g
   return pn;
 }
 
-// One 32x32 weight tile of an update phase, UT threads:
-//   1. all threads stage the tile's 32 dY^T rows and 32 X^T rows (the dW GEMM's
-//      operands, K = batch) into LDS and fetch their elements' master weight,
+// One 32x32 weight tile of an update phase, UT threads: dw_adam_tile (below) calls these stages in order.
+//   1. geometry and loads (UpdGeom, UpdLoader, UpdState::load): all threads fetch the tile's 32 dY^T rows
+//      and 32 X^T rows (the dW GEMM's operands, K = batch) for LDS and their elements' master weight,
 //      Adam moments, target weight and bias state, all in one round trip;
-//   2. the dW MFMAs run as 16 (sub-tile, K-quarter) pairs spread over the
-//      waves (one pair per wave at 16 waves): pair p owns 16x16 sub-tile p & 3
-//      and the MFMA K-steps ch = p >> 2 (mod 4) of every staged chunk; the four
-//      K-quarter partials are summed in LDS in quarter order (the same bits for
-//      any block size);
-//   3. every thread updates 1024 / UT elements: Adam (torch single-tensor op
-//      order), Polyak, master weights; the packed compute copies are written
-//      from LDS as whole 16-B fragment pieces (plain stores: the reader is the
-//      next launch).
+//   2. dW (dw_single_round / dw_multi_round): the MFMAs run as 16 (sub-tile, K-quarter) pairs spread over
+//      the waves (one pair per wave at 16 waves): pair p owns 16x16 sub-tile p & 3 and the MFMA K-steps
+//      ch = p >> 2 (mod 4) of every staged chunk; the four K-quarter partials are summed in LDS in
+//      quarter order (the same bits for any block size);
+//   3. the batch-part hand-off (parts_publish / parts_collect) where a tile is split over the batch;
+//   4. Adam + Polyak (UpdState): every thread updates 1024 / UT elements, torch single-tensor op order;
+//   5. the packed compute copies (store_packed), from LDS as whole 16-B fragment pieces.
 // 16 waves (measured on C2: 256-thread tiles took B 8.7 / D 7.8 us vs 6.4 / 5.9)
 #define SAC_UPD_THREADS 1024
 #define SAC_UPD_BCH (512 / (int)sizeof(T))  // batch columns staged per chunk (512 B per row)
@@ -795,75 +811,87 @@ __device__ __forceinline__ lf* upd_partials() {
   __shared__ float part[SAC_UPD_PART_BYTES / 4];
   return (lf*)part;
 }
-template <typename T, int UT, int GS = 1, int MS = 2>
-__device__ __forceinline__ void dw_adam_tile(const AS_C EngineDev& E, const TileDesc* tdp_, bool polyak, int par,
-                                             int par_x, lf* lds) {
-  constexpr int KC = MM<T>::KC, KL = MM<T>::KL;
-  constexpr int EPR = 16 / sizeof(T);  // elements per 16-B piece (= KL)
-  constexpr int EPT = 1024 / UT;       // elements per thread
+
+// A stage takes the tile descriptor as a POINTER: as a reference parameter it is known dereferenceable, its
+// loads are hoisted out of the hand-off's poll loop with every granule address, and the 512-thread kernel
+// goes from 84 to 108 VGPRs (occupancy 5 -> 4; profiles/update_tile_stages_resources.txt).
+
+// ---- tile geometry: an instance's compile-time shape and one tile's LDS carve-up:
+// stage [ns][64][lds_row] of T | accs: dW, then new params [32][33] f32 | tgts: new targets [32][33] |
+// red: bias lanes [32][17] | seedL [MS][SAC_UPD_BCH]
+template <typename T, int UT, int MS>
+struct UpdGeom {
+  static constexpr int KC = MM<T>::KC, KL = MM<T>::KL;
+  static constexpr int EPR = 16 / sizeof(T);  // elements per 16-B piece (= KL)
+  static constexpr int EPT = 1024 / UT;       // elements per thread
+  // slots (MS: the kernel's cap -- 2, or 1 for the 512-thread phase B: a second slot in flight bought nothing
+  // there, one slot is C3 bf16 +1%, profiles/r05_ab_update_slots.txt), pieces per thread per operand per full chunk
+  static constexpr int MAXS = MS, PPO = 32 * (SAC_UPD_BCH / EPR) / UT;
+  static constexpr int SQ = EPR / 4;                           // seed f32x4 per 16-B piece (fp32 1, bf16 2)
+  static constexpr int KQ = 4, NWV = UT / 64, PPW = 16 / NWV;  // K-quarters, waves, pairs per wave
+  static constexpr int NIT = SAC_UPD_BCH / KC / KQ;            // MFMA K-steps per (slot, K-quarter)
+  static constexpr int NBP = SAC_UPD_BCH / (16 * EPR);         // bias pieces per lane per slot
+  // bias partial lanes: 16 per column (512 lanes, BPT per thread: the same sums for 8- and 16-wave blocks)
+  static constexpr int BPT = (512 + UT - 1) / UT;
+  static constexpr int lds_row = SAC_UPD_BCH + 16 / (int)sizeof(T);  // +16 B per row: rows start on different banks
+  static constexpr int slot_el = 64 * lds_row;                       // T elements per stage slot
   static_assert(EPR == KL, "a piece is one lane's fragment slice");
-  const AS_C TileDesc& td = *(const AS_C TileDesc*)tdp_;  // scalar loads
-  STAMP(polyak ? 48 : 52);
-  const int tid = threadIdx.x;
-  const int Bp = td.bp;
-  // LDS: stage [64][SAC_UPD_BCH + pad] of T | acc / new params [32][33] f32 | targets [32][33] | bias reduce [32][17]
-  const int lds_row = SAC_UPD_BCH + 16 / (int)sizeof(T);  // +16 B per row: rows start on different banks
-  AS_L T* stage = (AS_L T*)lds;
-  const int nslot = E.upd_slots;
-  // slots (MS: the kernel's cap -- 2, or 1 for the 512-thread phase B: a
-  // second slot in flight bought nothing there, one slot is C3 bf16 +1%,
-  // profiles/r05_ab_update_slots.txt), pieces per thread per operand (32 rows)
-  // per full chunk
-  constexpr int MAXS = MS, PPO = 32 * (SAC_UPD_BCH / EPR) / UT;
-  const int ns = nslot < MAXS ? nslot : MAXS;  // slots per round
-  const int slot_el = 64 * lds_row;  // T elements per stage slot
-  lf* accs = lds + (ns * slot_el * (int)sizeof(T) + 15) / 16 * 4;
-  lf* tgts = accs + 32 * 33;
-  lf* red = tgts + 32 * 33;
-  // this step's Adam scalars (written by phase A)
-  const float neg_step = GPC(float, E.adam_sc)[par * 6 + td.opt * 2];
-  const float bc2s = GPC(float, E.adam_sc)[par * 6 + td.opt * 2 + 1];
-  // ---- 1. loads: the first round of staged operands, then element state + bias
-  // state + bias partials, all before the first wait (one round trip; the bias
-  // sums below wait for everything issued before them, in issue order)
   static_assert(PPO >= 1 && (32 * (SAC_UPD_BCH / EPR)) % UT == 0, "whole pieces per thread");
-  const int rstep = ns * SAC_UPD_BCH;          // batch columns per round
-  u32x4 rg[MAXS][GS + 1][PPO];                 // [slot][dY part 0..GS-1, then X][piece]
-  // the batch columns' seeds (TileDesc::seed).  Per dY piece (sdr) they are 16x
-  // redundant loads, as many bytes as the dY pieces themselves through each CU's
-  // load path; with several rounds (fp32 at C3) each chunk's seeds are instead
-  // loaded ONCE (by the first bch / 4 threads) and handed over through LDS, a
-  // round's written at the end of the round before: C3 fp32 +3%, while at C2
-  // (one round) the extra barrier cost phase B 0.5 us (profiles/r05_ab_seeds_lds.txt)
-  const AS_G float* const seedp = GPC(float, td.seed);  // uniform
-  const bool lseeds = seedp && sizeof(T) == 4 && Bp > rstep;  // uniform
-  AS_L float* seedL = (AS_L float*)(red + 32 * 17);      // [MAXS][SAC_UPD_BCH]
-  f32x4 sreg[MAXS];                                       // lseeds: the next round's seeds of slot sl (tid < bch / 4)
-  constexpr int SQ = EPR / 4;                             // seed f32x4 per 16-B piece (fp32 1, bf16 2)
-  f32x4 sdr[MAXS][PPO][SQ];                               // !lseeds: the seeds of this thread's dY pieces
-  // the operands' bases as separate values: a per-lane choice between two
-  // descriptor fields was compiled into a per-lane LOAD of the chosen field and a
-  // wait before every piece (the pieces' loads ran one round trip after another)
-  const AS_G T* const gsrc = GPC(T, td.GT);
-  const AS_G T* const xsrc = GPC(T, td.XT) + par_x * td.xt_par;
-  const long goff = GS > 1 ? td.goff : 0;
-  const int ldg = td.ld, ldx = td.ldx;
-  // round r0's slot sl -> rg[sl] (16-B pieces of the 32 dY^T rows of every part, then of the 32 X^T rows)
-  // what: 1 operands, 2 seeds, 3 both
-  auto issue_seeds = [&](int r0, auto slc) __attribute__((always_inline)) {
-    constexpr int sl = decltype(slc)::value;
+  static_assert(UT % 64 == 0 && 16 % NWV == 0, "16 (sub-tile, K-quarter) pairs over whole waves");
+  const int tid, Bp, ns, rstep;  // ns: slots per round, rstep: batch columns per round
+  AS_L T* const stage;
+  lf *const accs, *const tgts, *const red;
+  AS_L float* const seedL;
+  __device__ __forceinline__ UpdGeom(const AS_C EngineDev& E, const AS_C TileDesc* td, lf* lds)
+      : tid(threadIdx.x), Bp(td->bp), ns(E.upd_slots < MAXS ? E.upd_slots : MAXS), rstep(ns * SAC_UPD_BCH),
+        stage((AS_L T*)lds), accs(lds + (ns * slot_el * (int)sizeof(T) + 15) / 16 * 4), tgts(accs + 32 * 33),
+        red(tgts + 32 * 33), seedL((AS_L float*)(red + 32 * 17)) {}
+  // batch columns of the chunk that starts at column b0
+  static __device__ __forceinline__ int bch(int Bp, int b0) { return Bp - b0 < SAC_UPD_BCH ? Bp - b0 : SAC_UPD_BCH; }
+};
+// element el = en * 32 + ek of the tile in a [32][33] LDS area
+__device__ __forceinline__ int upd_el(int el) { return (el >> 5) * 33 + (el & 31); }
+
+// ---- the operand and seed loader: a round's 16-B pieces of the 32 dY^T rows of every part and of the 32
+// X^T rows, held in registers (rg) until their slot of the stage is free, and the batch columns' seeds
+// (TileDesc::seed).  Per dY piece (sdr) the seeds are 16x redundant loads, as many bytes as the dY pieces
+// themselves through each CU's load path; with several rounds (fp32 at C3) each chunk's seeds are instead
+// loaded ONCE (by the first bch / 4 threads) and handed over through LDS, a round's written at the end of the
+// round before: C3 fp32 +3%, while at C2 (one round) the extra barrier cost phase B 0.5 us
+// (profiles/r05_ab_seeds_lds.txt)
+template <typename T, int UT, int GS, int MS>
+struct UpdLoader {
+  typedef UpdGeom<T, UT, MS> Geom;
+  static constexpr int EPR = Geom::EPR, PPO = Geom::PPO, SQ = Geom::SQ, MAXS = Geom::MAXS;
+  const Geom& t;
+  const AS_G float* const seedp;  // uniform
+  const bool lseeds;              // uniform
+  // the operands' bases as separate values: a per-lane choice between two descriptor fields was compiled into a
+  // per-lane LOAD of the chosen field and a wait before every piece (the loads ran one round trip after another)
+  const AS_G T *const gsrc, *const xsrc;
+  const long goff;
+  const int ldg, ldx;
+  u32x4 rg[MAXS][GS + 1][PPO];  // [slot][dY part 0..GS-1, then X][piece]
+  f32x4 sreg[MAXS];             // lseeds: the next round's seeds of slot sl (tid < bch / 4)
+  f32x4 sdr[MAXS][PPO][SQ];     // !lseeds: the seeds of this thread's dY pieces
+  __device__ __forceinline__ UpdLoader(const Geom& t_, const AS_C TileDesc* td, int par_x)
+      : t(t_), seedp(GPC(float, td->seed)), lseeds(seedp && sizeof(T) == 4 && t_.Bp > t_.rstep),
+        gsrc(GPC(T, td->GT)), xsrc(GPC(T, td->XT) + par_x * td->xt_par), goff(GS > 1 ? td->goff : 0), ldg(td->ld),
+        ldx(td->ldx) {}
+  template <int sl>
+  __device__ __forceinline__ void issue_seeds(int r0, std::integral_constant<int, sl>) {
     const int b0 = r0 + sl * SAC_UPD_BCH;
-    if (lseeds && sl < ns && b0 < Bp) {  // uniform
-      const int bch = Bp - b0 < SAC_UPD_BCH ? Bp - b0 : SAC_UPD_BCH;
+    if (lseeds && sl < t.ns && b0 < t.Bp) {  // uniform
+      const int bch = t.bch(t.Bp, b0);
       if (threadIdx.x * 4 < bch) sreg[sl] = *(const AS_G f32x4*)(seedp + b0 + threadIdx.x * 4);
     }
-  };
-  // pieces: seeds = false for round 0 (its seeds were issued before any piece)
-  auto issue = [&](int r0, auto slc, bool seeds = true) {
-    constexpr int sl = decltype(slc)::value;
+  }
+  // round r0's slot sl -> rg[sl].  seeds = false for round 0 (its seeds were issued before any piece)
+  template <int sl>
+  __device__ __forceinline__ void issue(int r0, std::integral_constant<int, sl> slc, bool seeds = true) {
     const int b0 = r0 + sl * SAC_UPD_BCH;
-    if (sl < ns && b0 < Bp) {  // uniform
-      const int bch = Bp - b0 < SAC_UPD_BCH ? Bp - b0 : SAC_UPD_BCH;
+    if (sl < t.ns && b0 < t.Bp) {  // uniform
+      const int bch = t.bch(t.Bp, b0);
       const int per_row = bch / EPR;  // 16-B pieces per operand row of this chunk
       // the slot's seeds before its pieces: their wait (end of round) then does
       // not include this slot's pieces
@@ -881,86 +909,29 @@ __device__ __forceinline__ void dw_adam_tile(const AS_C EngineDev& E, const Tile
             for (int q = 0; q < SQ; ++q) sdr[sl][pi][q] = *(const AS_G f32x4*)(seedp + b0 + pc * EPR + 4 * q);
         }
     }
-  };
-  // round 0: every slot's seeds, then the pieces (the seeds' wait below includes no piece)
-  static_for<MAXS>([&](auto sl) { issue_seeds(0, sl); });
-  static_for<MAXS>([&](auto sl) { issue(0, sl, false); });
-  // the seeds of round r0 + rstep's slots -> LDS (after round r0's last reads of seedL)
-  auto seeds_to_lds = [&](int r0) __attribute__((always_inline)) {
+  }
+  // the seeds of round r0's slots -> LDS (after the round before's last reads of seedL)
+  __device__ __forceinline__ void seeds_to_lds(int r0) {
     if (lseeds)  // uniform
       static_for<MAXS>([&](auto slc) {
         constexpr int sl = decltype(slc)::value;
         const int b0 = r0 + sl * SAC_UPD_BCH;
-        if (sl < ns && b0 < Bp) {
-          const int bch = Bp - b0 < SAC_UPD_BCH ? Bp - b0 : SAC_UPD_BCH;
-          if (tid * 4 < bch) *(AS_L f32x4*)(seedL + sl * SAC_UPD_BCH + tid * 4) = sreg[sl];
+        if (sl < t.ns && b0 < t.Bp) {
+          const int bch = t.bch(t.Bp, b0);
+          if (t.tid * 4 < bch) *(AS_L f32x4*)(t.seedL + sl * SAC_UPD_BCH + t.tid * 4) = sreg[sl];
         }
       });
-  };
-  AS_G float* W = GP(float, td.W);
-  AS_G float* Wm = GP(float, td.Wm);
-  AS_G float* Wv = GP(float, td.Wv);
-  AS_G float* tW = GP(float, td.tW);
-  float p[EPT], m[EPT], v[EPT], tp[EPT];
-  size_t idx[EPT];
-  bool ok[EPT];
-#pragma unroll
-  for (int e = 0; e < EPT; ++e) {
-    const int el = tid + e * UT, en = el >> 5, ek = el & 31;  // element (n0 + en, k0 + ek)
-    const int n = td.n0 + en, k = td.k0 + ek;
-    ok[e] = n < td.N && k < td.K;
-    idx[e] = ok[e] ? (size_t)n * td.K + k : 0;
-    if (td.kpart < 2) {  // uniform: a producer part only computes its partial dW
-      p[e] = W[idx[e]];
-      m[e] = Wm[idx[e]];
-      v[e] = Wv[idx[e]];
-      tp[e] = polyak ? tW[idx[e]] : 0.f;
-    } else {
-      p[e] = m[e] = v[e] = tp[e] = 0.f;
-    }
   }
-  const bool do_bias = td.k0 == 0 && td.kpart <= 1;
-  // the bias gradient is summed from the staged (seed-scaled) dY rows, every
-  // batch part its own columns (handed over with the partial dW)
-  const bool bias_acc = td.k0 == 0;
-  float pb = 0.f, mb = 0.f, vb = 0.f, tbv = 0.f;
-  if (do_bias && tid < 32 && td.n0 + tid < td.N) {
-    pb = GPC(float, td.b)[td.n0 + tid];
-    mb = GPC(float, td.bm)[td.n0 + tid];
-    vb = GPC(float, td.bv)[td.n0 + tid];
-    if (polyak) tbv = GPC(float, td.tb)[td.n0 + tid];
-  }
-  // bias partial lanes: 16 per column (512 lanes, BPT per thread: the same sums
-  // for 8- and 16-wave blocks), summed in LDS in lane order below
-  constexpr int BPT = (512 + UT - 1) / UT;
-  float bsum[BPT];
-#pragma unroll
-  for (int j = 0; j < BPT; ++j) bsum[j] = 0.f;
-  // ---- 2. dW = dY^T X over the batch, staged through LDS in 512-B row chunks,
-  // nslot chunks per round; waves run (16x16 sub-tile, K-quarter) pairs, chunks
-  // in batch order.  A slot's registers are re-issued for the next round as
-  // soon as they are in LDS, so round r + 1's loads land under round r's MFMAs.
-  const int lane = tid & 63, wave = wave_id();
-  const int c = lane & 15, g = lane >> 4;
-  constexpr int KQ = 4, NWV = UT / 64, PPW = 16 / NWV;  // K-quarters, waves, pairs per wave
-  static_assert(UT % 64 == 0 && 16 % NWV == 0, "16 (sub-tile, K-quarter) pairs over whole waves");
-  f32x4 acc[PPW];
-#pragma unroll
-  for (int j = 0; j < PPW; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  // round 0's seeds -> LDS: issued first, so this waits for them alone, after
-  // every load of the tile (operands, element state, bias) is in flight
-  seeds_to_lds(0);
-  if (lseeds) __syncthreads();  // uniform
   // slot sl's pieces of a round -> LDS (waits only for this slot's loads: they
   // complete in issue order): dY parts added and seed-scaled in registers
-  auto stage_slot = [&](auto slc, int bch) __attribute__((always_inline)) {
-    constexpr int sl = decltype(slc)::value;
+  template <int sl>
+  __device__ __forceinline__ void stage_slot(std::integral_constant<int, sl>, int bch) {
     const int per_row = bch / EPR;
 #pragma unroll
     for (int op = 0; op < 2; ++op)
 #pragma unroll
       for (int pi = 0; pi < PPO; ++pi) {
-        const int i = tid + pi * UT;
+        const int i = t.tid + pi * UT;
         const int row = i / per_row + 32 * op, pc = i % per_row;
         u32x4 v = rg[sl][op ? GS : 0][pi];
         if constexpr (sizeof(T) == 4) {
@@ -973,7 +944,7 @@ __device__ __forceinline__ void dw_adam_tile(const AS_C EngineDev& E, const Tile
             }
           if (op == 0 && seedp)
             v = __builtin_bit_cast(u32x4, __builtin_bit_cast(f32x4, v) *
-                                              (lseeds ? *(const AS_L f32x4*)(seedL + sl * SAC_UPD_BCH + pc * EPR)
+                                              (lseeds ? *(const AS_L f32x4*)(t.seedL + sl * SAC_UPD_BCH + pc * EPR)
                                                       : sdr[sl][pi][0]));
         } else if (op == 0 && (GS > 1 || seedp)) {
           // bf16 dY: the parts added in fp32 (part order), scaled by the
@@ -995,321 +966,395 @@ __device__ __forceinline__ void dw_adam_tile(const AS_C EngineDev& E, const Tile
           for (int e = 0; e < 8; ++e) h[e] = (bf16)a[e];
           v = __builtin_bit_cast(u32x4, h);
         }
-        if (i < 32 * per_row) *(AS_L u32x4*)(stage + sl * slot_el + row * lds_row + pc * EPR) = v;
+        if (i < 32 * per_row) *(AS_L u32x4*)(t.stage + sl * t.slot_el + row * t.lds_row + pc * EPR) = v;
       }
-  };
-  // ---- single-round tiles: the 1024-thread kernels with the whole batch in
-  // one round's slots (every tile of the small-batch layouts).  One barrier
-  // once every slot is staged; each wave then issues all fragment reads of its
-  // (sub-tile, K-quarter) pair and runs its MFMAs in the multi-round order
-  // (slot 0's chunks kq, kq + 4, .., then slot 1's), the bias lanes' reads in
-  // flight under them.  The K-quarter partials go to an LDS area of their own
-  // (upd_partials: nothing waits for the stage to be free), and after the
-  // second barrier the thread that sums an element's partials keeps the sum in
-  // a register (gel) for its Adam step: 3 barriers per tile, 7 on the
-  // multi-round path below.  Every float operation is the multi-round path's,
-  // in the same order.
-  constexpr int NIT = SAC_UPD_BCH / KC / KQ;     // MFMA K-steps per (slot, K-quarter)
-  constexpr int NBP = SAC_UPD_BCH / (16 * EPR);  // bias pieces per lane per slot
-  bool single = false;
-  if constexpr (UT == SAC_UPD_THREADS) single = Bp <= rstep;  // uniform
-  float gel[EPT];  // single-round: the elements' dW (K-quarters summed, then the batch parts)
-  if (single) {
-    if constexpr (UT == SAC_UPD_THREADS) {
-      static_assert(PPW == 1 && BPT == 1, "one (sub-tile, K-quarter) pair per wave");
-      typedef typename MM<T>::Frag Frag;
+  }
+};
+
+struct AdamHyp {  // one step's Adam / Polyak scalars
+  float w1, b2, w2, bc2s, eps, neg_step, tau, omt;
+};
+// the 16 bias partial lanes of column n, in lane order
+__device__ __forceinline__ float bias_lane_sum(const lf* red, int n) {
+  float gb = 0.f;
+  for (int q = 0; q < 16; ++q) gb += red[n * 17 + q];
+  return gb;
+}
+
+// ---- element and bias state: this thread's 1024 / UT elements' master weight,
+// Adam moments and target weight, and (tid < 32 of a k0 == 0 tile) one bias
+// column's; loaded behind round 0's operands, updated and stored by the Adam steps
+template <int UT>
+struct UpdState {
+  static constexpr int EPT = 1024 / UT;
+  static constexpr int MAXP = UT == 512 ? 7 : 3;  // producer parts a consumer takes (the 512-thread tiles: up to 7)
+  AS_G float *W, *Wm, *Wv, *tW;
+  float p[EPT], m[EPT], v[EPT], tp[EPT];
+  size_t idx[EPT];
+  bool ok[EPT];
+  bool do_bias;
+  // the bias gradient is summed from the staged (seed-scaled) dY rows, every
+  // batch part its own columns (handed over with the partial dW)
+  bool bias_acc;
+  float pb, mb, vb, tbv;
+  float pn[EPT], tn[EPT];  // the new weights and target weights (padding elements: 0, as packed)
+
+  __device__ __forceinline__ void load(const AS_C TileDesc* td, bool polyak, int tid) {
+    W = GP(float, td->W);
+    Wm = GP(float, td->Wm);
+    Wv = GP(float, td->Wv);
+    tW = GP(float, td->tW);
+    static_for<EPT>([&](auto ec) {  // (compile-time indices: the members stay SSA values)
+      constexpr int e = decltype(ec)::value;
+      const int el = tid + e * UT, en = el >> 5, ek = el & 31;  // element (n0 + en, k0 + ek)
+      const int n = td->n0 + en, k = td->k0 + ek;
+      ok[e] = n < td->N && k < td->K;
+      idx[e] = ok[e] ? (size_t)n * td->K + k : 0;
+      if (td->kpart < 2) {  // uniform: a producer part only computes its partial dW
+        p[e] = W[idx[e]];
+        m[e] = Wm[idx[e]];
+        v[e] = Wv[idx[e]];
+        tp[e] = polyak ? tW[idx[e]] : 0.f;
+      } else {
+        // (stored in the branch above's order: merging the two branches' stores
+        // must not pair different members, which would leave them in scratch)
+        p[e] = 0.f, m[e] = 0.f, v[e] = 0.f, tp[e] = 0.f;
+      }
+    });
+    do_bias = td->k0 == 0 && td->kpart <= 1;
+    bias_acc = td->k0 == 0;
+    pb = 0.f, mb = 0.f, vb = 0.f, tbv = 0.f;
+    if (do_bias && tid < 32 && td->n0 + tid < td->N) {
+      pb = GPC(float, td->b)[td->n0 + tid];
+      mb = GPC(float, td->bm)[td->n0 + tid];
+      vb = GPC(float, td->bv)[td->n0 + tid];
+      if (polyak) tbv = GPC(float, td->tb)[td->n0 + tid];
+    }
+  }
+  // Adam (torch single-tensor op order) + Polyak on the elements; the masters are stored at once
+  __device__ __forceinline__ void adam_elements(const AdamHyp& h, bool polyak, bool single, const float (&gel)[EPT],
+                                                const lf* accs, int tid) {
+    static_for<EPT>([&](auto ec) {
+      constexpr int e = decltype(ec)::value;
+      const int el = tid + e * UT;
+      pn[e] = 0.f;
+      tn[e] = 0.f;
+      if (ok[e]) {
+        const float dw = single ? gel[e] : accs[upd_el(el)];
+        pn[e] = adam_elem(p[e], m[e], v[e], dw, h.w1, h.b2, h.w2, h.bc2s, h.eps, h.neg_step);
+        W[idx[e]] = p[e];
+        Wm[idx[e]] = m[e];
+        Wv[idx[e]] = v[e];
+        if (polyak) {
+          tn[e] = h.tau * pn[e] + h.omt * tp[e];
+          tW[idx[e]] = tn[e];
+        }
+      }
+    });
+  }
+  // the new values -> LDS, for the packed copies
+  __device__ __forceinline__ void new_values_to_lds(lf* accs, lf* tgts, bool polyak, int tid) {
+    static_for<EPT>([&](auto ec) {
+      constexpr int e = decltype(ec)::value;
+      const int el = tid + e * UT;
+      accs[upd_el(el)] = pn[e];
+      if (polyak) tgts[upd_el(el)] = tn[e];
+    });
+  }
+  // the bias column of tid < 32: its lanes' sums, then the other batch parts' (gbx, part order)
+  __device__ __forceinline__ void adam_bias(const AS_C TileDesc* td, const AdamHyp& h, bool polyak, const lf* red,
+                                            const float (&gbx)[MAXP], int tid) {
+    if (do_bias && tid < 32 && td->n0 + tid < td->N) {
+      float gb = bias_lane_sum(red, tid);
+      if (td->kpart) {
+#pragma unroll
+        for (int q = 0; q < MAXP; ++q)
+          if (q < td->nparts - 1) gb += gbx[q];
+      }
+      const float pbn = adam_elem(pb, mb, vb, gb, h.w1, h.b2, h.w2, h.bc2s, h.eps, h.neg_step);
+      GP(float, td->b)[td->n0 + tid] = pb;
+      GP(float, td->bm)[td->n0 + tid] = mb;
+      GP(float, td->bv)[td->n0 + tid] = vb;
+      if (polyak) GP(float, td->tb)[td->n0 + tid] = h.tau * pbn + h.omt * tbv;  // read by the next step's launch only
+    }
+  }
+};
+
+// ---- what the two dW paths share
+// pair pr of the 16 (sub-tile, K-quarter) pairs: K-quarter kq of the 16x16 sub-tile at rows sn, columns sk
+struct UpdPair {
+  int kq, sn, sk;
+};
+__device__ __forceinline__ UpdPair upd_pair(int pr) { return UpdPair{pr >> 2, ((pr & 3) >> 1) * 16, (pr & 1) * 16}; }
+// one 16-B piece of a staged (scaled) dY row, summed for the bias gradient
+template <typename T>
+__device__ __forceinline__ float bias_piece_sum(typename MM<T>::Frag x) {
+  if constexpr (sizeof(T) == 4) {
+    return (x[0] + x[1]) + (x[2] + x[3]);
+  } else {
+    float s = 0.f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) s += (float)x[e];
+    return s;
+  }
+}
+// a wave's accumulator of pair pr -> its K-quarter's [32][33] partial in part (lane: column c, rows g * 4 ..)
+__device__ __forceinline__ void put_partials(lf* part, const UpdPair& pr, int g, int c, const f32x4& acc) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) part[pr.kq * (32 * 33) + (pr.sn + g * 4 + i) * 33 + pr.sk + c] = acc[i];
+}
+// element offset o's four K-quarter partials, summed in quarter order (the same bits for any block size)
+__device__ __forceinline__ float sum_quarters(const lf* part, int o) {
+  float sum = part[o];
+#pragma unroll
+  for (int q = 1; q < 4; ++q) sum += part[q * (32 * 33) + o];
+  return sum;
+}
+
+// ---- dW, single-round tiles: the 1024-thread kernels with the whole batch in one round's slots (every tile
+// of the small-batch layouts).  One barrier once every slot is staged; each wave then issues all fragment
+// reads of its (sub-tile, K-quarter) pair and runs its MFMAs in the multi-round order (slot 0's chunks kq,
+// kq + 4, .., then slot 1's), the bias lanes' reads in flight under them.  The K-quarter partials go to an
+// LDS area of their own (upd_partials: nothing waits for the stage to be free), and after the second barrier
+// the thread that sums an element's partials keeps the sum in a register (gel) for its Adam step: 2 barriers
+// here, 3 per tile.  Every float operation is the multi-round path's, in the same order.
+template <typename T, int UT, int GS, int MS>
+__device__ __forceinline__ void dw_single_round(const AS_C EngineDev& E, const UpdGeom<T, UT, MS>& t,
+                                                UpdLoader<T, UT, GS, MS>& ld, bool polyak, bool bias_acc,
+                                                float (&gel)[1024 / UT]) {
+  typedef UpdGeom<T, UT, MS> Geom;
+  typedef typename MM<T>::Frag Frag;
+  constexpr int KC = Geom::KC, KL = Geom::KL, EPR = Geom::EPR, EPT = Geom::EPT, MAXS = Geom::MAXS;
+  constexpr int KQ = Geom::KQ, NIT = Geom::NIT, NBP = Geom::NBP;
+  static_assert(Geom::PPW == 1 && Geom::BPT == 1, "one (sub-tile, K-quarter) pair per wave");
+  const int tid = t.tid, Bp = t.Bp, ns = t.ns;
+  const int lane = tid & 63, wave = wave_id();
+  const int c = lane & 15, g = lane >> 4;
+  f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+  float bsum = 0.f;
+  static_for<MAXS>([&](auto slc) {
+    constexpr int sl = decltype(slc)::value;
+    const int b0 = sl * SAC_UPD_BCH;
+    if (sl < ns && b0 < Bp) ld.stage_slot(slc, t.bch(Bp, b0));  // uniform
+  });
+  __syncthreads();  // 1: every slot staged
+  STAMP(polyak ? 51 : 55);
+  const UpdPair pr = upd_pair(wave);
+  const int kq = pr.kq;
+  const int bn = tid >> 4, bs = tid & 15;
+  const bool bias_lane = bias_acc && tid < 512;
+  // FULL: every slot in use is a whole one (compile-time trip counts, no masks)
+  auto dw_and_bias = [&](auto fullc) __attribute__((always_inline)) {
+    constexpr bool FULL = decltype(fullc)::value;
+    Frag fa[MAXS][NIT], fb[MAXS][NIT], bx[MAXS][NBP];
+    auto slots = [&](auto&& f) __attribute__((always_inline)) {
       static_for<MAXS>([&](auto slc) {
         constexpr int sl = decltype(slc)::value;
         const int b0 = sl * SAC_UPD_BCH;
-        if (sl < ns && b0 < Bp) stage_slot(slc, Bp - b0 < SAC_UPD_BCH ? Bp - b0 : SAC_UPD_BCH);  // uniform
+        if (sl < ns && b0 < Bp)  // uniform
+          f(slc, FULL || Bp - b0 >= SAC_UPD_BCH ? SAC_UPD_BCH : Bp - b0);
       });
-      __syncthreads();
-      STAMP(polyak ? 51 : 55);
-      const int kq = wave >> 2, sn = ((wave & 3) >> 1) * 16, sk = (wave & 1) * 16;
-      const int bn = tid >> 4, bs = tid & 15;
-      const bool bias_lane = bias_acc && tid < 512;
-      // FULL: every slot in use is a whole one (compile-time trip counts, no masks)
-      auto dw_and_bias = [&](auto fullc) __attribute__((always_inline)) {
-        constexpr bool FULL = decltype(fullc)::value;
-        Frag fa[MAXS][NIT], fb[MAXS][NIT], bx[MAXS][NBP];
-        auto slots = [&](auto&& f) __attribute__((always_inline)) {
-          static_for<MAXS>([&](auto slc) {
-            constexpr int sl = decltype(slc)::value;
-            const int b0 = sl * SAC_UPD_BCH;
-            if (sl < ns && b0 < Bp)  // uniform
-              f(slc, FULL || Bp - b0 >= SAC_UPD_BCH ? SAC_UPD_BCH : Bp - b0);
-          });
-        };
-        slots([&](auto slc, int bch) {
-          constexpr int sl = decltype(slc)::value;
-          const AS_L T* arow = stage + sl * slot_el + (sn + c) * lds_row + g * KL;
-          const AS_L T* brow = stage + sl * slot_el + (32 + sk + c) * lds_row + g * KL;
+    };
+    slots([&](auto slc, int bch) {
+      constexpr int sl = decltype(slc)::value;
+      const AS_L T* arow = t.stage + sl * t.slot_el + (pr.sn + c) * t.lds_row + g * KL;
+      const AS_L T* brow = t.stage + sl * t.slot_el + (32 + pr.sk + c) * t.lds_row + g * KL;
 #pragma unroll
-          for (int it = 0; it < NIT; ++it) {
-            const int ch = kq + it * KQ;
-            if (FULL || ch < bch / KC) {
-              fa[sl][it] = *(const AS_L Frag*)(arow + ch * KC);
-              fb[sl][it] = *(const AS_L Frag*)(brow + ch * KC);
-            }
-          }
-        });
-        if (bias_lane)  // lane bs takes its row's 16-B pieces bs, bs + 16, ... of the (scaled) dY rows
-          slots([&](auto slc, int bch) {
-            constexpr int sl = decltype(slc)::value;
-#pragma unroll
-            for (int it = 0; it < NBP; ++it) {
-              const int bc = (bs + it * 16) * EPR;
-              if (FULL || bc < bch) bx[sl][it] = *(const AS_L Frag*)(stage + sl * slot_el + bn * lds_row + bc);
-            }
-          });
-        slots([&](auto slc, int bch) {
-          constexpr int sl = decltype(slc)::value;
-#pragma unroll
-          for (int it = 0; it < NIT; ++it)
-            if (FULL || kq + it * KQ < bch / KC) MM<T>::mma(acc[0], fa[sl][it], fb[sl][it]);
-        });
-        if (bias_lane)
-          slots([&](auto slc, int bch) {
-            constexpr int sl = decltype(slc)::value;
-#pragma unroll
-            for (int it = 0; it < NBP; ++it)
-              if (FULL || (bs + it * 16) * EPR < bch) {
-                const Frag x = bx[sl][it];
-                if constexpr (sizeof(T) == 4) {
-                  bsum[0] += (x[0] + x[1]) + (x[2] + x[3]);
-                } else {
-                  float s = 0.f;
-#pragma unroll
-                  for (int e = 0; e < 8; ++e) s += (float)x[e];
-                  bsum[0] += s;
-                }
-              }
-          });
-      };
-      if (Bp % SAC_UPD_BCH == 0)  // uniform
-        dw_and_bias(std::true_type{});
-      else
-        dw_and_bias(std::false_type{});
-      STAMP(polyak ? 49 : 53);
-      lf* part = upd_partials();
-#pragma unroll
-      for (int i = 0; i < 4; ++i) part[kq * (32 * 33) + (sn + g * 4 + i) * 33 + sk + c] = acc[0][i];
-      if (bias_lane) red[bn * 17 + bs] = bsum[0];
-      __syncthreads();
-#pragma unroll
-      for (int e = 0; e < EPT; ++e) {  // summed in quarter order
-        const int el = tid + e * UT, o = (el >> 5) * 33 + (el & 31);
-        float sum = part[o];
-#pragma unroll
-        for (int q = 1; q < KQ; ++q) sum += part[q * (32 * 33) + o];
-        gel[e] = sum;
+      for (int it = 0; it < NIT; ++it) {
+        const int ch = kq + it * KQ;
+        if (FULL || ch < bch / KC) {
+          fa[sl][it] = *(const AS_L Frag*)(arow + ch * KC);
+          fb[sl][it] = *(const AS_L Frag*)(brow + ch * KC);
+        }
       }
-    }
-  } else {
-    for (int r0 = 0; r0 < Bp; r0 += rstep) {
-      // slot by slot: its pieces -> LDS, the next round's loads into its
-      // registers, barrier, its MFMAs -- while the later slots' loads are still
-      // landing
-      static_for<MAXS>([&](auto slc) {
+    });
+    if (bias_lane)  // lane bs takes its row's 16-B pieces bs, bs + 16, ... of the (scaled) dY rows
+      slots([&](auto slc, int bch) {
         constexpr int sl = decltype(slc)::value;
-        const int b0 = r0 + sl * SAC_UPD_BCH;
-        if (sl < ns && b0 < Bp) {  // uniform
-          const int bch = Bp - b0 < SAC_UPD_BCH ? Bp - b0 : SAC_UPD_BCH;
-          stage_slot(slc, bch);
-          issue(r0 + rstep, slc);
-          __syncthreads();
-          if (r0 == 0 && sl == 0) STAMP(polyak ? 51 : 55);
-          if (bias_acc) {  // bias gradient: this lane's columns of the slot's (scaled) dY rows
 #pragma unroll
-            for (int j = 0; j < BPT; ++j) {
-              const int t = tid + j * UT, bn = t >> 4, bs = t & 15;
-              if (t < 512)  // 16-B LDS reads: lane bs takes the row's 16-B pieces bs, bs + 16, ...
-                for (int c = bs * EPR; c < bch; c += 16 * EPR) {
-                  const AS_L T* q = stage + sl * slot_el + bn * lds_row + c;
-                  if constexpr (sizeof(T) == 4) {
-                    const f32x4 x = *(const AS_L f32x4*)q;
-                    bsum[j] += (x[0] + x[1]) + (x[2] + x[3]);
-                  } else {
-                    const bf16x8 x = *(const AS_L bf16x8*)q;
-                    float s = 0.f;
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) s += (float)x[e];
-                    bsum[j] += s;
-                  }
-                }
-            }
-          }
-#pragma unroll
-          for (int j = 0; j < PPW; ++j) {
-            const int pr = wave + j * NWV, kq = pr >> 2;
-            const int ns = ((pr & 3) >> 1) * 16, ks = (pr & 1) * 16;
-            const AS_L T* arow = stage + sl * slot_el + (ns + c) * lds_row + g * KL;
-            const AS_L T* brow = stage + sl * slot_el + (32 + ks + c) * lds_row + g * KL;
-            for (int ch = kq; ch < bch / KC; ch += KQ) {
-              typename MM<T>::Frag a, b;
-              if constexpr (sizeof(T) == 2) {
-                a = *(const AS_L bf16x8*)(arow + ch * KC);
-                b = *(const AS_L bf16x8*)(brow + ch * KC);
-              } else {
-                a = *(const AS_L f32x4*)(arow + ch * KC);
-                b = *(const AS_L f32x4*)(brow + ch * KC);
-              }
-              MM<T>::mma(acc[j], a, b);
-            }
-          }
+        for (int it = 0; it < NBP; ++it) {
+          const int bc = (bs + it * 16) * EPR;
+          if (FULL || bc < bch) bx[sl][it] = *(const AS_L Frag*)(t.stage + sl * t.slot_el + bn * t.lds_row + bc);
         }
       });
-      seeds_to_lds(r0 + rstep);  // every thread's reads of this round's seeds are behind a slot barrier
-      __syncthreads();  // the stage is refilled by the next round
-    }
-    STAMP(polyak ? 49 : 53);
-    {  // K-quarter partials -> the (free) stage area, summed in quarter order below
+    slots([&](auto slc, int bch) {
+      constexpr int sl = decltype(slc)::value;
 #pragma unroll
-      for (int j = 0; j < PPW; ++j) {
-        const int pr = wave + j * NWV;
-        const int ns = ((pr & 3) >> 1) * 16, ks = (pr & 1) * 16;
-        lf* part = (lf*)stage + (pr >> 2) * (32 * 33);
+      for (int it = 0; it < NIT; ++it)
+        if (FULL || kq + it * KQ < bch / KC) MM<T>::mma(acc, fa[sl][it], fb[sl][it]);
+    });
+    if (bias_lane)
+      slots([&](auto slc, int bch) {
+        constexpr int sl = decltype(slc)::value;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) part[(ns + g * 4 + i) * 33 + ks + c] = acc[j][i];
-      }
-    }
-    __syncthreads();
-    for (int el = tid; el < 1024; el += UT) {
-      const int o = (el >> 5) * 33 + (el & 31);
-      const lf* part = (const lf*)stage;
-      float sum = part[o];
+        for (int it = 0; it < NBP; ++it)
+          if (FULL || (bs + it * 16) * EPR < bch) bsum += bias_piece_sum<T>(bx[sl][it]);
+      });
+  };
+  if (Bp % SAC_UPD_BCH == 0)  // uniform
+    dw_and_bias(std::true_type{});
+  else
+    dw_and_bias(std::false_type{});
+  STAMP(polyak ? 49 : 53);
+  lf* part = upd_partials();
+  put_partials(part, pr, g, c, acc);
+  if (bias_lane) t.red[bn * 17 + bs] = bsum;
+  __syncthreads();  // 2: the four K-quarter partials and the bias lanes are in LDS
 #pragma unroll
-      for (int q = 1; q < KQ; ++q) sum += part[q * (32 * 33) + o];
-      accs[o] = sum;
-    }
+  for (int e = 0; e < EPT; ++e) gel[e] = sum_quarters(part, upd_el(tid + e * UT));
+}
+
+// ---- dW, multi-round tiles: staged through LDS in 512-B row chunks, ns chunks per round; waves run (16x16
+// sub-tile, K-quarter) pairs, chunks in batch order.  A slot's registers are re-issued for the next round as
+// soon as they are in LDS, so round r + 1's loads land under round r's MFMAs.  Barriers: one per slot and one
+// per round, then one on each side of the K-quarter sum (which uses the then free stage): 5 with two slots
+// and one round, 7 per tile.  The sums end in accs, the bias lanes in red.
+template <typename T, int UT, int GS, int MS>
+__device__ __forceinline__ void dw_multi_round(const AS_C EngineDev& E, const UpdGeom<T, UT, MS>& t,
+                                               UpdLoader<T, UT, GS, MS>& ld, bool polyak, bool bias_acc) {
+  typedef UpdGeom<T, UT, MS> Geom;
+  typedef typename MM<T>::Frag Frag;
+  constexpr int KC = Geom::KC, KL = Geom::KL, EPR = Geom::EPR, MAXS = Geom::MAXS;
+  constexpr int KQ = Geom::KQ, NWV = Geom::NWV, PPW = Geom::PPW, BPT = Geom::BPT;
+  const int tid = t.tid, Bp = t.Bp;
+  const int lane = tid & 63, wave = wave_id();
+  const int c = lane & 15, g = lane >> 4;
+  f32x4 acc[PPW];
 #pragma unroll
-    for (int j = 0; j < BPT; ++j) {
-      const int t = tid + j * UT;
-      if (bias_acc && t < 512) red[(t >> 4) * 17 + (t & 15)] = bsum[j];
-    }
-    __syncthreads();
-  }
-  // producer parts a consumer takes (the 512-thread tiles: up to 7, else 3)
-  constexpr int MAXP = UT == 512 ? 7 : 3;
-  float gbx[MAXP];  // staged-row bias: the producer parts' column sums (consumer, tid < 32)
+  for (int j = 0; j < PPW; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  float bsum[BPT];
 #pragma unroll
-  for (int q = 0; q < MAXP; ++q) gbx[q] = 0.f;
-  if (td.kpart) {  // hidden-split layer 0: the batch parts of this tile meet here
-    const uint32_t ep = *GPC(uint32_t, E.sync) + 1u;  // per launch (B and D have their own granules)
-    if (td.kpart >= 2) {
-      AS_G uint64_t* mine = GP(uint64_t, td.part) + (size_t)(td.kpart - 2) * SAC_PART_STRIDE;
+  for (int j = 0; j < BPT; ++j) bsum[j] = 0.f;
+  for (int r0 = 0; r0 < Bp; r0 += t.rstep) {
+    // slot by slot: its pieces -> LDS, the next round's loads into its registers, barrier, its MFMAs --
+    // while the later slots' loads are still landing
+    static_for<MAXS>([&](auto slc) {
+      constexpr int sl = decltype(slc)::value;
+      const int b0 = r0 + sl * SAC_UPD_BCH;
+      if (sl < t.ns && b0 < Bp) {  // uniform
+        const int bch = t.bch(Bp, b0);
+        ld.stage_slot(slc, bch);
+        ld.issue(r0 + t.rstep, slc);
+        __syncthreads();  // per slot: the slot is staged
+        if (r0 == 0 && sl == 0) STAMP(polyak ? 51 : 55);
+        if (bias_acc) {  // bias gradient: this lane's columns of the slot's (scaled) dY rows
 #pragma unroll
-      for (int e = 0; e < EPT; ++e) {
-        const int el = tid + e * UT;
-        const float dw = single ? gel[e] : accs[(el >> 5) * 33 + (el & 31)];
-        const uint64_t x = (uint64_t)__float_as_uint(dw) | ((uint64_t)ep << 32);
-        __hip_atomic_store((uint64_t*)(mine + el), x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-      if (bias_acc && tid < 32) {
-        float gb = 0.f;
-        for (int q = 0; q < 16; ++q) gb += red[tid * 17 + q];
-        const uint64_t x = (uint64_t)__float_as_uint(gb) | ((uint64_t)ep << 32);
-        __hip_atomic_store((uint64_t*)(mine + 1024 + tid), x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-      return;  // uniform: part 1 runs Adam on the sum
-    }
-    // each thread polls all of its 1024 / UT elements' granules of every
-    // producer part in one batch of loads per attempt (one round trip, not one
-    // per element); parts are added in order
-    constexpr int EL = 1024 / UT;
-    static_assert(EL * UT == 1024 && EL <= 4, "granules per thread");
-    const int np = td.nparts - 1;  // producer parts (1..MAXP)
-    const bool pb_here = do_bias && tid < 32;
-    float v[MAXP][EL];
-    for (int it = 0;; ++it) {
-      bool all = true;
-#pragma unroll
-      for (int q = 0; q < MAXP; ++q)
-        if (q < np) {
-#pragma unroll
-          for (int j = 0; j < EL; ++j) {
-            const uint64_t x = __hip_atomic_load(td.part + (size_t)q * SAC_PART_STRIDE + tid + j * UT,
-                                                 __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            all = all && (uint32_t)(x >> 32) == ep;
-            v[q][j] = __uint_as_float((uint32_t)x);
-          }
-          if (pb_here) {
-            const uint64_t x = __hip_atomic_load(td.part + (size_t)q * SAC_PART_STRIDE + 1024 + tid,
-                                                 __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            all = all && (uint32_t)(x >> 32) == ep;
-            gbx[q] = __uint_as_float((uint32_t)x);
+          for (int j = 0; j < BPT; ++j) {
+            const int bt = tid + j * UT, bn = bt >> 4, bs = bt & 15;
+            if (bt < 512)  // 16-B LDS reads: lane bs takes the row's 16-B pieces bs, bs + 16, ...
+              for (int bc = bs * EPR; bc < bch; bc += 16 * EPR)
+                bsum[j] += bias_piece_sum<T>(*(const AS_L Frag*)(t.stage + sl * t.slot_el + bn * t.lds_row + bc));
           }
         }
-      if (all) break;
-      if (it > E.spin_limit) {  // a producer part never ran: flag the error, do not hang
-        __hip_atomic_store((uint32_t*)GP(uint32_t, E.sync) + 1 /* SYNC_TIMEOUT */, 1u, __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
-        break;
+#pragma unroll
+        for (int j = 0; j < PPW; ++j) {
+          const UpdPair pr = upd_pair(wave + j * NWV);
+          const AS_L T* arow = t.stage + sl * t.slot_el + (pr.sn + c) * t.lds_row + g * KL;
+          const AS_L T* brow = t.stage + sl * t.slot_el + (32 + pr.sk + c) * t.lds_row + g * KL;
+          for (int ch = pr.kq; ch < bch / KC; ch += KQ) {
+            const Frag a = *(const AS_L Frag*)(arow + ch * KC);
+            const Frag b = *(const AS_L Frag*)(brow + ch * KC);
+            MM<T>::mma(acc[j], a, b);
+          }
+        }
       }
-      __builtin_amdgcn_s_sleep(1);
-    }
-#pragma unroll
-    for (int j = 0; j < EL; ++j) {
-      const int el = tid + j * UT, o = (el >> 5) * 33 + (el & 31);
-      float sum = single ? gel[j] : accs[o];
-#pragma unroll
-      for (int q = 0; q < MAXP; ++q)
-        if (q < np) sum += v[q][j];
-      if (single)
-        gel[j] = sum;
-      else
-        accs[o] = sum;
-    }
-    if (!single) __syncthreads();  // uniform
+    });
+    ld.seeds_to_lds(r0 + t.rstep);  // every thread's reads of this round's seeds are behind a slot barrier
+    __syncthreads();  // per round: the stage is refilled by the next round
   }
-  STAMP(polyak ? 50 : 54);
-  // ---- 3. elements: Adam + Polyak on the masters; new values -> LDS
-  const float w1 = (float)(1.0 - (double)E.beta1), b2 = E.beta2, w2 = (float)(1.0 - (double)E.beta2);
-  const float eps = E.adam_eps, tau = E.tau, omt = (float)(1.0 - (double)E.tau);
-  float pn[EPT], tn[EPT];
+  STAMP(polyak ? 49 : 53);
+  lf* part = (lf*)t.stage;  // K-quarter partials -> the (free) stage area
+  // (compile-time j: with a run-time pair index here the 512-thread fp32 kernel takes 86 VGPRs, not 84)
+  static_for<PPW>([&](auto jc) {
+    constexpr int j = decltype(jc)::value;
+    put_partials(part, upd_pair(wave + j * NWV), g, c, acc[j]);
+  });
+  __syncthreads();  // the four K-quarter partials are in LDS
+  for (int el = tid; el < 1024; el += UT) t.accs[upd_el(el)] = sum_quarters(part, upd_el(el));
 #pragma unroll
-  for (int e = 0; e < EPT; ++e) {
+  for (int j = 0; j < BPT; ++j) {
+    const int bt = tid + j * UT;
+    if (bias_acc && bt < 512) t.red[(bt >> 4) * 17 + (bt & 15)] = bsum[j];
+  }
+  __syncthreads();  // accs and red are complete
+}
+
+// ---- the batch-part hand-off (hidden-split layer 0, and large batches off the split): producer parts
+// 2..nparts publish their partial dW, and a seeded tile's bias column sums, as granules of this launch's
+// epoch; part 1 adds them to its own in part order and runs Adam on the sum
+template <typename T, int UT, int MS>
+__device__ __forceinline__ void parts_publish(const UpdGeom<T, UT, MS>& t, const AS_C TileDesc* td, bool bias_acc,
+                                              bool single, const float (&gel)[1024 / UT], uint32_t ep) {
+  const int tid = t.tid;
+  AS_G uint64_t* mine = GP(uint64_t, td->part) + (size_t)(td->kpart - 2) * SAC_PART_STRIDE;
+#pragma unroll
+  for (int e = 0; e < 1024 / UT; ++e) {
     const int el = tid + e * UT;
-    pn[e] = 0.f;
-    tn[e] = 0.f;
-    if (ok[e]) {
-      const float dw = single ? gel[e] : accs[(el >> 5) * 33 + (el & 31)];
-      pn[e] = adam_elem(p[e], m[e], v[e], dw, w1, b2, w2, bc2s, eps, neg_step);
-      W[idx[e]] = p[e];
-      Wm[idx[e]] = m[e];
-      Wv[idx[e]] = v[e];
-      if (polyak) {
-        tn[e] = tau * pn[e] + omt * tp[e];
-        tW[idx[e]] = tn[e];
+    gran_put(mine + el, single ? gel[e] : t.accs[upd_el(el)], ep);
+  }
+  if (bias_acc && tid < 32) gran_put(mine + 1024 + tid, bias_lane_sum(t.red, tid), ep);
+}
+// each thread polls all of its 1024 / UT elements' granules of every producer
+// part in one batch of loads per attempt (one round trip, not one per element);
+// parts are added in order.  gbx: the producer parts' bias column sums (pb_here)
+template <typename T, int UT, int MS>
+__device__ __forceinline__ void parts_collect(const AS_C EngineDev& E, const UpdGeom<T, UT, MS>& t,
+                                              const AS_C TileDesc* td, bool pb_here, bool single,
+                                              float (&gel)[1024 / UT], float (&gbx)[UpdState<UT>::MAXP], uint32_t ep) {
+  constexpr int EL = 1024 / UT, MAXP = UpdState<UT>::MAXP;
+  static_assert(EL * UT == 1024 && EL <= 4, "granules per thread");
+  const int tid = t.tid;
+  const int np = td->nparts - 1;  // producer parts (1..MAXP)
+  float v[MAXP][EL];
+  for (int it = 0;; ++it) {
+    bool all = true;
+#pragma unroll
+    for (int q = 0; q < MAXP; ++q)
+      if (q < np) {
+#pragma unroll
+        for (int j = 0; j < EL; ++j) {
+          const uint64_t x = __hip_atomic_load(td->part + (size_t)q * SAC_PART_STRIDE + tid + j * UT,
+                                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          all = all && gran_fresh(x, ep);
+          v[q][j] = gran_value(x);
+        }
+        if (pb_here) {
+          const uint64_t x = __hip_atomic_load(td->part + (size_t)q * SAC_PART_STRIDE + 1024 + tid,
+                                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          all = all && gran_fresh(x, ep);
+          gbx[q] = gran_value(x);
+        }
       }
+    if (all) break;
+    if (it > E.spin_limit) {  // a producer part never ran
+      sync_timeout(E);
+      break;
     }
+    __builtin_amdgcn_s_sleep(1);
   }
-  if (!single) __syncthreads();  // every read of accs done (uniform; a single-round tile reads none)
 #pragma unroll
-  for (int e = 0; e < EPT; ++e) {
-    const int el = tid + e * UT;
-    accs[(el >> 5) * 33 + (el & 31)] = pn[e];  // padding elements: 0, as packed
-    if (polyak) tgts[(el >> 5) * 33 + (el & 31)] = tn[e];
-  }
-  if (do_bias && tid < 32 && td.n0 + tid < td.N) {
-    float gb = 0.f;
-    for (int q = 0; q < 16; ++q) gb += red[tid * 17 + q];
-    if (td.kpart) {  // the other batch parts' sums, in part order
+  for (int j = 0; j < EL; ++j) {
+    const int o = upd_el(tid + j * UT);
+    float sum = single ? gel[j] : t.accs[o];
 #pragma unroll
-      for (int q = 0; q < MAXP; ++q)
-        if (q < td.nparts - 1) gb += gbx[q];
-    }
-    const float pbn = adam_elem(pb, mb, vb, gb, w1, b2, w2, bc2s, eps, neg_step);
-    GP(float, td.b)[td.n0 + tid] = pb;
-    GP(float, td.bm)[td.n0 + tid] = mb;
-    GP(float, td.bv)[td.n0 + tid] = vb;
-    if (polyak) GP(float, td.tb)[td.n0 + tid] = tau * pbn + omt * tbv;  // read by the next step's launch only
+    for (int q = 0; q < MAXP; ++q)
+      if (q < np) sum += v[q][j];
+    if (single)
+      gel[j] = sum;
+    else
+      t.accs[o] = sum;
   }
-  __syncthreads();
-  // ---- packed copies as 16-B pieces: Wc / tWc rows n (EPR consecutive k), WTc rows k
+}
+
+// ---- the packed compute copies from the new values in LDS, as 16-B pieces: Wc /
+// tWc rows n (EPR consecutive k), WTc rows k (plain stores: the reader is the next launch)
+template <typename T, int UT>
+__device__ __forceinline__ void store_packed(const AS_C TileDesc* td, const lf* accs, const lf* tgts, bool polyak,
+                                             int tid) {
+  constexpr int EPR = 16 / sizeof(T);
   constexpr int PPR = 32 / EPR;  // pieces per 32-element tile row
   for (int mat = 0; mat < (polyak ? 3 : 2); ++mat) {  // uniform: one buffer descriptor per matrix
-    const void* base = mat == 0 ? td.Wc : mat == 1 ? td.WTc : td.tWc;
+    const void* base = mat == 0 ? td->Wc : mat == 1 ? td->WTc : td->tWc;
     for (int i = tid; i < 32 * PPR; i += UT) {
       const int row = i / PPR, pc = i % PPR;
       T vv[EPR];
@@ -1317,16 +1362,82 @@ __device__ __forceinline__ void dw_adam_tile(const AS_C EngineDev& E, const Tile
       if (mat == 1) {  // W^T: row k = k0 + row, columns n = n0 + pc * EPR + j
 #pragma unroll
         for (int j = 0; j < EPR; ++j) vv[j] = MM<T>::cvt(accs[(pc * EPR + j) * 33 + row]);
-        off = packed_off<T>(td.k0 + row, td.n0 + pc * EPR, td.Np);
+        off = packed_off<T>(td->k0 + row, td->n0 + pc * EPR, td->Np);
       } else {  // W or target W: row n = n0 + row, columns k = k0 + pc * EPR + j
         const lf* srcm = mat == 0 ? accs : tgts;
 #pragma unroll
         for (int j = 0; j < EPR; ++j) vv[j] = MM<T>::cvt(srcm[row * 33 + pc * EPR + j]);
-        off = packed_off<T>(td.n0 + row, td.k0 + pc * EPR, td.Kp);
+        off = packed_off<T>(td->n0 + row, td->k0 + pc * EPR, td->Kp);
       }
       coh_store16<false>(base, (uint32_t)(off * sizeof(T)), *(const u32x4*)vv);
     }
   }
+}
+
+// ---- the tile.  Block barriers, by the stage that owns them (every one is in this body or in the path's
+// dW function):
+//   single-round (3): dw_single_round 2 (slots staged; partials + bias lanes in LDS), then the one before
+//     store_packed;
+//   multi-round (7 with two slots and one round): dw_multi_round 5 (one per slot, one per round, one on each
+//     side of the K-quarter sum), "reads of accs done" inside the Adam stage, the one before store_packed;
+//     plus one after round 0's seeds with LDS seeds (fp32, several rounds) and one after parts_collect on a
+//     consumer part.
+template <typename T, int UT, int GS = 1, int MS = 2>
+__device__ __forceinline__ void dw_adam_tile(const AS_C EngineDev& E, const TileDesc* tdp_, bool polyak, int par,
+                                             int par_x, lf* lds) {
+  constexpr int EPT = 1024 / UT;
+  const AS_C TileDesc* td = (const AS_C TileDesc*)tdp_;  // scalar loads
+  STAMP(polyak ? 48 : 52);
+  // ---- 1. geometry and loads: the first round of staged operands, then element
+  // state + bias state, all before the first wait (one round trip)
+  const UpdGeom<T, UT, MS> t(E, td, lds);
+  const int tid = t.tid;
+  // this step's Adam scalars (written by phase A)
+  const float neg_step = GPC(float, E.adam_sc)[par * 6 + td->opt * 2];
+  const float bc2s = GPC(float, E.adam_sc)[par * 6 + td->opt * 2 + 1];
+  UpdLoader<T, UT, GS, MS> ld(t, td, par_x);
+  // round 0: every slot's seeds, then the pieces (the seeds' wait below includes no piece)
+  static_for<MS>([&](auto sl) { ld.issue_seeds(0, sl); });
+  static_for<MS>([&](auto sl) { ld.issue(0, sl, false); });
+  UpdState<UT> st;
+  st.load(td, polyak, tid);
+  // round 0's seeds -> LDS: issued first, so this waits for them alone, after
+  // every load of the tile (operands, element state, bias) is in flight
+  ld.seeds_to_lds(0);
+  if (ld.lseeds) __syncthreads();  // uniform; LDS seeds: several rounds, so never a single-round tile
+  // ---- 2. dW = dY^T X over the batch -> gel (single-round) or accs (multi-round); bias lanes -> red
+  bool single = false;
+  if constexpr (UT == SAC_UPD_THREADS) single = t.Bp <= t.rstep;  // uniform
+  float gel[EPT];  // single-round: the elements' dW (K-quarters summed, then the batch parts)
+  if (single) {
+    if constexpr (UT == SAC_UPD_THREADS) dw_single_round(E, t, ld, polyak, st.bias_acc, gel);
+  } else {
+    dw_multi_round(E, t, ld, polyak, st.bias_acc);
+  }
+  // ---- 3. hidden-split layer 0 and large batches: the batch parts of this tile meet here
+  float gbx[UpdState<UT>::MAXP];  // the producer parts' bias column sums (consumer, tid < 32)
+#pragma unroll
+  for (int q = 0; q < UpdState<UT>::MAXP; ++q) gbx[q] = 0.f;
+  if (td->kpart) {
+    const uint32_t ep = *GPC(uint32_t, E.sync) + 1u;  // per launch (B and D have their own granules)
+    if (td->kpart >= 2) {
+      parts_publish(t, td, st.bias_acc, single, gel, ep);
+      return;  // uniform: part 1 runs Adam on the sum
+    }
+    parts_collect(E, t, td, st.do_bias && tid < 32, single, gel, gbx, ep);
+    if (!single) __syncthreads();  // uniform: the summed accs
+  }
+  STAMP(polyak ? 50 : 54);
+  // ---- 4. Adam + Polyak on the masters; new values -> LDS
+  const AdamHyp hyp = {(float)(1.0 - (double)E.beta1), E.beta2, (float)(1.0 - (double)E.beta2), bc2s, E.adam_eps,
+                       neg_step, E.tau, (float)(1.0 - (double)E.tau)};
+  st.adam_elements(hyp, polyak, single, gel, t.accs, tid);
+  if (!single) __syncthreads();  // every read of accs done (uniform; a single-round tile reads none)
+  st.new_values_to_lds(t.accs, t.tgts, polyak, tid);
+  st.adam_bias(td, hyp, polyak, t.red, gbx, tid);
+  __syncthreads();  // the new values are in LDS
+  // ---- 5. packed copies
+  store_packed<T, UT>(td, t.accs, t.tgts, polyak, tid);
 }
 
 // a tile with summed dY parts (hidden-split layer 0) runs its own instance
@@ -1418,8 +1529,6 @@ __device__ __forceinline__ void alpha_and_losses(const AS_C EngineDev& E, int pa
 // still bounded (E.spin_limit) and set E.sync[1] on a timeout, which the host
 // API turns into an error (sac_engine_read_status, SacEngine._poll_status).
 enum HandKind { HK_PI = 0, HK_T1 = 1, HK_T2 = 2, HK_C1 = 3, HK_C2 = 4, HK_COUNT = 5 };
-// SYNC_STAGED (u64 at words 4-5): step whose phase A last used a staged batch record
-enum SyncWord { SYNC_EPOCH = 0, SYNC_TIMEOUT = 1, SYNC_STAGED = 4, SYNC_CDONE = 64, SYNC_FLAGS = 128 };
 #define SAC_HAND_STRIDE 576  // floats per (kind, row tile) payload: >= SAC_ROWS * (act_dim + 1)
 
 __device__ __forceinline__ AS_G uint32_t* hand_flag(const AS_C EngineDev& E, int kind, int rbi) {
@@ -1488,25 +1597,21 @@ enum GranKind { G_Q1T = 0, G_Q2T = 1, G_LP = 2, G_C1 = 3, G_C2 = 4, G_PI = 5, G_
 __device__ __forceinline__ AS_G uint64_t* gran_at(const AS_C EngineDev& E, int kind, int rbi) {
   return GP(uint64_t, E.gran) + (size_t)(kind * E.nrt + rbi) * E.gstride;
 }
-__device__ __forceinline__ void gran_put(AS_G uint64_t* g, float v, uint32_t ep) {
-  const uint64_t x = (uint64_t)__float_as_uint(v) | ((uint64_t)ep << 32);
-  __hip_atomic_store((uint64_t*)g, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
+// (gran_put, gran_fresh, gran_value and sync_timeout: "granule primitives" above)
 // one lane: the granule's value once it carries epoch ep (bounded spin; a
 // timeout sets the engine's error flag, see sac_engine_check)
 __device__ __forceinline__ float gran_get(const AS_C EngineDev& E, const AS_G uint64_t* g, uint32_t ep) {
   uint64_t x = 0;
   for (int it = 0;; ++it) {
     x = __hip_atomic_load((uint64_t*)g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if ((uint32_t)(x >> 32) == ep) break;
+    if (gran_fresh(x, ep)) break;
     if (it > E.spin_limit) {
-      __hip_atomic_store((uint32_t*)GP(uint32_t, E.sync) + SYNC_TIMEOUT, 1u, __ATOMIC_RELAXED,
-                         __HIP_MEMORY_SCOPE_AGENT);
+      sync_timeout(E);
       break;
     }
     __builtin_amdgcn_s_sleep(1);
   }
-  return __uint_as_float((uint32_t)x);
+  return gran_value(x);
 }
 
 // one lane: N granules polled together (every load of a poll in flight at once:
@@ -1520,7 +1625,7 @@ template <int N>
 __device__ __forceinline__ bool gran_ok(const uint64_t (&x)[N], uint32_t ep) {
   bool all = true;
 #pragma unroll
-  for (int i = 0; i < N; ++i) all = all && (uint32_t)(x[i] >> 32) == ep;
+  for (int i = 0; i < N; ++i) all = all && gran_fresh(x[i], ep);
   return all;
 }
 template <int N>

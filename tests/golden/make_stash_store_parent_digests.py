@@ -6,37 +6,21 @@ the GEMM epilogues' registers (csrc/sac_split.h, store_acc_T).
     SAC_ENGINE_LIB=/path/to/parent/libsac_engine.so \
         python tests/golden/make_stash_store_parent_digests.py --parent <commit>
 
-Needs the MI355X.  SAC_ENGINE_LIB must name a library built from the parent
-commit (tools/build_rev.sh; the script refuses to run without it, so that the
-file is never made from the tree's own build); --parent is recorded in the
-file.  The change moves no float operation and every stash element receives
-the value store_T gave it, so tests/test_gpu_stash_stores.py recomputes every
-digest on the build under test and asks for equality.
-
-Each case builds tests/_gpu.py::build_engine's engine and synthetic replay
-(seed 3), draws indices and eps for two steps from numpy's default_rng(17), runs
-them one by one and hashes the bytes of every array of state_tensors() and of
-the stats buffer (losses, y, log pi).
+How the file is made and what a digest covers: tests/golden/_parent_digests.py.
+The change moves no float operation and every stash element receives the value
+store_T gave it, so tests/test_gpu_stash_stores.py recomputes every digest on
+the build under test and asks for equality.
 """
 from __future__ import annotations
 
-import argparse
-import contextlib
-import hashlib
-import json
 import os
-import sys
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(os.path.dirname(HERE))
-for p in (ROOT, os.path.join(ROOT, "soft-actor-critic_amd"), os.path.join(ROOT, "tests")):
-    if p not in sys.path:
-        sys.path.insert(0, p)
+import _parent_digests as P
+from _parent_digests import STEPS, render  # noqa: F401  (the test reads them from here)
 
-import _dead_units as D  # noqa: E402
+import _dead_units as D  # noqa: E402  (tests/ is on the path once _parent_digests is imported)
 
-OUT = os.path.join(HERE, "stash_store_parent_digests.json")
-STEPS = 2
+OUT = os.path.join(P.HERE, "stash_store_parent_digests.json")
 
 
 def _shape(obs, act, batch, **extra):
@@ -61,44 +45,11 @@ CASES = {
 
 def digests(name):
     """{array name: sha256 hex} of case `name` on the loaded engine library."""
-    import numpy as np
-    import torch
-    from _gpu import assert_layout, build_engine
-
     c, sp, precision = CASES[name]
-    with D.dead_nets(sp) if sp else contextlib.nullcontext():
-        eng, rb, cc = build_engine(dict(c, name="stash_store_" + name), precision, 3, torch.device("cuda", 0))
-    assert_layout(eng, "split")
-    B, A = cc["batch"], cc["act"]
-    g = np.random.default_rng(17)
-    idx = g.integers(0, cc["capacity"], (STEPS, B)).astype(np.int32)
-    eps = g.standard_normal((STEPS, 2, B, A)).astype(np.float32)
-    for k in range(STEPS):
-        eng.train(rb, 1, indices=torch.from_numpy(idx[k:k + 1]), eps=torch.from_numpy(eps[k:k + 1]))
-    torch.cuda.synchronize()
-    eng.check()
-    if sp:
-        D.assert_engine_rows_zero(eng, sp, name)
-    arrays = dict(eng.state_tensors(), stats=eng.stats)
-    return {k: hashlib.sha256(v.detach().cpu().contiguous().numpy().tobytes()).hexdigest()
-            for k, v in sorted(arrays.items())}
-
-
-def render(doc):
-    return json.dumps(doc, indent=1, sort_keys=True) + "\n"
-
-
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--parent", required=True, help="the commit the library named by SAC_ENGINE_LIB was built from")
-    args = ap.parse_args()
-    if not os.environ.get("SAC_ENGINE_LIB"):
-        sys.exit("SAC_ENGINE_LIB must name a library built from the parent commit")
-    doc = {"parent": args.parent, "steps": STEPS, "cases": {name: digests(name) for name in CASES}}
-    with open(OUT, "w") as f:
-        f.write(render(doc))
-    print(f"wrote {OUT}: {len(CASES)} cases, {sum(len(v) for v in doc['cases'].values())} digests")
+    return P.state_digests(dict(c, name="stash_store_" + name), precision, "split",
+                           nets=D.dead_nets(sp) if sp else None,
+                           check=(lambda eng: D.assert_engine_rows_zero(eng, sp, name)) if sp else None)
 
 
 if __name__ == "__main__":
-    main()
+    P.main(OUT, CASES, digests)
