@@ -199,6 +199,41 @@ int sac_q_values_replay(sac_engine *e, const sac_replay *rb, int64_t first_slot,
 int sac_replay_push(const sac_replay *rb, const float *rows, int64_t n,
                     int64_t size_host, int64_t pos_host, void *stream);
 
+/* ---- n-step returns (train.n_step) ---------------------------
+ * `stage` is a replay table of capacity exactly n * num_envs, with rb's obs_dim
+ * and act_dim, that holds the last n vector steps' one-step rows (o, a, r, o',
+ * d) -- d = terminated | truncated, as sac_rollout_step and sac_replay_push
+ * store them.  `newest` is the staging slot of environment 0's row of the newest
+ * vector step; the row of environment i at age a (0 = newest) is slot (newest -
+ * a * num_envs + i) mod (n * num_envs), and the window scanned is ages n - 1
+ * down to 0, i.e. window steps j = 0 (oldest) .. n - 1.
+ *
+ * One launch writes num_envs n-step rows (o_0, a_0, R, o'_{k-1}, d_{k-1}) into
+ * rb at slots (pos_host + i) % capacity: k is the smallest j + 1 with d_j = 1,
+ * or n if there is none, and R = gpow[0] r_0 + gpow[1] r_1 + ... + gpow[k-1]
+ * r_{k-1}, accumulated in float64 in that order starting from the first
+ * product (so n = 1 copies every reward bit for bit, -0.0 included), without
+ * fused multiply-adds, and rounded to fp32 once.  It also writes rb->state =
+ * {min(capacity, size_host + num_envs), (pos_host + num_envs) % capacity,
+ * generation + 1}, as sac_replay_push and sac_rollout_step do.  A window an
+ * episode end closes never bootstraps (its done is 1) and an open one spans
+ * exactly n steps, so the rows train as ordinary replay rows on an engine
+ * created with gamma = gpow[n].
+ *
+ * gpow_host[0..n-1] (host memory, gpow[0] = 1, gpow[j] = gpow[j-1] * gamma) is
+ * copied into the kernel arguments by value: the call keeps no host state, is
+ * asynchronous on `stream` and can be captured.  Every argument is checked
+ * before any HIP call; SAC_E_INVALID for a null table or field, n outside
+ * 1..SAC_NSTEP_MAX, num_envs < 1, a staging capacity other than n * num_envs,
+ * differing dims, num_envs > rb->capacity, newest / size_host / pos_host out of
+ * range, and stage and rb the same table.  Both replay layouts work, for stage
+ * and rb independently.
+ * Replaces: nothing in the reference (one-step targets only, agent.py:195-211). */
+#define SAC_NSTEP_MAX 8
+int sac_replay_emit_nstep(const sac_replay *stage, const sac_replay *rb, int32_t n, int32_t num_envs,
+                          int64_t newest, const double *gpow_host, int64_t size_host, int64_t pos_host,
+                          void *stream);
+
 /* Gather rows by LOGICAL index into SoA outputs (s[B][obs], a[B][act], r[B],
  * s2[B][obs], d[B]).  Replaces: ReplayBuffer.sample + SAC.sample_batch's
  * stacking (replay_buffer.py:32-39, agent.py:166-193). */

@@ -40,6 +40,7 @@
 #include "sac_wide.h"
 #include "sac_pairs.h"
 #include "sac_envs.h"
+#include "sac_nstep.h"
 #include "sac_plan.h"
 
 // ============================================================================ params / replay
@@ -1152,6 +1153,47 @@ int sac_replay_push(const sac_replay* rb, const float* rows, int64_t n, int64_t 
   const int64_t total = (n - skip) * (2 * rb->obs_dim + rb->act_dim + 2);
   const int blocks = (int)std::min<int64_t>(4096, (total + 255) / 256);
   replay_push_kernel<<<blocks, 256, 0, (hipStream_t)stream>>>(*rb, rows, n, skip, pos_host, new_size, new_pos);
+  HIPCHK(hipGetLastError());
+  return SAC_OK;
+}
+
+static bool replay_fields(const sac_replay* rb) {
+  return rb && rb->obs && rb->act && rb->rew && rb->next_obs && rb->done;
+}
+
+int sac_replay_emit_nstep(const sac_replay* stage, const sac_replay* rb, int32_t n, int32_t num_envs, int64_t newest,
+                          const double* gpow_host, int64_t size_host, int64_t pos_host, void* stream) {
+  if (!replay_fields(stage)) return fail(SAC_E_INVALID, "emit_nstep: null staging table or field");
+  if (!replay_fields(rb) || !rb->state) return fail(SAC_E_INVALID, "emit_nstep: null replay buffer, field or state");
+  if (!gpow_host) return fail(SAC_E_INVALID, "emit_nstep: null discount powers");
+  if (n < 1 || n > SAC_NSTEP_MAX)
+    return fail(SAC_E_INVALID, "emit_nstep: n (" + std::to_string(n) + ") outside 1.." + std::to_string(SAC_NSTEP_MAX));
+  if (num_envs < 1) return fail(SAC_E_INVALID, "emit_nstep: num_envs >= 1");
+  const int64_t scap = (int64_t)n * num_envs, cap = rb->capacity;
+  if (stage->capacity != scap)
+    return fail(SAC_E_INVALID, "emit_nstep: the staging table holds " + std::to_string(stage->capacity) +
+                                   " rows, not n * num_envs = " + std::to_string(scap));
+  if (stage->obs_dim != rb->obs_dim || stage->act_dim != rb->act_dim || rb->obs_dim < 1 || rb->act_dim < 1)
+    return fail(SAC_E_INVALID, "emit_nstep: staging dims do not match the replay buffer's");
+  for (const sac_replay* t : {stage, rb})
+    if (t->row_stride < 0 || (t->row_stride && t->row_stride < std::max(t->obs_dim, t->act_dim)))
+      return fail(SAC_E_INVALID, "emit_nstep: record stride below the field width");
+  if (cap < 1 || num_envs > cap)
+    return fail(SAC_E_INVALID, "emit_nstep: num_envs (" + std::to_string(num_envs) + ") exceeds the replay capacity (" +
+                                   std::to_string(cap) + ")");
+  if (newest < 0 || newest >= scap)
+    return fail(SAC_E_INVALID, "emit_nstep: newest (" + std::to_string(newest) + ") outside the staging table");
+  if (size_host < 0 || size_host > cap || pos_host < 0 || pos_host >= cap)
+    return fail(SAC_E_INVALID, "emit_nstep: replay (size, pos) out of range");
+  if (stage == rb || stage->obs == rb->obs || stage->rew == rb->rew)
+    return fail(SAC_E_INVALID, "emit_nstep: the staging table and the replay buffer are the same table");
+  NStepPowers gp{};
+  for (int j = 0; j < n; ++j) gp.g[j] = gpow_host[j];
+  const int64_t new_size = std::min(cap, size_host + (int64_t)num_envs);
+  const int64_t new_pos = (pos_host + num_envs) % cap;
+  const int blocks = (num_envs + 3) / 4;  // one wave per environment row
+  sac_replay_emit_nstep_kernel<<<blocks, 256, 0, (hipStream_t)stream>>>(*stage, *rb, n, num_envs, newest, gp, pos_host,
+                                                                        new_size, new_pos);
   HIPCHK(hipGetLastError());
   return SAC_OK;
 }

@@ -12,6 +12,7 @@
 //                        SAC.sample_batch stacking     sac/agent.py:166-193)
 //   replay_sample        the index draw of random.sample (replay_buffer.py:39)
 //   replay_sample_gather sampler + gather in one kernel
+//   replay_emit_nstep    the n-step rows of the last n vector steps, staging table -> replay ring (train.n_step)
 //   train_step           SAC.training_step            (sac/agent.py:302-327)
 //   train_graph          a loop of training_step      (sac/agent.py:361-364), hipGraph-replayed
 //   policy_act           SAC.select_action            (sac/agent.py:149-156; models.py:79-92)
@@ -63,6 +64,7 @@ struct EngineApi {
   decltype(&sac_replay_gather) replay_gather = nullptr;
   decltype(&sac_replay_sample_indices) replay_sample_indices = nullptr;
   decltype(&sac_replay_sample_gather) replay_sample_gather = nullptr;
+  decltype(&sac_replay_emit_nstep) replay_emit_nstep = nullptr;
   decltype(&sac_engine_train) engine_train = nullptr;
   decltype(&sac_engine_train_graph) engine_train_graph = nullptr;
   decltype(&sac_policy_act) policy_act = nullptr;
@@ -95,6 +97,7 @@ void bind_engine_library(c10::string_view path_) {
   resolve(h, "sac_replay_gather", a.replay_gather);
   resolve(h, "sac_replay_sample_indices", a.replay_sample_indices);
   resolve(h, "sac_replay_sample_gather", a.replay_sample_gather);
+  resolve(h, "sac_replay_emit_nstep", a.replay_emit_nstep);
   resolve(h, "sac_engine_train", a.engine_train);
   resolve(h, "sac_engine_train_graph", a.engine_train_graph);
   resolve(h, "sac_policy_act", a.policy_act);
@@ -237,6 +240,22 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tenso
                                     out[1].data_ptr<float>(), out[2].data_ptr<float>(), out[3].data_ptr<float>(),
                                     out[4].data_ptr<float>(), stream_of(storage)));
   return {idx, out[0], out[1], out[2], out[3], out[4]};
+}
+
+// The n-step rows of the last n vector steps: reads the staging table, writes num_envs rows and the state
+// words of the destination (include/sac_engine.h sac_replay_emit_nstep).  gpow = [1, g, g^2, ...], at least n long.
+void replay_emit_nstep(at::Tensor& storage, at::Tensor& state, at::IntArrayRef layout, const at::Tensor& stage_storage,
+                       const at::Tensor& stage_state, at::IntArrayRef stage_layout, int64_t n, int64_t num_envs,
+                       int64_t newest, at::ArrayRef<double> gpow, int64_t size, int64_t pos) {
+  Replay r = make_replay(storage, state, layout);
+  Replay st = make_replay(stage_storage, stage_state, stage_layout);
+  TORCH_CHECK(stage_storage.device() == storage.device(), "staging table and replay on different devices");
+  TORCH_CHECK(n >= 1 && n <= SAC_NSTEP_MAX, "n must be in [1, ", SAC_NSTEP_MAX, "]");
+  TORCH_CHECK(num_envs >= 1 && num_envs <= INT32_MAX, "num_envs must be >= 1");
+  TORCH_CHECK(static_cast<int64_t>(gpow.size()) >= n, "gpow must hold at least n discount powers");
+  Guard g(storage.device());
+  check_rc(api().replay_emit_nstep(&st.d, &r.d, static_cast<int32_t>(n), static_cast<int32_t>(num_envs), newest,
+                                   gpow.data(), size, pos, stream_of(storage)));
 }
 
 // ---------------------------------------------------------------- learner
@@ -532,6 +551,9 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tenso
   return {at::empty({batch}, storage.options().dtype(at::kInt)), o[0], o[1], o[2], o[3], o[4]};
 }
 
+void replay_emit_nstep_meta(at::Tensor&, at::Tensor&, at::IntArrayRef, const at::Tensor&, const at::Tensor&,
+                            at::IntArrayRef, int64_t, int64_t, int64_t, at::ArrayRef<double>, int64_t, int64_t) {}
+
 void train_step_meta(int64_t, at::TensorList, const at::Tensor&, const at::Tensor&, at::IntArrayRef, int64_t,
                      const std::optional<at::Tensor>&, const std::optional<at::Tensor>&) {}
 
@@ -590,6 +612,9 @@ TORCH_LIBRARY(sac_hip, m) {
   m.def("replay_sample(Tensor storage, Tensor state, int[] layout, int batch, int seed, int step) -> Tensor");
   m.def("replay_sample_gather(Tensor storage, Tensor state, int[] layout, int batch, int seed, int step) "
         "-> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
+  m.def("replay_emit_nstep(Tensor(a!) storage, Tensor(b!) state, int[] layout, Tensor stage_storage, "
+        "Tensor stage_state, int[] stage_layout, int n, int num_envs, int newest, float[] gpow, int size, int pos) "
+        "-> ()");
   m.def("train_step(int engine, Tensor(a!)[] state, Tensor storage, Tensor replay_state, int[] layout, "
         "int n_steps, Tensor? indices=None, Tensor? eps=None) -> ()");
   m.def("train_graph(int engine, Tensor(a!)[] state, Tensor storage, Tensor replay_state, int[] layout, "
@@ -620,6 +645,7 @@ TORCH_LIBRARY_IMPL(sac_hip, CUDA, m) {
   m.impl("replay_gather", &replay_gather);
   m.impl("replay_sample", &replay_sample);
   m.impl("replay_sample_gather", &replay_sample_gather);
+  m.impl("replay_emit_nstep", &replay_emit_nstep);
   m.impl("train_step", &train_step);
   m.impl("train_graph", &train_graph);
   m.impl("policy_act", &policy_act);
@@ -638,6 +664,7 @@ TORCH_LIBRARY_IMPL(sac_hip, Meta, m) {
   m.impl("replay_gather", &replay_gather_meta);
   m.impl("replay_sample", &replay_sample_meta);
   m.impl("replay_sample_gather", &replay_sample_gather_meta);
+  m.impl("replay_emit_nstep", &replay_emit_nstep_meta);
   m.impl("train_step", &train_step_meta);
   m.impl("train_graph", &train_graph_meta);
   m.impl("policy_act", &policy_act_meta);

@@ -12,6 +12,7 @@ from typing import Optional, Sequence
 
 import torch
 
+NSTEP_MAX = 8  # largest train.n_step (SAC_NSTEP_MAX)
 MAX_LAYERS = 8  # slots of sac_engine_config.q_dims / pi_dims (SAC_MAX_LAYERS): the struct's layout
 DEV_LAYERS = 6  # Linear layers per network the library takes (SAC_DEV_LAYERS): 1..5 hidden layers
 PREC_FP32, PREC_BF16 = 0, 1
@@ -123,6 +124,9 @@ SIGNATURES = {
                                            ctypes.c_void_p]),
     "sac_replay_push": (ctypes.c_int, [ctypes.POINTER(ReplayDesc), ctypes.c_void_p, ctypes.c_int64,
                                        ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p]),
+    "sac_replay_emit_nstep": (ctypes.c_int, [ctypes.POINTER(ReplayDesc), ctypes.POINTER(ReplayDesc), ctypes.c_int32,
+                                             ctypes.c_int32, ctypes.c_int64, ctypes.POINTER(ctypes.c_double),
+                                             ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p]),
     "sac_replay_gather": (ctypes.c_int, [ctypes.POINTER(ReplayDesc), ctypes.c_void_p, ctypes.c_int32]
                           + [ctypes.c_void_p] * 6),
     "sac_replay_sample_indices": (ctypes.c_int, [ctypes.POINTER(ReplayDesc), ctypes.c_int32, ctypes.c_uint64,
@@ -189,9 +193,9 @@ def ops_library_path() -> str:
 def ops():
     """``torch.ops.sac_hip``: the PyTorch custom ops over the C ABI
     (csrc/sac_torch_ops.cpp: replay_push, replay_gather, replay_sample,
-    replay_sample_gather, train_step, train_graph, policy_act, q_values,
-    q_values_replay, envs_reset, envs_step, rollout_step, rollout_step_dev,
-    q_values_replay_dev, loop_graph).  The op library
+    replay_sample_gather, replay_emit_nstep, train_step, train_graph, policy_act,
+    q_values, q_values_replay, envs_reset, envs_step, rollout_step,
+    rollout_step_dev, q_values_replay_dev, loop_graph).  The op library
     dlopens the engine library ctypes loaded (bind_engine_library: the same file,
     so the same instance owns the engine handles).  Raises EngineUnavailable
     when it is not built."""

@@ -24,6 +24,14 @@ Extra (optional) config keys, all under ``train``:
                'cpu' keeps the networks on the host, where the hot path raises
                ``EngineUnavailable`` (there is no CPU fallback).
 
+    n_step:    n-step returns, 1 (default) .. 8, in ``run_vectorized_training_loop`` and
+               ``run_device_training_loop`` (``sac.nstep``): the loops stage the last n
+               vector steps' rows and store n-step rows, and the engine trains with the
+               discount gamma^n.  Everything that stores one-step rows or replays the
+               loop graph refuses n_step > 1 (ValueError): ``run_training_loop``,
+               ``store_transition``, ``warmup_replay_buffer``, ``graph_steps`` > 0 and
+               ``device_q_values=True``.
+
 After ``load_agent`` with auto-tuning, alpha stays frozen as in the reference
 (it rebinds ``log_alpha`` but not its optimizer, agent.py:550-554); the
 optional ``train.alpha_after_load: tune`` keeps tuning it instead.
@@ -50,6 +58,7 @@ from . import _engine as E
 from .copy_behind import PendingCopies, copy_ring_cells
 from .engine import SacEngine
 from .models import PolicyNetwork, QNetwork
+from .nstep import NStepStage, check_n_step, discount_powers, refuse_n_step
 from .replay_buffer import ReplayBuffer, Transition
 
 try:  # progress bars are optional
@@ -102,6 +111,22 @@ def due_updates_gated(old_steps: int, new_steps: int, len_before: int, capacity:
     if first > new_steps:
         return 0
     return due_updates(first - 1, new_steps, update_frequency, gradient_steps)
+
+
+def due_updates_staged(old_steps: int, new_steps: int, emitted: int, len_before: int, capacity: int,
+                       warming_steps: int, update_frequency: int, gradient_steps: int) -> int:
+    """The gate of a vector step of an n-step loop (``train.n_step``), which
+    stores its rows n - 1 vector steps late.  A step that ``emitted`` its rows is
+    gated exactly as ``due_updates_gated``; a step that emitted none leaves the
+    buffer at ``len_before`` rows, so ``can_update()`` holds at every one of its
+    env steps or at none: ``due_updates`` if ``warming_steps <= capacity`` and
+    ``len_before >= warming_steps``, else 0."""
+    if emitted:
+        return due_updates_gated(old_steps, new_steps, len_before, capacity, warming_steps, update_frequency,
+                                 gradient_steps)
+    if warming_steps > capacity or len_before < warming_steps or new_steps <= old_steps:
+        return 0
+    return due_updates(old_steps, new_steps, update_frequency, gradient_steps)
 
 
 #: times ``run_device_training_loop(graph_steps=K)`` captures its loop graph again because the block's
@@ -311,9 +336,14 @@ class EpisodeStats:
 
 
 class SAC:
+    n_step = 1  # train.n_step; __init__ reads it
+
     def __init__(self, env, config: dict):
         self.env = env
         self.config = config
+        # n-step returns (sac.nstep): the discount powers gpow[0..n]; the engine trains with gpow[n]
+        self.n_step = check_n_step(config["train"].get("n_step", 1))
+        self.gpow = discount_powers(config["sac"]["gamma"], self.n_step)
         self.device = resolve_device(config["train"])
         self.replay_buffer = ReplayBuffer(config["buffer"]["capacity"], device=self.device)
         self.obs_size = env.observation_space.shape[0]
@@ -378,7 +408,7 @@ class SAC:
         s, tr = self.config["sac"], self.config["train"]
         self.engine = SacEngine(
             self.policy_net, self.q_net1, self.q_net2, self.q_net1_target, self.q_net2_target,
-            batch_size=tr["batch_size"], gamma=s["gamma"], tau=s["tau"], actor_lr=s["actor_lr"],
+            batch_size=tr["batch_size"], gamma=self._discount(), tau=s["tau"], actor_lr=s["actor_lr"],
             critic_lr=s["critic_lr"], alpha_lr=s["alpha_lr"], alpha=s["alpha"],
             auto_entropy_tuning=self._auto, device=self.device, precision=self.precision,
             seed=int(tr.get("engine_seed", tr["seed"])))
@@ -394,6 +424,16 @@ class SAC:
             self.alpha_optimizer.state[self.log_alpha] = {
                 "step": torch.tensor(0.0), "exp_avg": eng.alpha_state[2], "exp_avg_sq": eng.alpha_state[3]}
 
+    def _discount(self) -> float:
+        """The discount of the stored rows: sac.gamma, or gamma^n (``gpow[n]``) with train.n_step = n > 1."""
+        return self.config["sac"]["gamma"] if self.n_step == 1 else self.gpow[self.n_step]
+
+    def _new_stage(self, num_envs: int) -> Optional[NStepStage]:
+        """The staging table of one loop run (None at n_step = 1: the loops store their rows directly)."""
+        if self.n_step == 1:
+            return None
+        return NStepStage(self.n_step, num_envs, self.replay_buffer, self.config["sac"]["gamma"])
+
     def _engine(self) -> SacEngine:
         if self.engine is None:
             E.require_gpu(self.device)
@@ -408,9 +448,11 @@ class SAC:
 
     # ------------------------------------------------------------------ data
     def store_transition(self, state: Any, action: Any, reward: float, next_state: Any, done: bool) -> None:
+        refuse_n_step(self.n_step, "store_transition")
         self.replay_buffer.push(state, action, reward, next_state, done)
 
     def warmup_replay_buffer(self, env: Any, steps: int) -> None:
+        refuse_n_step(self.n_step, "warmup_replay_buffer")
         state, _ = env.reset()
         for _ in range(steps):
             action = env.action_space.sample()
@@ -567,7 +609,7 @@ class SAC:
             next_actions, next_log_pi = self.policy_net.sample_action(next_states)
             q1 = self.q_net1_target(next_states, next_actions)
             q2 = self.q_net2_target(next_states, next_actions)
-            return rewards + self.config["sac"]["gamma"] * (1 - dones) * (torch.min(q1, q2) - alpha * next_log_pi)
+            return rewards + self._discount() * (1 - dones) * (torch.min(q1, q2) - alpha * next_log_pi)
 
     def update_q_networks(self, states: Any, actions: Any, target_q_values: Any) -> None:
         """MSE critic losses, one Adam step per critic (agent.py:213-236)."""
@@ -653,6 +695,7 @@ class SAC:
 
     def run_training_loop(self, num_episodes: int, logger=None, tqdm_disable: bool = False,
                           print_rewards: bool = False) -> Dict[str, float]:
+        refuse_n_step(self.n_step, "run_training_loop")
         active_logger = logger or self.logger
         total_steps = 0
         stats = self._episode_stats(active_logger, print_rewards)
@@ -723,7 +766,12 @@ class SAC:
         loop's host counters (``env_steps``, ``gradient_steps``, ``episodes``,
         ``avg_return`` over the last 100 episodes): the hook of
         ``sac.replicas.ReplicaAggregator`` (independent-seed replicas, one per
-        GPU, sac/train_replicas.py).  It must not synchronise the device."""
+        GPU, sac/train_replicas.py).  It must not synchronise the device.
+
+        ``train.n_step`` = n > 1: the N rows of a vector step go to a staging
+        table (``sac.nstep.NStepStage``) and, from the n-th vector step on, one
+        launch stores the N n-step rows of the window that just closed; the
+        gradient steps are gated by ``due_updates_staged``."""
         env = vec_env if vec_env is not None else self.env
         if not hasattr(env, "num_envs"):
             raise TypeError("run_vectorized_training_loop needs a vectorised env (sac.vector_env.SyncVectorEnv)")
@@ -732,7 +780,10 @@ class SAC:
         update_every = tr.get("update_frequency", 1)
         n_grad = tr.get("gradient_steps_per_update", 1)
         N = env.num_envs
+        stage = self._new_stage(N)
         obs, _ = env.reset(seed=seed)
+        if stage is not None:
+            stage.clear()
         ep_ret = np.zeros(N, np.float64)
         ep_len = np.zeros(N, np.int64)
         stats = self._episode_stats(active_logger, print_rewards)
@@ -745,11 +796,17 @@ class SAC:
             next_obs, rewards, terminated, truncated, info = env.step(actions)
             dones = np.logical_or(terminated, truncated)
             len_before = len(self.replay_buffer)
-            self.store_transitions(obs, actions, rewards, info["final_obs"], dones)
+            emitted = N
+            if stage is None:
+                self.store_transitions(obs, actions, rewards, info["final_obs"], dones)
+            else:
+                stage.push(obs, actions, rewards, info["final_obs"], dones)
+                emitted = stage.emit()
             old = total_steps
             total_steps += N
-            grad_steps += self._run_due(due_updates_gated(old, total_steps, len_before, self.replay_buffer.capacity,
-                                                          tr["warming_steps"], update_every, n_grad),
+            grad_steps += self._run_due(due_updates_staged(old, total_steps, emitted, len_before,
+                                                           self.replay_buffer.capacity, tr["warming_steps"],
+                                                           update_every, n_grad),
                                         loss_log, total_steps)
             if q_log is not None:  # env step old + 1 + i logs Q(s'_i, a_i) under the critics after this vector step
                 q_log.record(info["final_obs"], actions, old + 1)
@@ -833,9 +890,21 @@ class SAC:
         run once per block: a callback sees ``env_steps`` advance by K * N.
         Needs ``K + drain_every <= `` the episode ring's (and the Q ring's)
         steps, and the device RNG (``rng_mode`` "reference" feeds the gradient
-        step from the host): otherwise ValueError before any launch."""
+        step from the host): otherwise ValueError before any launch.
+
+        ``train.n_step`` = n > 1: the step is ``SacEngine.rollout_step_nstep``
+        -- the same fused launch into a staging table plus one launch that
+        stores the n-step rows -- gated by ``due_updates_staged``.
+        ``graph_steps`` > 0 and ``device_q_values=True`` are refused (the loop
+        graph needs a second cursor for the staging table)."""
         from .device_envs import DeviceQValueLog, EpisodeDrain
 
+        if graph_steps:
+            refuse_n_step(self.n_step, "graph_steps")
+        if device_q_values:
+            refuse_n_step(self.n_step, "device_q_values")
+        if self.config["logger"]["log_q_values"]:
+            refuse_n_step(self.n_step, "logger.log_q_values in run_device_training_loop")
         env = self._device_env(vec_env, "run_device_training_loop")
         K = int(graph_steps)
         if K:
@@ -862,7 +931,10 @@ class SAC:
         update_every = tr.get("update_frequency", 1)
         n_grad = tr.get("gradient_steps_per_update", 1)
         N = env.num_envs
+        stage = self._new_stage(N)
         env.reset(seed=seed)
+        if stage is not None:
+            stage.clear()
         stats = self._episode_stats(active_logger, print_rewards)
         total_steps = grad_steps = 0
         loss_log = self._loss_log(active_logger)
@@ -915,6 +987,14 @@ class SAC:
                     for due in counts[:vec_steps - done]:
                         step(due)
                         done += 1
+                report()
+        elif stage is not None:  # train.n_step > 1: the rows of a vector step are stored n - 1 steps late
+            for _ in range(vec_steps):
+                len_before = len(rb)
+                emitted = eng.rollout_step_nstep(env, stage)
+                total_steps += N
+                grad_steps += self._run_due(due_updates_staged(total_steps - N, total_steps, emitted, len_before, cap,
+                                                               warming, update_every, n_grad), loss_log, total_steps)
                 report()
         else:
             for _ in range(vec_steps):

@@ -381,6 +381,21 @@ class SacEngine:
             replay._size = min(replay.capacity, replay._size + n)
             replay._pos = (replay._pos + n) % replay.capacity
 
+    def rollout_step_nstep(self, envs, stage, deterministic: bool = False) -> int:
+        """``rollout_step`` with n-step returns (``stage``: a
+        ``sac.nstep.NStepStage`` on the training replay buffer): the fused
+        launch, unchanged, writes the vector step's N one-step rows into the
+        stage's table, then ``stage.emit()`` stores the N n-step rows of the
+        window that closed with it -- one more launch, none for the first n - 1
+        vector steps after a reset.  Returns the rows stored, N or 0.
+        Evaluation (``rollout_step(store=False)``) never touches a stage."""
+        if envs.num_envs != stage.num_envs:
+            raise ValueError(f"rollout_step_nstep: the stage holds steps of {stage.num_envs} environments, not "
+                             f"{envs.num_envs}")
+        self.rollout_step(envs, stage.buffer, deterministic=deterministic)
+        stage.after_rollout(envs.t)
+        return stage.emit()
+
     # ------------------------------------------------------------------ device loop cursor
     def new_cursor(self) -> torch.Tensor:
         """A device loop cursor (include/sac_engine.h): int64 [2][4], slot p =

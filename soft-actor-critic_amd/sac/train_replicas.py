@@ -34,6 +34,11 @@ are evaluated and logged on the device (``device_q_values=True``).
 vector steps from one hipGraph with the loop cursor on the device
 (``run_device_training_loop(graph_steps=K)``); the aggregation callback then
 runs once per block.
+
+``--n-step K`` (1..8) sets ``train.n_step``: n-step returns in either loop
+(``sac.nstep``).  The loop graph does not hold them, so ``--n-step`` above 1
+with ``--graph-steps`` exits, and with ``--device-envs`` the per-env-step Q
+values are not logged (``logger.log_q_values`` must be off).
 """
 from __future__ import annotations
 
@@ -124,8 +129,9 @@ def train_replica(config: dict, make_env: Callable[[], object], num_envs: int, e
     if device_envs:
         # a config with logger.log_q_values (every probe config of the reference) logs them on the device
         extra = {"graph_steps": graph_steps} if graph_steps else {}
+        # n-step returns (train.n_step > 1) have no device Q-value log
         metrics = agent.run_device_training_loop(env_steps, callback=agg, seed=cfg["train"]["seed"],
-                                                 device_q_values=True, **extra)
+                                                 device_q_values=int(cfg["train"].get("n_step", 1)) == 1, **extra)
     else:
         metrics = agent.run_vectorized_training_loop(env_steps, callback=agg, seed=cfg["train"]["seed"])
     return {"metrics": metrics, "aggregate": agg.finish()}
@@ -144,11 +150,22 @@ def parse_args(argv=None) -> argparse.Namespace:
                          "step")
     ap.add_argument("--graph-steps", type=int, default=0,
                     help="with --device-envs: vector steps per hipGraph replay of the loop (even, >= 2; 0 = stepwise)")
+    ap.add_argument("--n-step", type=int, default=None,
+                    help="n-step returns: sets train.n_step (1..8; default: the config's, else 1)")
     a = ap.parse_args(argv)
     if a.device_envs and a.env not in PROBE_ENVS:
         raise SystemExit(f"--device-envs: {a.env!r} is not a probe env ({sorted(PROBE_ENVS)})")
     if a.graph_steps and not a.device_envs:
         raise SystemExit("--graph-steps needs --device-envs (the loop graph holds the device-resident loop)")
+    if a.n_step is not None:
+        from sac.nstep import check_n_step, n_step_refusal
+
+        try:
+            check_n_step(a.n_step, "--n-step")
+        except ValueError as e:
+            raise SystemExit(str(e)) from e
+        if a.n_step > 1 and a.graph_steps:
+            raise SystemExit(n_step_refusal(a.n_step, "graph_steps"))
     return a
 
 
@@ -158,6 +175,8 @@ def main(argv=None) -> int:
 
     with open(a.config) as f:
         config = yaml.safe_load(f)
+    if a.n_step is not None:
+        config["train"]["n_step"] = a.n_step
     rank, world, local = rank_env()
     if not torch.cuda.is_available():
         raise SystemExit("train_replicas: no HIP device visible; replica training runs the HIP engine, one "
