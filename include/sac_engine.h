@@ -36,6 +36,16 @@
  *     (the oldest row once full), state[2] = push generation (incremented by
  *     every push and by ReplayBuffer.clear(); a batch the engine staged for
  *     the next step is used only while it matches).
+ *
+ * The done word
+ *   - a stored row's done is a float d that every path of the gradient step
+ *     reads as y = r + (gamma (1 - d)) (...).  By default d = terminated |
+ *     truncated.  enum sac_done_mode / sac_engine_set_done_mode choose what the
+ *     fused rollout step stores instead: terminated alone, or, for the staging
+ *     table of n-step returns, the END CODE c = terminated + 2 * truncated in
+ *     {0, 1, 2, 3}.  sac_replay_emit_nstep_codes turns a window of end codes
+ *     into a row whose d is 0, 1, or 1 - gamma^k / gamma^n (<= 0) for a window
+ *     the time limit closed after k of n steps.
  */
 #ifndef SAC_ENGINE_H
 #define SAC_ENGINE_H
@@ -234,6 +244,28 @@ int sac_replay_emit_nstep(const sac_replay *stage, const sac_replay *rb, int32_t
                           int64_t newest, const double *gpow_host, int64_t size_host, int64_t pos_host,
                           void *stream);
 
+/* ---- n-step rows from end codes (train.bootstrap_truncated) ---
+ * sac_replay_emit_nstep with a staging table whose done column holds END CODES:
+ * c = terminated + 2 * truncated as a float in {0, 1, 2, 3}, which the rollout
+ * step stores in the mode SAC_DONE_END_CODE (sac_engine_set_done_mode).  k is
+ * the smallest j + 1 with c_j != 0, or n; R, o'_{k-1}, the slots, rb->state and
+ * the validation are sac_replay_emit_nstep's.  The stored done is
+ *   +0.0f                                  if no row of the window ended,
+ *   1.0f                                   if c_{k-1} is 1 or 3 (the closing step terminated),
+ *   (float)(1.0 - gpow[k] / gpow[n])       if c_{k-1} is 2 (truncated only):
+ * one float64 division, one float64 subtraction, one rounding; +0.0f at k = n,
+ * negative for k < n.  The gradient step computes y = r + (gamma_eff (1 - d))
+ * (...) with d read as a float, so on an engine created with gamma = gpow[n]
+ * a window a truncation closed after k steps bootstraps with gamma^k (to within
+ * 4 fp32 ulps) from the true next state, and one a termination closed does not
+ * bootstrap.  gpow_host has n + 1 entries here (gpow[n] is read).  A table that
+ * holds only 0 and 1 gives exactly sac_replay_emit_nstep's rows.
+ * Replaces: nothing in the reference (it stores terminated | truncated,
+ * agent.py:343-356, and one-step targets only). */
+int sac_replay_emit_nstep_codes(const sac_replay *stage, const sac_replay *rb, int32_t n, int32_t num_envs,
+                                int64_t newest, const double *gpow_host, int64_t size_host, int64_t pos_host,
+                                void *stream);
+
 /* Gather rows by LOGICAL index into SoA outputs (s[B][obs], a[B][act], r[B],
  * s2[B][obs], d[B]).  Replaces: ReplayBuffer.sample + SAC.sample_batch's
  * stacking (replay_buffer.py:32-39, agent.py:166-193). */
@@ -273,6 +305,24 @@ int sac_engine_time_phases(sac_engine *e, const sac_replay *rb, int32_t n_steps,
  * log_alpha, alpha, its Adam moments and step count stay as loaded.  Takes
  * effect for launches (and graph replays) after this point on `stream`. */
 int sac_engine_set_alpha_update(sac_engine *e, int32_t enabled, void *stream);
+
+/* What the fused rollout step stores in a row's done word
+ * (train.bootstrap_truncated). */
+enum sac_done_mode {
+  SAC_DONE_ANY_END = 0,     /* terminated | truncated (default; the reference's rows) */
+  SAC_DONE_TERMINATED = 1,  /* terminated alone: a row the time limit ended bootstraps from its final_obs */
+  SAC_DONE_END_CODE = 2     /* terminated + 2 * truncated in {0, 1, 2, 3}: rows of a staging table
+                               (sac_replay_emit_nstep_codes), never of a replay the gradient step reads */
+};
+
+/* Sets the mode (default SAC_DONE_ANY_END).  Host state of the engine, no HIP
+ * call: sac_rollout_step, sac_rollout_step_dev and the capture inside
+ * sac_engine_loop_graph read it when they are called; the mode is part of the
+ * loop graph's cache key, so a call in another mode captures again.  The
+ * `store` argument of those calls keeps its meaning (non-zero = store);
+ * nothing else in a stored row changes with the mode.  SAC_E_INVALID outside
+ * 0..2. */
+int sac_engine_set_done_mode(sac_engine *e, int32_t mode);
 
 /* Health check (synchronises the stream): SAC_E_HIP if an in-launch
  * workgroup hand-off of the role-split phase kernels gave up waiting (the
@@ -437,8 +487,9 @@ int sac_envs_step(const sac_envs *envs, const float *actions, uint64_t t, float 
  * deterministic), the environment step, and the num_envs transitions written
  * into the replay ring at slots (pos_host + i) % capacity, with the new (size,
  * pos) and the push generation written to rb->state as sac_replay_push does.
- * store = 0 leaves the replay untouched (evaluation).  Needs envs->episodes
- * and num_envs <= capacity.
+ * store = 0 leaves the replay untouched (evaluation).  The done word of a
+ * stored row follows the engine's sac_done_mode (default: terminated |
+ * truncated).  Needs envs->episodes and num_envs <= capacity.
  * Replaces: one iteration of SAC.run_vectorized_training_loop up to the
  * updates (select_actions, env.step, store_transitions; sac/agent.py:343-356
  * of the reference per environment). */
@@ -480,7 +531,7 @@ int sac_q_values_replay_dev(sac_engine *e, const sac_replay *rb, const int64_t *
  * q_ring[q_ring_steps][num_envs][2].  Every replay starts at parity 0: the
  * caller seeds cursor[0] before the first replay of a run, and after any vector
  * step it issued another way.  The graph is cached on (envs, rb, cursor,
- * k_steps, the gradient-step counts, q_ring, q_ring_steps) -- a call with
+ * k_steps, the gradient-step counts, q_ring, q_ring_steps, the done mode) -- a call with
  * another key captures again -- apart from sac_engine_train_graph's cache.
  * Replaces: k_steps iterations of SAC.run_vectorized_training_loop
  * (sac/agent.py:343-364 of the reference per environment). */

@@ -690,6 +690,14 @@ int sac_engine_set_alpha_update(sac_engine* e, int32_t enabled, void* stream) {
   return SAC_OK;
 }
 
+int sac_engine_set_done_mode(sac_engine* e, int32_t mode) {
+  if (mode < SAC_DONE_ANY_END || mode > SAC_DONE_END_CODE)
+    return fail(SAC_E_INVALID, "set_done_mode: mode (" + std::to_string(mode) + ") outside 0..2");
+  if (!e) return fail(SAC_E_INVALID, "set_done_mode: null engine");
+  e->done_mode = mode;
+  return SAC_OK;
+}
+
 int sac_engine_check(sac_engine* e, void* stream) {
   if (!e) return fail(SAC_E_INVALID, "null engine");
   uint32_t w[2] = {0, 0};
@@ -949,6 +957,9 @@ static int check_rollout_dims(const sac_engine* e, const sac_envs* envs, const s
   return check_policy_forward(e, who);
 }
 
+// rollout_step_body's `store`: 0 stores nothing, else 1 + the engine's sac_done_mode picks the done word
+static int rollout_store(const sac_engine* e, int32_t store) { return store ? 1 + e->done_mode : 0; }
+
 int sac_rollout_step(sac_engine* e, const sac_envs* envs, const sac_replay* rb, int64_t size_host, int64_t pos_host,
                      uint64_t t, int32_t deterministic, int32_t store, void* stream) {
   int rc = check_rollout_buffers(envs, rb);
@@ -965,7 +976,7 @@ int sac_rollout_step(sac_engine* e, const sac_envs* envs, const sac_replay* rb, 
   const int kind = envs->cfg.kind;
   auto kernel = e->cfg.precision == SAC_PREC_BF16 ? rollout_kernel<bf16>(kind) : rollout_kernel<float>(kind);
   kernel<<<blocks, SAC_THREADS, e->lds_bytes, s>>>(e->d, *envs, *rb, pos_host, new_size, new_pos, t, deterministic ? 1 : 0,
-                                                   store ? 1 : 0);
+                                                   rollout_store(e, store));
   HIPCHK(hipGetLastError());
   return SAC_OK;
 }
@@ -991,7 +1002,8 @@ int sac_rollout_step_dev(sac_engine* e, const sac_envs* envs, const sac_replay* 
   if (rc) return rc;
   rc = check_rollout_dims(e, envs, rb, "rollout_step_dev");
   if (rc) return rc;
-  return launch_rollout_dev(e, envs, rb, cursor, parity, deterministic ? 1 : 0, store ? 1 : 0, (hipStream_t)stream);
+  return launch_rollout_dev(e, envs, rb, cursor, parity, deterministic ? 1 : 0, rollout_store(e, store),
+                            (hipStream_t)stream);
 }
 
 int sac_engine_loop_graph(sac_engine* e, const sac_envs* envs, const sac_replay* rb, int64_t* cursor, int32_t k_steps,
@@ -1025,7 +1037,7 @@ int sac_engine_loop_graph(sac_engine* e, const sac_envs* envs, const sac_replay*
   hipStream_t s = (hipStream_t)stream;
   const sac_engine::LoopKey& k = e->lkey;
   const bool same = e->lgexec && !memcmp(&k.envs, envs, sizeof(sac_envs)) && !memcmp(&k.rb, rb, sizeof(sac_replay)) &&
-                    k.cursor == cursor && k.q_ring == q_ring && k.q_ring_steps == (q_ring ? q_ring_steps : 0) &&
+                    k.cursor == cursor && k.done_mode == e->done_mode && k.q_ring == q_ring && k.q_ring_steps == (q_ring ? q_ring_steps : 0) &&
                     (int)k.grad.size() == k_steps && std::equal(k.grad.begin(), k.grad.end(), grad_steps_host);
   if (!same) {
     if (e->lgexec) (void)hipGraphExecDestroy(e->lgexec);
@@ -1036,7 +1048,7 @@ int sac_engine_loop_graph(sac_engine* e, const sac_envs* envs, const sac_replay*
     // one stream, no forks: node j + 1 follows node j, so the slot vector step j writes is the one j + 1 reads
     HIPCHK(hipStreamBeginCapture(e->cap, hipStreamCaptureModeThreadLocal));
     for (int j = 0; j < k_steps && !rc; ++j) {
-      rc = launch_rollout_dev(e, envs, rb, cursor, j & 1, 0, 1, e->cap);
+      rc = launch_rollout_dev(e, envs, rb, cursor, j & 1, 0, rollout_store(e, 1), e->cap);
       if (!rc && grad_steps_host[j]) launch_steps(e, rb, grad_steps_host[j], nullptr, nullptr, e->cap);
       if (!rc && q_ring) {
         rows.cursor = cursor + 4 * (j & 1);  // the slot this vector step read: its pos is the step's first row
@@ -1054,6 +1066,7 @@ int sac_engine_loop_graph(sac_engine* e, const sac_envs* envs, const sac_replay*
     e->lkey.envs = *envs;
     e->lkey.rb = *rb;
     e->lkey.cursor = cursor;
+    e->lkey.done_mode = e->done_mode;
     e->lkey.q_ring = q_ring;
     e->lkey.q_ring_steps = q_ring ? q_ring_steps : 0;
     e->lkey.grad.assign(grad_steps_host, grad_steps_host + k_steps);
@@ -1161,8 +1174,9 @@ static bool replay_fields(const sac_replay* rb) {
   return rb && rb->obs && rb->act && rb->rew && rb->next_obs && rb->done;
 }
 
-int sac_replay_emit_nstep(const sac_replay* stage, const sac_replay* rb, int32_t n, int32_t num_envs, int64_t newest,
-                          const double* gpow_host, int64_t size_host, int64_t pos_host, void* stream) {
+// sac_replay_emit_nstep (codes = false: gpow_host[0..n-1]) and sac_replay_emit_nstep_codes (true: gpow_host[0..n])
+static int emit_nstep(const sac_replay* stage, const sac_replay* rb, int32_t n, int32_t num_envs, int64_t newest,
+                      const double* gpow_host, int64_t size_host, int64_t pos_host, bool codes, hipStream_t stream) {
   if (!replay_fields(stage)) return fail(SAC_E_INVALID, "emit_nstep: null staging table or field");
   if (!replay_fields(rb) || !rb->state) return fail(SAC_E_INVALID, "emit_nstep: null replay buffer, field or state");
   if (!gpow_host) return fail(SAC_E_INVALID, "emit_nstep: null discount powers");
@@ -1187,15 +1201,33 @@ int sac_replay_emit_nstep(const sac_replay* stage, const sac_replay* rb, int32_t
     return fail(SAC_E_INVALID, "emit_nstep: replay (size, pos) out of range");
   if (stage == rb || stage->obs == rb->obs || stage->rew == rb->rew)
     return fail(SAC_E_INVALID, "emit_nstep: the staging table and the replay buffer are the same table");
-  NStepPowers gp{};
-  for (int j = 0; j < n; ++j) gp.g[j] = gpow_host[j];
   const int64_t new_size = std::min(cap, size_host + (int64_t)num_envs);
   const int64_t new_pos = (pos_host + num_envs) % cap;
   const int blocks = (num_envs + 3) / 4;  // one wave per environment row
-  sac_replay_emit_nstep_kernel<<<blocks, 256, 0, (hipStream_t)stream>>>(*stage, *rb, n, num_envs, newest, gp, pos_host,
-                                                                        new_size, new_pos);
+  if (codes) {
+    NStepCodePowers gp{};
+    for (int j = 0; j <= n; ++j) gp.g[j] = gpow_host[j];
+    sac_replay_emit_nstep_codes_kernel<SAC_NSTEP_MAX + 1>
+        <<<blocks, 256, 0, stream>>>(*stage, *rb, n, num_envs, newest, gp, pos_host, new_size, new_pos);
+  } else {
+    NStepPowers gp{};
+    for (int j = 0; j < n; ++j) gp.g[j] = gpow_host[j];
+    sac_replay_emit_nstep_kernel<<<blocks, 256, 0, stream>>>(*stage, *rb, n, num_envs, newest, gp, pos_host,
+                                                                new_size, new_pos);
+  }
   HIPCHK(hipGetLastError());
   return SAC_OK;
+}
+
+int sac_replay_emit_nstep(const sac_replay* stage, const sac_replay* rb, int32_t n, int32_t num_envs, int64_t newest,
+                          const double* gpow_host, int64_t size_host, int64_t pos_host, void* stream) {
+  return emit_nstep(stage, rb, n, num_envs, newest, gpow_host, size_host, pos_host, false, (hipStream_t)stream);
+}
+
+int sac_replay_emit_nstep_codes(const sac_replay* stage, const sac_replay* rb, int32_t n, int32_t num_envs,
+                                int64_t newest, const double* gpow_host, int64_t size_host, int64_t pos_host,
+                                void* stream) {
+  return emit_nstep(stage, rb, n, num_envs, newest, gpow_host, size_host, pos_host, true, (hipStream_t)stream);
 }
 
 // rows per wave of the records gather: 16 (4x the waves in flight of 64 rows per wave:

@@ -464,8 +464,10 @@ __global__ void sac_envs_step_kernel(sac_envs ev, const float* __restrict__ acti
 // The fused step of one workgroup (SAC_ROWS environments) at RNG step t, its
 // rows going to ring slots (pos + i) % capacity.  new_size / new_pos: the
 // replay's (size, write slot) after this step, as sac_replay_push computes
-// them.  Both kernels below are this body; they differ in where (pos, t) come
-// from.
+// them.  store: 0 stores nothing; 1 / 2 / 3 store the rows with done =
+// terminated | truncated / terminated / terminated + 2 * truncated (the engine's
+// sac_done_mode + 1: rollout_store).  Both kernels below are
+// this body; they differ in where (pos, t) come from.
 template <typename T, int KC>
 __device__ __forceinline__ void rollout_step_body(const EngineDev* __restrict__ Ep, const sac_envs& ev,
                                                   const sac_replay& rb, int64_t pos, int64_t new_size, int64_t new_pos,
@@ -524,7 +526,9 @@ __device__ __forceinline__ void rollout_step_body(const EngineDev* __restrict__ 
     env_account(ev, i, t, eo);
     if (store) {
       rb.rew[slot * rs.one] = (float)eo.reward;
-      rb.done[slot * rs.one] = (eo.terminated || eo.truncated) ? 1.f : 0.f;
+      // the done word by `store`: any end, terminated alone, or the end code of a staging table
+      const int code = (eo.terminated ? 1 : 0) + (eo.truncated ? 2 : 0);
+      rb.done[slot * rs.one] = (float)(store == 3 ? code : store == 2 ? (code & 1) : (code != 0));
     }
   }
   if (store && blockIdx.x == 0 && tid == 0) {  // as replay_push_kernel

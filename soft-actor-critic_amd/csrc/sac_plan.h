@@ -69,6 +69,7 @@ struct sac_engine {
     sac_envs envs;
     sac_replay rb;
     int64_t* cursor;
+    int32_t done_mode;
     float* q_ring;
     int32_t q_ring_steps;
     std::vector<int32_t> grad;  // gradient steps after each rollout: its size is k_steps
@@ -76,6 +77,8 @@ struct sac_engine {
   hipGraphExec_t lgexec = nullptr;
   hipGraph_t lgraph = nullptr;
   LoopKey lkey{};
+  // what the rollout step stores as done (enum sac_done_mode; sac_engine_set_done_mode): host state, read per call
+  int32_t done_mode = 0;
 };
 
 static inline int rup(int x, int m) { return (x + m - 1) / m * m; }

@@ -13,6 +13,8 @@
 //   replay_sample        the index draw of random.sample (replay_buffer.py:39)
 //   replay_sample_gather sampler + gather in one kernel
 //   replay_emit_nstep    the n-step rows of the last n vector steps, staging table -> replay ring (train.n_step)
+//   replay_emit_nstep_codes  the same from a staging table of end codes (train.bootstrap_truncated)
+//   engine_set_done_mode what the rollout step stores as done (enum sac_done_mode); host state, no launch
 //   train_step           SAC.training_step            (sac/agent.py:302-327)
 //   train_graph          a loop of training_step      (sac/agent.py:361-364), hipGraph-replayed
 //   policy_act           SAC.select_action            (sac/agent.py:149-156; models.py:79-92)
@@ -65,6 +67,8 @@ struct EngineApi {
   decltype(&sac_replay_sample_indices) replay_sample_indices = nullptr;
   decltype(&sac_replay_sample_gather) replay_sample_gather = nullptr;
   decltype(&sac_replay_emit_nstep) replay_emit_nstep = nullptr;
+  decltype(&sac_replay_emit_nstep_codes) replay_emit_nstep_codes = nullptr;
+  decltype(&sac_engine_set_done_mode) engine_set_done_mode = nullptr;
   decltype(&sac_engine_train) engine_train = nullptr;
   decltype(&sac_engine_train_graph) engine_train_graph = nullptr;
   decltype(&sac_policy_act) policy_act = nullptr;
@@ -98,6 +102,8 @@ void bind_engine_library(c10::string_view path_) {
   resolve(h, "sac_replay_sample_indices", a.replay_sample_indices);
   resolve(h, "sac_replay_sample_gather", a.replay_sample_gather);
   resolve(h, "sac_replay_emit_nstep", a.replay_emit_nstep);
+  resolve(h, "sac_replay_emit_nstep_codes", a.replay_emit_nstep_codes);
+  resolve(h, "sac_engine_set_done_mode", a.engine_set_done_mode);
   resolve(h, "sac_engine_train", a.engine_train);
   resolve(h, "sac_engine_train_graph", a.engine_train_graph);
   resolve(h, "sac_policy_act", a.policy_act);
@@ -258,7 +264,29 @@ void replay_emit_nstep(at::Tensor& storage, at::Tensor& state, at::IntArrayRef l
                                    gpow.data(), size, pos, stream_of(storage)));
 }
 
+// The same from end codes (include/sac_engine.h sac_replay_emit_nstep_codes): gpow at least n + 1 long.
+void replay_emit_nstep_codes(at::Tensor& storage, at::Tensor& state, at::IntArrayRef layout,
+                             const at::Tensor& stage_storage, const at::Tensor& stage_state,
+                             at::IntArrayRef stage_layout, int64_t n, int64_t num_envs, int64_t newest,
+                             at::ArrayRef<double> gpow, int64_t size, int64_t pos) {
+  Replay r = make_replay(storage, state, layout);
+  Replay st = make_replay(stage_storage, stage_state, stage_layout);
+  TORCH_CHECK(stage_storage.device() == storage.device(), "staging table and replay on different devices");
+  TORCH_CHECK(n >= 1 && n <= SAC_NSTEP_MAX, "n must be in [1, ", SAC_NSTEP_MAX, "]");
+  TORCH_CHECK(num_envs >= 1 && num_envs <= INT32_MAX, "num_envs must be >= 1");
+  TORCH_CHECK(static_cast<int64_t>(gpow.size()) >= n + 1, "gpow must hold at least n + 1 discount powers");
+  Guard g(storage.device());
+  check_rc(api().replay_emit_nstep_codes(&st.d, &r.d, static_cast<int32_t>(n), static_cast<int32_t>(num_envs), newest,
+                                         gpow.data(), size, pos, stream_of(storage)));
+}
+
 // ---------------------------------------------------------------- learner
+void engine_set_done_mode(int64_t engine, int64_t mode) {
+  TORCH_CHECK(engine != 0, "null engine handle");
+  TORCH_CHECK_VALUE(mode >= 0 && mode <= 2, "done mode must be 0 (any end), 1 (terminated) or 2 (end code)");
+  check_rc(api().engine_set_done_mode(reinterpret_cast<sac_engine*>(engine), static_cast<int32_t>(mode)));
+}
+
 void train_step(int64_t engine, at::TensorList state, const at::Tensor& storage, const at::Tensor& rstate,
                 at::IntArrayRef layout, int64_t n_steps, const std::optional<at::Tensor>& indices,
                 const std::optional<at::Tensor>& eps) {
@@ -615,6 +643,10 @@ TORCH_LIBRARY(sac_hip, m) {
   m.def("replay_emit_nstep(Tensor(a!) storage, Tensor(b!) state, int[] layout, Tensor stage_storage, "
         "Tensor stage_state, int[] stage_layout, int n, int num_envs, int newest, float[] gpow, int size, int pos) "
         "-> ()");
+  m.def("replay_emit_nstep_codes(Tensor(a!) storage, Tensor(b!) state, int[] layout, Tensor stage_storage, "
+        "Tensor stage_state, int[] stage_layout, int n, int num_envs, int newest, float[] gpow, int size, int pos) "
+        "-> ()");
+  m.def("engine_set_done_mode(int engine, int mode) -> ()", &engine_set_done_mode);
   m.def("train_step(int engine, Tensor(a!)[] state, Tensor storage, Tensor replay_state, int[] layout, "
         "int n_steps, Tensor? indices=None, Tensor? eps=None) -> ()");
   m.def("train_graph(int engine, Tensor(a!)[] state, Tensor storage, Tensor replay_state, int[] layout, "
@@ -646,6 +678,7 @@ TORCH_LIBRARY_IMPL(sac_hip, CUDA, m) {
   m.impl("replay_sample", &replay_sample);
   m.impl("replay_sample_gather", &replay_sample_gather);
   m.impl("replay_emit_nstep", &replay_emit_nstep);
+  m.impl("replay_emit_nstep_codes", &replay_emit_nstep_codes);
   m.impl("train_step", &train_step);
   m.impl("train_graph", &train_graph);
   m.impl("policy_act", &policy_act);
@@ -665,6 +698,7 @@ TORCH_LIBRARY_IMPL(sac_hip, Meta, m) {
   m.impl("replay_sample", &replay_sample_meta);
   m.impl("replay_sample_gather", &replay_sample_gather_meta);
   m.impl("replay_emit_nstep", &replay_emit_nstep_meta);
+  m.impl("replay_emit_nstep_codes", &replay_emit_nstep_meta);
   m.impl("train_step", &train_step_meta);
   m.impl("train_graph", &train_graph_meta);
   m.impl("policy_act", &policy_act_meta);

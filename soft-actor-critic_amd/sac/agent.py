@@ -32,6 +32,12 @@ Extra (optional) config keys, all under ``train``:
                ``store_transition``, ``warmup_replay_buffer``, ``graph_steps`` > 0 and
                ``device_q_values=True``.
 
+    bootstrap_truncated: false (default) | true.  Time-limit bootstrapping in all four
+               loops: a stored row's ``done`` is ``terminated`` alone, so a
+               row the time limit ended bootstraps from its true next state.  With n_step > 1
+               a window the limit closes after k < n steps stores ``1 - gamma^k / gamma^n``
+               (<= 0), which the gradient step's ``gamma^n (1 - done)`` turns into gamma^k.
+
 After ``load_agent`` with auto-tuning, alpha stays frozen as in the reference
 (it rebinds ``log_alpha`` but not its optimizer, agent.py:550-554); the
 optional ``train.alpha_after_load: tune`` keeps tuning it instead.
@@ -58,7 +64,7 @@ from . import _engine as E
 from .copy_behind import PendingCopies, copy_ring_cells
 from .engine import SacEngine
 from .models import PolicyNetwork, QNetwork
-from .nstep import NStepStage, check_n_step, discount_powers, refuse_n_step
+from .nstep import NStepStage, check_n_step, discount_powers, end_codes, refuse_n_step
 from .replay_buffer import ReplayBuffer, Transition
 
 try:  # progress bars are optional
@@ -337,6 +343,7 @@ class EpisodeStats:
 
 class SAC:
     n_step = 1  # train.n_step; __init__ reads it
+    bootstrap_truncated = False  # train.bootstrap_truncated; __init__ reads it
 
     def __init__(self, env, config: dict):
         self.env = env
@@ -344,6 +351,11 @@ class SAC:
         # n-step returns (sac.nstep): the discount powers gpow[0..n]; the engine trains with gpow[n]
         self.n_step = check_n_step(config["train"].get("n_step", 1))
         self.gpow = discount_powers(config["sac"]["gamma"], self.n_step)
+        # time-limit bootstrapping: the stored done is `terminated` alone
+        self.bootstrap_truncated = config["train"].get("bootstrap_truncated", False)
+        if not isinstance(self.bootstrap_truncated, (bool, np.bool_)):
+            raise ValueError(f"train.bootstrap_truncated must be a bool, got {self.bootstrap_truncated!r}")
+        self.bootstrap_truncated = bool(self.bootstrap_truncated)
         self.device = resolve_device(config["train"])
         self.replay_buffer = ReplayBuffer(config["buffer"]["capacity"], device=self.device)
         self.obs_size = env.observation_space.shape[0]
@@ -413,6 +425,8 @@ class SAC:
             auto_entropy_tuning=self._auto, device=self.device, precision=self.precision,
             seed=int(tr.get("engine_seed", tr["seed"])))
         eng = self.engine
+        if self.bootstrap_truncated:  # at n > 1 the rollout kernel's rows go to the staging table, as end codes
+            eng.set_done_mode(E.DONE_TERMINATED if self.n_step == 1 else E.DONE_END_CODE)
         # torch.optim.Adam objects whose state IS the engine's device state
         for opt, key in ((self.policy_optimizer, "pi"), (self.q1_optimizer, "q1"), (self.q2_optimizer, "q2")):
             ms, vs = eng.adam_views(key)
@@ -432,7 +446,13 @@ class SAC:
         """The staging table of one loop run (None at n_step = 1: the loops store their rows directly)."""
         if self.n_step == 1:
             return None
-        return NStepStage(self.n_step, num_envs, self.replay_buffer, self.config["sac"]["gamma"])
+        return NStepStage(self.n_step, num_envs, self.replay_buffer, self.config["sac"]["gamma"],
+                          bootstrap_truncated=self.bootstrap_truncated)
+
+    def _stored_done(self, terminated, truncated):
+        """The ``done`` of a one-step row: ``terminated | truncated``, or ``terminated`` alone with
+        train.bootstrap_truncated (scalars or arrays)."""
+        return terminated if self.bootstrap_truncated else np.logical_or(terminated, truncated)
 
     def _engine(self) -> SacEngine:
         if self.engine is None:
@@ -458,7 +478,7 @@ class SAC:
             action = env.action_space.sample()
             next_state, reward, terminated, truncated, _ = env.step(action)
             done = terminated or truncated
-            self.store_transition(state, action, reward, next_state, done)
+            self.store_transition(state, action, reward, next_state, bool(self._stored_done(terminated, truncated)))
             state = next_state
             if done:
                 state, _ = env.reset()
@@ -602,7 +622,9 @@ class SAC:
         eng.opt_steps[idx] = t + 1.0
 
     def compute_target_q_values(self, rewards: Any, dones: Any, next_states: Any) -> Any:
-        """y = r + gamma (1 - d)(min Q_t(s', a') - alpha log pi(a'|s')) (agent.py:195-211)."""
+        """y = r + gamma (1 - d)(min Q_t(s', a') - alpha log pi(a'|s')) (agent.py:195-211).
+        ``d`` enters as the float it is, so the fractional ``done`` of train.bootstrap_truncated with
+        n_step > 1 needs nothing else here."""
         self._engine()
         with torch.no_grad():
             alpha = self.alpha.detach()
@@ -713,7 +735,8 @@ class SAC:
                 action = self.select_action(state)
                 next_state, reward, terminated, truncated, _ = self.env.step(action)
                 done = terminated or truncated
-                self.store_transition(state, action, reward, next_state, done)
+                self.store_transition(state, action, reward, next_state,
+                                      bool(self._stored_done(terminated, truncated)))
                 state = next_state
                 episode_return += reward
                 episode_steps += 1
@@ -798,9 +821,11 @@ class SAC:
             len_before = len(self.replay_buffer)
             emitted = N
             if stage is None:
-                self.store_transitions(obs, actions, rewards, info["final_obs"], dones)
-            else:
-                stage.push(obs, actions, rewards, info["final_obs"], dones)
+                self.store_transitions(obs, actions, rewards, info["final_obs"],
+                                       self._stored_done(terminated, truncated))
+            else:  # the stage holds flags, or with train.bootstrap_truncated end codes
+                stage.push(obs, actions, rewards, info["final_obs"],
+                           end_codes(terminated, truncated) if self.bootstrap_truncated else dones)
                 emitted = stage.emit()
             old = total_steps
             total_steps += N

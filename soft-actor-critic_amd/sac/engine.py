@@ -191,6 +191,20 @@ class SacEngine:
         E.check(self.lib.sac_engine_set_alpha_update(self.handle, int(bool(enabled)), self._stream()))
         self.alpha_updates = bool(enabled)
 
+    done_mode = E.DONE_ANY_END
+
+    def set_done_mode(self, mode: int) -> None:
+        """What ``rollout_step``, ``rollout_step_dev`` and ``loop_graph`` store as
+        a row's ``done`` from now on (enum sac_done_mode): ``E.DONE_ANY_END``
+        (default, terminated | truncated), ``E.DONE_TERMINATED`` or
+        ``E.DONE_END_CODE`` (terminated + 2 * truncated, for the staging table of
+        ``sac.nstep.NStepStage(bootstrap_truncated=True)`` only).  Host state of
+        the engine: no launch, no synchronisation."""
+        if isinstance(mode, bool) or not isinstance(mode, int) or not 0 <= mode <= 2:
+            raise ValueError(f"set_done_mode: mode {mode!r} must be 0, 1 or 2")
+        E.check(self.lib.sac_engine_set_done_mode(self.handle, mode))
+        self.done_mode = mode
+
     def sync_params(self) -> None:
         """Re-pack the MFMA compute copies after host-side parameter changes."""
         E.check(self.lib.sac_engine_sync_params(self.handle, self._stream()))
@@ -392,6 +406,10 @@ class SacEngine:
         if envs.num_envs != stage.num_envs:
             raise ValueError(f"rollout_step_nstep: the stage holds steps of {stage.num_envs} environments, not "
                              f"{envs.num_envs}")
+        want = E.DONE_END_CODE if stage.bootstrap_truncated else E.DONE_ANY_END
+        if self.done_mode != want:
+            raise ValueError(f"rollout_step_nstep: the stage {'reads end codes' if want else 'reads done flags'} but "
+                             f"the engine's done mode is {self.done_mode} (set_done_mode({want}))")
         self.rollout_step(envs, stage.buffer, deterministic=deterministic)
         stage.after_rollout(envs.t)
         return stage.emit()

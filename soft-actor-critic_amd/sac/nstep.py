@@ -1,7 +1,7 @@
 """n-step returns for the vectorised and device-resident loops (``train.n_step``).
 
-The stored ``done`` is ``terminated | truncated``, so a window that an episode
-end closes never bootstraps and a window that stays open spans exactly n steps:
+By default the stored ``done`` is ``terminated | truncated``, so a window that
+an episode end closes never bootstraps and one that stays open spans n steps:
 an n-step row is an ordinary replay row trained with the constant discount
 gamma^n.  With ``x_s = (o_s, a_s, r_s, o'_s, d_s)`` the
 one-step rows of one environment for consecutive vector steps, the n-step row
@@ -10,7 +10,17 @@ opened at s is ``(o_s, a_s, R, o'_{s+k-1}, d_{s+k-1})``: k is the smallest j + 1
 r_{s+k-1}`` in float64, accumulated in that order from the first product and
 rounded to fp32 once.
 
-* ``discount_powers`` / ``nstep_rows``: the definition in plain Python and numpy.
+With ``train.bootstrap_truncated`` the staged ``done`` is the
+END CODE ``c = terminated + 2 * truncated`` in {0, 1, 2, 3}.  Any non-zero code
+closes the window as above (k, R and ``next_obs`` do not change); the stored
+``done`` is ``+0.0`` if no row of the window ended, ``1.0`` if the closing step
+terminated (code 1 or 3), and ``fp32(1.0 - gpow[k] / gpow[n])`` -- float64, one
+rounding, ``+0.0`` at k = n and negative below -- if the time limit alone closed
+it (code 2).  The gradient step computes ``y = r + (gamma^n (1 - d)) (...)``, so
+such a row bootstraps with gamma^k from its true next state.
+
+* ``discount_powers`` / ``nstep_rows`` (``codes=True``: from end codes): the
+  definition in plain Python and numpy.
 * ``NStepStage``: the last n vector steps' one-step rows in a staging
   ``ReplayBuffer`` of n * N rows, and ONE launch per vector step
   (``torch.ops.sac_hip.replay_emit_nstep``) that writes the N n-step rows of the
@@ -57,11 +67,18 @@ def discount_powers(gamma: float, n: int) -> List[float]:
     return gpow
 
 
-def nstep_rows(obs, act, rew, next_obs, done, gpow):
+def end_codes(terminated, truncated) -> np.ndarray:
+    """``terminated + 2 * truncated`` as fp32: the end codes of a staging table."""
+    return (np.asarray(terminated, bool).astype(np.float32)
+            + np.float32(2.0) * np.asarray(truncated, bool).astype(np.float32))
+
+
+def nstep_rows(obs, act, rew, next_obs, done, gpow, codes: bool = False):
     """The n-step rows (n = len(gpow) - 1) of one-step rows ``[T][N][...]``
     (``rew`` and ``done`` ``[T][N]``): ``(obs, act, rew, next_obs, done)`` of
     shape ``[T - n + 1][N][...]``, fp32, window s built from steps s .. s + n - 1.
-    T < n gives no rows."""
+    T < n gives no rows.  ``codes``: ``done`` holds end codes (``end_codes``) and
+    the rows' done is 0, 1 or ``fp32(1 - gpow[k] / gpow[n])`` (module docstring)."""
     n = len(gpow) - 1
     obs, act, next_obs = (np.asarray(x, np.float32) for x in (obs, act, next_obs))
     rew = np.asarray(rew, np.float32)
@@ -77,7 +94,12 @@ def nstep_rows(obs, act, rew, next_obs, done, gpow):
         opened = opened & (done[j:j + W] == 0)
     step = np.arange(W)[:, None] + last
     row = np.broadcast_to(np.arange(N)[None, :], (W, N))
-    return (obs[:W].copy(), act[:W].copy(), acc.astype(np.float32), next_obs[step, row], done[step, row])
+    dlast = done[step, row]
+    if codes:
+        share = 1.0 - np.asarray(gpow, np.float64)[last + 1] / float(gpow[n])  # k = last + 1
+        dlast = np.where(dlast == 0, np.float32(0.0),
+                         np.where(dlast == 2, share.astype(np.float32), np.float32(1.0))).astype(np.float32)
+    return (obs[:W].copy(), act[:W].copy(), acc.astype(np.float32), next_obs[step, row], dlast)
 
 
 class NStepStage:
@@ -87,8 +109,10 @@ class NStepStage:
     that closed with it into ``replay`` -- nothing for the first n - 1 vector
     steps after ``clear()``.  ``staged`` counts the vector steps since then."""
 
-    def __init__(self, n: int, num_envs: int, replay: ReplayBuffer, gamma: float):
+    def __init__(self, n: int, num_envs: int, replay: ReplayBuffer, gamma: float, bootstrap_truncated: bool = False):
         self.n = check_n_step(n, "n")
+        # the table's done column holds end codes (``end_codes``; the rollout kernel in DONE_END_CODE mode)
+        self.bootstrap_truncated = bool(bootstrap_truncated)
         self.num_envs = int(num_envs)
         if self.num_envs < 1:
             raise ValueError("num_envs must be >= 1")
@@ -127,11 +151,15 @@ class NStepStage:
 
     def push(self, states, actions, rewards, next_states, dones, t: Optional[int] = None) -> None:
         """Stage one host vector step (the arguments of ``SAC.store_transitions``;
-        N rows in environment order).  ``t``: the environments' step counter
-        after it, if they keep one."""
+        N rows in environment order; with ``bootstrap_truncated`` ``dones`` are
+        the step's ``end_codes``).  ``t``: the environments' step counter after
+        it, if they keep one."""
         if np.asarray(rewards).reshape(-1).shape[0] != self.num_envs:
             raise ValueError(f"NStepStage.push takes one vector step of {self.num_envs} rows")
-        self.buffer.push_batch(states, actions, rewards, next_states, dones)
+        if self.bootstrap_truncated:  # the codes as the floats they are, not as flags
+            self.buffer.push_batch(states, actions, rewards, next_states, dones, done_values=True)
+        else:
+            self.buffer.push_batch(states, actions, rewards, next_states, dones)
         self._count(t)
 
     def after_rollout(self, t: Optional[int] = None) -> None:
@@ -142,8 +170,13 @@ class NStepStage:
     def _launch(self, newest: int) -> None:
         rb, buf = self.replay, self.buffer
         with torch.cuda.device(rb.device):
-            ops().replay_emit_nstep(rb.storage, rb.state, rb.layout_spec, buf.storage, buf.state, buf.layout_spec,
-                                    self.n, self.num_envs, newest, self.gpow[:self.n], rb._size, rb._pos)
+            if self.bootstrap_truncated:
+                ops().replay_emit_nstep_codes(rb.storage, rb.state, rb.layout_spec, buf.storage, buf.state,
+                                              buf.layout_spec, self.n, self.num_envs, newest, self.gpow[:self.n + 1],
+                                              rb._size, rb._pos)
+            else:
+                ops().replay_emit_nstep(rb.storage, rb.state, rb.layout_spec, buf.storage, buf.state, buf.layout_spec,
+                                        self.n, self.num_envs, newest, self.gpow[:self.n], rb._size, rb._pos)
 
     def emit(self) -> int:
         """Write the n-step rows of the window the newest staged step closed:

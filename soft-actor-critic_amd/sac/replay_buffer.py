@@ -130,8 +130,10 @@ class ReplayBuffer:
         if self._n_staged >= self._stage_rows:
             self.flush()
 
-    def push_batch(self, states, actions, rewards, next_states, dones) -> None:
+    def push_batch(self, states, actions, rewards, next_states, dones, done_values: bool = False) -> None:
         """Append n transitions at once (device or host arrays; rows in order).
+        ``done_values``: store ``dones`` as the fp32 values they are (the end
+        codes of an n-step staging table, ``sac.nstep``), not as 0 / 1 flags.
 
         Host inputs are packed into ONE pinned [n][2O+A+2] buffer: one H2D copy
         and one push kernel per batch (the vectorised rollout's per-step cost)."""
@@ -152,7 +154,8 @@ class ReplayBuffer:
             h[:, O:O + A] = ac
             h[:, O + A] = np.asarray(rewards, np.float32).reshape(n)
             h[:, O + A + 1:2 * O + A + 1] = np.asarray(next_states, np.float32).reshape(n, -1)
-            h[:, -1] = np.asarray(dones).reshape(n).astype(bool)
+            d = np.asarray(dones).reshape(n)
+            h[:, -1] = d.astype(np.float32) if done_values else d.astype(bool)
             self._push_device_rows(host.to(self.device, non_blocking=True))
             return
         st = torch.as_tensor(states, dtype=torch.float32)

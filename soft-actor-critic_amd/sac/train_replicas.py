@@ -39,6 +39,10 @@ runs once per block.
 (``sac.nstep``).  The loop graph does not hold them, so ``--n-step`` above 1
 with ``--graph-steps`` exits, and with ``--device-envs`` the per-env-step Q
 values are not logged (``logger.log_q_values`` must be off).
+
+``--bootstrap-truncated`` sets ``train.bootstrap_truncated: true``: time-limit
+bootstrapping in either loop, with or without ``--graph-steps`` and ``--n-step``
+(a stored row's done is ``terminated`` alone).
 """
 from __future__ import annotations
 
@@ -152,6 +156,9 @@ def parse_args(argv=None) -> argparse.Namespace:
                     help="with --device-envs: vector steps per hipGraph replay of the loop (even, >= 2; 0 = stepwise)")
     ap.add_argument("--n-step", type=int, default=None,
                     help="n-step returns: sets train.n_step (1..8; default: the config's, else 1)")
+    ap.add_argument("--bootstrap-truncated", action="store_true",
+                    help="time-limit bootstrapping: sets train.bootstrap_truncated (rows the time limit ended "
+                         "bootstrap from their next state)")
     a = ap.parse_args(argv)
     if a.device_envs and a.env not in PROBE_ENVS:
         raise SystemExit(f"--device-envs: {a.env!r} is not a probe env ({sorted(PROBE_ENVS)})")
@@ -177,6 +184,8 @@ def main(argv=None) -> int:
         config = yaml.safe_load(f)
     if a.n_step is not None:
         config["train"]["n_step"] = a.n_step
+    if a.bootstrap_truncated:
+        config["train"]["bootstrap_truncated"] = True
     rank, world, local = rank_env()
     if not torch.cuda.is_available():
         raise SystemExit("train_replicas: no HIP device visible; replica training runs the HIP engine, one "
