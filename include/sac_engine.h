@@ -324,6 +324,38 @@ enum sac_done_mode {
  * 0..2. */
 int sac_engine_set_done_mode(sac_engine *e, int32_t mode);
 
+/* Where a sampled rollout step's actions come from (train.random_steps;
+ * DESIGN.md §3.13). */
+enum sac_action_source {
+  SAC_ACTIONS_POLICY = 0,   /* the squashed-Gaussian sample of the policy (default) */
+  SAC_ACTIONS_UNIFORM = 1   /* uniform in [-action_scale, action_scale): no policy forward (below) */
+};
+
+/* Sets the source (default SAC_ACTIONS_POLICY).  Host state of the engine, no
+ * HIP call, exactly like sac_engine_set_done_mode: sac_rollout_step,
+ * sac_rollout_step_dev and the capture inside sac_engine_loop_graph read it
+ * when they are called, and it is part of the loop graph's cache key.  With
+ * SAC_ACTIONS_UNIFORM a step with deterministic = 0 is one launch of a kernel
+ * with one thread per environment row that reads nothing of the policy:
+ * component j of env row i at RNG step t is word j % 4 of the Philox4x32-10
+ * block with key = the engine's seed and counter (t lo, t hi, i, 5 << 16 | j /
+ * 4) (which = 5), u = (float)(word >> 8) * 2^-24, a = action_scale * (2.0f * u
+ * - 1.0f): 2u - 1 is exact, the product is the one rounding, the range is
+ * [-action_scale, action_scale).  The environment step, the stored row, the
+ * done word, rb->state and the cursor are the fused step's.  deterministic !=
+ * 0 is the policy mean whatever the source.  The entry points validate as
+ * before (the engine must still be able to run the policy).  SAC_E_INVALID
+ * outside 0..1.
+ * Replaces: env.action_space.sample() of SAC.warmup_replay_buffer
+ * (sac/agent.py:137-147 of the reference), over the policy's own range. */
+int sac_engine_set_action_source(sac_engine *e, int32_t source);
+
+/* The same draws on the host: out_host[n][act_dim], row i component j as above
+ * for (seed, t) and `scale`.  Needs no device and no engine.  SAC_E_INVALID,
+ * with nothing written, for a null out_host, n < 1, act_dim outside 1..32 or a
+ * scale that is not finite and positive. */
+int sac_uniform_actions_host(uint64_t seed, uint64_t t, int32_t n, int32_t act_dim, float scale, float *out_host);
+
 /* Health check (synchronises the stream): SAC_E_HIP if an in-launch
  * workgroup hand-off of the role-split phase kernels gave up waiting (the
  * affected steps are invalid), else 0.  Replaces: nothing (diagnostic). */
@@ -360,6 +392,8 @@ const char *sac_phase_kernel_name(int32_t phase);
  * RNG (Philox4x32-10, key = seed, counter (t, env row, which << 16 | block)):
  * which = 2 the action noise of sac_rollout_step (key = the engine's seed,
  * block = action pair, Box-Muller as the training draws, which use 0 / 1);
+ * which = 5 its uniform actions under SAC_ACTIONS_UNIFORM (key = the engine's
+ * seed, block = four action components; sac_engine_set_action_source);
  * which = 3 the observation a SAC_ENV_RANDOM_OBS environment steps to at t,
  * which = 4 a reset draw at t (key = the environment seed; four draws per
  * block, u = (word >> 8) * 2^-24): the reset observation 2u - 1 of
@@ -489,7 +523,8 @@ int sac_envs_step(const sac_envs *envs, const float *actions, uint64_t t, float 
  * pos) and the push generation written to rb->state as sac_replay_push does.
  * store = 0 leaves the replay untouched (evaluation).  The done word of a
  * stored row follows the engine's sac_done_mode (default: terminated |
- * truncated).  Needs envs->episodes and num_envs <= capacity.
+ * truncated); a sampled step's actions follow its sac_action_source (default:
+ * the policy).  Needs envs->episodes and num_envs <= capacity.
  * Replaces: one iteration of SAC.run_vectorized_training_loop up to the
  * updates (select_actions, env.step, store_transitions; sac/agent.py:343-356
  * of the reference per environment). */
@@ -531,8 +566,9 @@ int sac_q_values_replay_dev(sac_engine *e, const sac_replay *rb, const int64_t *
  * q_ring[q_ring_steps][num_envs][2].  Every replay starts at parity 0: the
  * caller seeds cursor[0] before the first replay of a run, and after any vector
  * step it issued another way.  The graph is cached on (envs, rb, cursor,
- * k_steps, the gradient-step counts, q_ring, q_ring_steps, the done mode) -- a call with
- * another key captures again -- apart from sac_engine_train_graph's cache.
+ * k_steps, the gradient-step counts, q_ring, q_ring_steps, the done mode, the
+ * action source) -- a call with another key captures again -- apart from
+ * sac_engine_train_graph's cache.
  * Replaces: k_steps iterations of SAC.run_vectorized_training_loop
  * (sac/agent.py:343-364 of the reference per environment). */
 int sac_engine_loop_graph(sac_engine *e, const sac_envs *envs, const sac_replay *rb, int64_t *cursor,

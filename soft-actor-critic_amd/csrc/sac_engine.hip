@@ -24,6 +24,7 @@
 #include "../../include/sac_engine_testing.h"
 
 #include <algorithm>
+#include <cmath>
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -332,6 +333,13 @@ static auto rollout_kernel(int kind) {
 template <typename T>
 static auto rollout_dev_kernel(int kind) {
   return with_env_class(kind, [](auto kc) { return sac_rollout_step_dev_kernel<T, decltype(kc)::value>; });
+}
+
+static auto rollout_uniform_kernel(int kind) {
+  return with_env_class(kind, [](auto kc) { return sac_rollout_uniform_kernel<decltype(kc)::value>; });
+}
+static auto rollout_uniform_dev_kernel(int kind) {
+  return with_env_class(kind, [](auto kc) { return sac_rollout_uniform_dev_kernel<decltype(kc)::value>; });
 }
 
 template <typename T>
@@ -698,6 +706,14 @@ int sac_engine_set_done_mode(sac_engine* e, int32_t mode) {
   return SAC_OK;
 }
 
+int sac_engine_set_action_source(sac_engine* e, int32_t source) {
+  if (source < SAC_ACTIONS_POLICY || source > SAC_ACTIONS_UNIFORM)
+    return fail(SAC_E_INVALID, "set_action_source: source (" + std::to_string(source) + ") outside 0..1");
+  if (!e) return fail(SAC_E_INVALID, "set_action_source: null engine");
+  e->action_source = source;
+  return SAC_OK;
+}
+
 int sac_engine_check(sac_engine* e, void* stream) {
   if (!e) return fail(SAC_E_INVALID, "null engine");
   uint32_t w[2] = {0, 0};
@@ -959,6 +975,11 @@ static int check_rollout_dims(const sac_engine* e, const sac_envs* envs, const s
 
 // rollout_step_body's `store`: 0 stores nothing, else 1 + the engine's sac_done_mode picks the done word
 static int rollout_store(const sac_engine* e, int32_t store) { return store ? 1 + e->done_mode : 0; }
+// a sampled step of an engine whose source is SAC_ACTIONS_UNIFORM takes the uniform kernels; the policy mean never does
+static bool rollout_uniform(const sac_engine* e, int deterministic) {
+  return !deterministic && e->action_source == SAC_ACTIONS_UNIFORM;
+}
+static int uniform_blocks(int64_t n) { return (int)((n + SAC_UNIFORM_THREADS - 1) / SAC_UNIFORM_THREADS); }
 
 int sac_rollout_step(sac_engine* e, const sac_envs* envs, const sac_replay* rb, int64_t size_host, int64_t pos_host,
                      uint64_t t, int32_t deterministic, int32_t store, void* stream) {
@@ -974,6 +995,12 @@ int sac_rollout_step(sac_engine* e, const sac_envs* envs, const sac_replay* rb, 
   const int blocks = (int)((n + SAC_ROWS - 1) / SAC_ROWS);
   hipStream_t s = (hipStream_t)stream;
   const int kind = envs->cfg.kind;
+  if (rollout_uniform(e, deterministic)) {
+    rollout_uniform_kernel(kind)<<<uniform_blocks(n), SAC_UNIFORM_THREADS, 0, s>>>(
+        e->cfg.seed, e->cfg.action_scale, *envs, *rb, pos_host, new_size, new_pos, t, rollout_store(e, store));
+    HIPCHK(hipGetLastError());
+    return SAC_OK;
+  }
   auto kernel = e->cfg.precision == SAC_PREC_BF16 ? rollout_kernel<bf16>(kind) : rollout_kernel<float>(kind);
   kernel<<<blocks, SAC_THREADS, e->lds_bytes, s>>>(e->d, *envs, *rb, pos_host, new_size, new_pos, t, deterministic ? 1 : 0,
                                                    rollout_store(e, store));
@@ -981,13 +1008,19 @@ int sac_rollout_step(sac_engine* e, const sac_envs* envs, const sac_replay* rb, 
   return SAC_OK;
 }
 
-// every argument validated by the caller; one launch, no host-side state
+// every argument validated by the caller; one launch, no host-side state written (the action source is read)
 static int launch_rollout_dev(sac_engine* e, const sac_envs* envs, const sac_replay* rb, int64_t* cursor, int parity,
                               int deterministic, int store, hipStream_t s) {
   const int blocks = (envs->cfg.num_envs + SAC_ROWS - 1) / SAC_ROWS;
   const int64_t* cur = cursor + 4 * parity;
   int64_t* nxt = cursor + 4 * (parity ^ 1);
   const int kind = envs->cfg.kind;
+  if (rollout_uniform(e, deterministic)) {
+    rollout_uniform_dev_kernel(kind)<<<uniform_blocks(envs->cfg.num_envs), SAC_UNIFORM_THREADS, 0, s>>>(
+        e->cfg.seed, e->cfg.action_scale, *envs, *rb, cur, nxt, store);
+    HIPCHK(hipGetLastError());
+    return SAC_OK;
+  }
   auto kernel = e->cfg.precision == SAC_PREC_BF16 ? rollout_dev_kernel<bf16>(kind) : rollout_dev_kernel<float>(kind);
   kernel<<<blocks, SAC_THREADS, e->lds_bytes, s>>>(e->d, *envs, *rb, cur, nxt, deterministic, store);
   HIPCHK(hipGetLastError());
@@ -1037,7 +1070,8 @@ int sac_engine_loop_graph(sac_engine* e, const sac_envs* envs, const sac_replay*
   hipStream_t s = (hipStream_t)stream;
   const sac_engine::LoopKey& k = e->lkey;
   const bool same = e->lgexec && !memcmp(&k.envs, envs, sizeof(sac_envs)) && !memcmp(&k.rb, rb, sizeof(sac_replay)) &&
-                    k.cursor == cursor && k.done_mode == e->done_mode && k.q_ring == q_ring && k.q_ring_steps == (q_ring ? q_ring_steps : 0) &&
+                    k.cursor == cursor && k.done_mode == e->done_mode && k.action_source == e->action_source &&
+                    k.q_ring == q_ring && k.q_ring_steps == (q_ring ? q_ring_steps : 0) &&
                     (int)k.grad.size() == k_steps && std::equal(k.grad.begin(), k.grad.end(), grad_steps_host);
   if (!same) {
     if (e->lgexec) (void)hipGraphExecDestroy(e->lgexec);
@@ -1067,11 +1101,19 @@ int sac_engine_loop_graph(sac_engine* e, const sac_envs* envs, const sac_replay*
     e->lkey.rb = *rb;
     e->lkey.cursor = cursor;
     e->lkey.done_mode = e->done_mode;
+    e->lkey.action_source = e->action_source;
     e->lkey.q_ring = q_ring;
     e->lkey.q_ring_steps = q_ring ? q_ring_steps : 0;
     e->lkey.grad.assign(grad_steps_host, grad_steps_host + k_steps);
   }
   for (int r = 0; r < n_replays; ++r) HIPCHK(hipGraphLaunch(e->lgexec, s));
+  return SAC_OK;
+}
+
+int sac_uniform_actions_host(uint64_t seed, uint64_t t, int32_t n, int32_t act_dim, float scale, float* out_host) {
+  if (!out_host || n < 1 || act_dim < 1 || act_dim > 32 || !(scale > 0.f) || !std::isfinite(scale))
+    return fail(SAC_E_INVALID, "uniform_actions: need out != NULL, n >= 1, act_dim in 1..32 and a finite scale > 0");
+  for (int i = 0; i < n; ++i) uniform_actions_row(seed, t, (uint32_t)i, scale, act_dim, out_host + (size_t)i * act_dim);
   return SAC_OK;
 }
 

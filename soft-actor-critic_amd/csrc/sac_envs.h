@@ -27,7 +27,13 @@
 //     that no class carries another's code; the host picks by the environments' kind;
 //   * sac_rollout_step_dev_kernel<T, KC>: the same body with (size, pos,
 //     t) read from a two-slot cursor in device memory, so whole loop iterations
-//     replay from one hipGraph (sac_engine_loop_graph).
+//     replay from one hipGraph (sac_engine_loop_graph);
+//   * rollout_row_tail<KC>: what a row owner does once it holds its action (copy
+//     the observation, store the action, step, account, reward and done word),
+//     shared by the fused body and the uniform kernels;
+//   * sac_rollout_uniform_kernel<KC> / sac_rollout_uniform_dev_kernel<KC>: the
+//     rollout step with uniform-random actions (train.random_steps): one thread
+//     per environment row, no policy forward, no LDS.
 //
 // State is caller-owned global memory (include/sac_engine.h sac_envs).  Every
 // environment row is read and written by exactly one thread of one launch, and
@@ -46,6 +52,7 @@ enum EnvClass { ENV_CLASS_PROBES = 0, ENV_CLASS_PENDULUM = 1, ENV_CLASS_REACHER 
 #define ENV_WHICH_NOISE 2u  // action noise of a rollout step, key = engine seed
 #define ENV_WHICH_STEP 3u   // observation an environment steps to at t, key = env seed
 #define ENV_WHICH_RESET 4u  // its reset observation at t
+#define ENV_WHICH_UNIFORM 5u  // uniform warm-up actions of a rollout step (train.random_steps), key = engine seed
 
 // Four uniforms in [0, 1) for (t, row, which, block): counter (t, row,
 // which << 16 | block), key = seed; the top 24 bits of each output word.
@@ -59,6 +66,21 @@ __host__ __device__ inline void philox_uniform4(uint64_t seed, uint64_t t, uint3
 }
 // 2u - 1 is exact in fp32 (u is a multiple of 2^-24 below 1): obs in [-1, 1)
 __host__ __device__ inline float env_uniform_obs(float u) { return 2.0f * u - 1.0f; }
+
+// The uniform warm-up action components 0..n-1 of env row `row` at RNG step t
+// (DESIGN.md §3.13): component j is word j % 4 of the row's ENV_WHICH_UNIFORM
+// block j / 4, a = scale * (2u - 1) in [-scale, scale).  2u - 1 is exact, the
+// product is the one rounding.  Host-callable: sac_uniform_actions_host is this.
+__host__ __device__ inline void uniform_actions_row(uint64_t seed, uint64_t t, uint32_t row, float scale, int n,
+                                                    float* a) {
+  for (int b = 0; 4 * b < n; ++b) {
+    float u[4];
+    philox_uniform4(seed, t, row, ENV_WHICH_UNIFORM, (uint32_t)b, u);
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if (4 * b + k < n) a[4 * b + k] = scale * env_uniform_obs(u[k]);
+  }
+}
 
 // np.clip on float32: min(max(x, lo), hi) with NaN passed through
 __host__ __device__ inline float clip_f32(float x, float lo, float hi) { return x < lo ? lo : (x > hi ? hi : x); }
@@ -461,6 +483,29 @@ __global__ void sac_envs_step_kernel(sac_envs ev, const float* __restrict__ acti
   truncated[i] = o.truncated ? 1 : 0;
 }
 
+// The row owner's tail: environment row i, holding the action components act[ACT
+// of the class] it takes at RNG step t, copies its observation and action to
+// ring slot `slot` (store != 0), steps, accounts the episode and writes the
+// reward and the done word.  store: as rollout_step_body's.
+template <int KC>
+__device__ __forceinline__ void rollout_row_tail(const sac_envs& ev, const sac_replay& rb, const RowStrides& rs, int O,
+                                                 int i, int64_t slot, uint64_t t,
+                                                 const float (&act)[EnvTask<KC>::ACT], int store) {
+  if (store) {
+    for (int k = 0; k < O; ++k) rb.obs[slot * rs.obs + k] = ev.obs[(size_t)i * O + k];
+#pragma unroll
+    for (int k = 0; k < EnvTask<KC>::ACT; ++k) rb.act[slot * rs.act + k] = act[k];
+  }
+  const EnvOut eo = env_step<KC>(ev, i, t, act, store ? rb.next_obs + slot * rs.obs : nullptr);
+  env_account(ev, i, t, eo);
+  if (store) {
+    rb.rew[slot * rs.one] = (float)eo.reward;
+    // the done word by `store`: any end, terminated alone, or the end code of a staging table
+    const int code = (eo.terminated ? 1 : 0) + (eo.truncated ? 2 : 0);
+    rb.done[slot * rs.one] = (float)(store == 3 ? code : store == 2 ? (code & 1) : (code != 0));
+  }
+}
+
 // The fused step of one workgroup (SAC_ROWS environments) at RNG step t, its
 // rows going to ring slots (pos + i) % capacity.  new_size / new_pos: the
 // replay's (size, write slot) after this step, as sac_replay_push computes
@@ -501,9 +546,8 @@ __device__ __forceinline__ void rollout_step_body(const EngineDev* __restrict__ 
     const float lo = E.ls_min, hi = E.ls_max, scale = E.scale;
     const RowStrides rs = row_strides(rb.row_stride, O, A);
     const int64_t slot = (pos + i) % rb.capacity;
-    if (store)
-      for (int k = 0; k < O; ++k) rb.obs[slot * rs.obs + k] = ev.obs[(size_t)i * O + k];
-    // what the environment takes: registers, not a re-read of the replay row (so never indexed by a run-time j)
+    // what the environment takes: registers (so never indexed by a run-time j).  A is the class's ACT
+    // (check_rollout_dims), so these are all the components the tail stores.
     constexpr int NA = EnvTask<KC>::ACT;
     float act[NA] = {};
     for (int p = 0; 2 * p < A; ++p) {
@@ -519,17 +563,9 @@ __device__ __forceinline__ void rollout_step_body(const EngineDev* __restrict__ 
 #pragma unroll
         for (int k = 0; k < NA; ++k)
           if (j == k) act[k] = a;
-        if (store) rb.act[slot * rs.act + j] = a;
       }
     }
-    const EnvOut eo = env_step<KC>(ev, i, t, act, store ? rb.next_obs + slot * rs.obs : nullptr);
-    env_account(ev, i, t, eo);
-    if (store) {
-      rb.rew[slot * rs.one] = (float)eo.reward;
-      // the done word by `store`: any end, terminated alone, or the end code of a staging table
-      const int code = (eo.terminated ? 1 : 0) + (eo.truncated ? 2 : 0);
-      rb.done[slot * rs.one] = (float)(store == 3 ? code : store == 2 ? (code & 1) : (code != 0));
-    }
+    rollout_row_tail<KC>(ev, rb, rs, O, i, slot, t, act, store);
   }
   if (store && blockIdx.x == 0 && tid == 0) {  // as replay_push_kernel
     rb.state[0] = new_size;
@@ -569,6 +605,62 @@ __global__ void __launch_bounds__(SAC_THREADS) sac_rollout_step_dev_kernel(const
   const int64_t new_size = store ? (size + n < cap ? size + n : cap) : size;
   const int64_t new_pos = store ? (pos + n) % cap : pos;
   rollout_step_body<T, KC>(Ep, ev, rb, pos, new_size, new_pos, t, deterministic, store);
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    nxt[0] = new_size;
+    nxt[1] = new_pos;
+    nxt[2] = (int64_t)t;
+    nxt[3] = 0;
+  }
+}
+
+// ---- The rollout step with uniform-random actions (train.random_steps)
+// One thread per environment row, 256 per workgroup: row i draws its actions
+// (uniform_actions_row, key = the engine's seed, scale = its action_scale, both
+// kernel arguments: nothing of the engine's device state is read) and runs the
+// row owner's tail.  No LDS, no barrier, no atomic.  (pos, new_size, new_pos, t,
+// store) as rollout_step_body's.
+#define SAC_UNIFORM_THREADS 256
+template <int KC>
+__device__ __forceinline__ void rollout_uniform_body(uint64_t seed, float scale, const sac_envs& ev,
+                                                     const sac_replay& rb, int64_t pos, int64_t new_size,
+                                                     int64_t new_pos, uint64_t t, int store) {
+  const int i = blockIdx.x * SAC_UNIFORM_THREADS + threadIdx.x;
+  if (i < ev.cfg.num_envs) {
+    constexpr int NA = EnvTask<KC>::ACT;
+    const int O = ev.cfg.obs_dim;
+    float act[NA];
+    uniform_actions_row(seed, t, (uint32_t)i, scale, NA, act);
+    rollout_row_tail<KC>(ev, rb, row_strides(rb.row_stride, O, NA), O, i, (pos + i) % rb.capacity, t, act, store);
+  }
+  if (store && blockIdx.x == 0 && threadIdx.x == 0) {  // as replay_push_kernel
+    rb.state[0] = new_size;
+    rb.state[1] = new_pos;
+    rb.state[2] += 1;
+  }
+}
+
+template <int KC>
+__global__ void __launch_bounds__(SAC_UNIFORM_THREADS) sac_rollout_uniform_kernel(uint64_t seed, float scale,
+                                                                                 sac_envs ev, sac_replay rb,
+                                                                                 int64_t pos, int64_t new_size,
+                                                                                 int64_t new_pos, uint64_t t,
+                                                                                 int store) {
+  rollout_uniform_body<KC>(seed, scale, ev, rb, pos, new_size, new_pos, t, store);
+}
+
+// The cursor form, exactly as sac_rollout_step_dev_kernel: cur is only read, nxt and rb.state only written.
+template <int KC>
+__global__ void __launch_bounds__(SAC_UNIFORM_THREADS) sac_rollout_uniform_dev_kernel(uint64_t seed, float scale,
+                                                                                     sac_envs ev, sac_replay rb,
+                                                                                     const int64_t* __restrict__ cur,
+                                                                                     int64_t* __restrict__ nxt,
+                                                                                     int store) {
+  const int64_t size = cur[0], pos = cur[1], cap = rb.capacity, n = ev.cfg.num_envs;
+  const uint64_t t = (uint64_t)cur[2] + 1;
+  if (size < 0 || size > cap || pos < 0 || pos >= cap) return;
+  const int64_t new_size = store ? (size + n < cap ? size + n : cap) : size;
+  const int64_t new_pos = store ? (pos + n) % cap : pos;
+  rollout_uniform_body<KC>(seed, scale, ev, rb, pos, new_size, new_pos, t, store);
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     nxt[0] = new_size;
     nxt[1] = new_pos;

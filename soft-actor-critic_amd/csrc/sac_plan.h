@@ -70,6 +70,7 @@ struct sac_engine {
     sac_replay rb;
     int64_t* cursor;
     int32_t done_mode;
+    int32_t action_source;
     float* q_ring;
     int32_t q_ring_steps;
     std::vector<int32_t> grad;  // gradient steps after each rollout: its size is k_steps
@@ -79,6 +80,8 @@ struct sac_engine {
   LoopKey lkey{};
   // what the rollout step stores as done (enum sac_done_mode; sac_engine_set_done_mode): host state, read per call
   int32_t done_mode = 0;
+  // where a sampled rollout step's actions come from (enum sac_action_source; sac_engine_set_action_source): likewise
+  int32_t action_source = 0;
 };
 
 static inline int rup(int x, int m) { return (x + m - 1) / m * m; }

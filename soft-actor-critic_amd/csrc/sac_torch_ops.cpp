@@ -15,6 +15,7 @@
 //   replay_emit_nstep    the n-step rows of the last n vector steps, staging table -> replay ring (train.n_step)
 //   replay_emit_nstep_codes  the same from a staging table of end codes (train.bootstrap_truncated)
 //   engine_set_done_mode what the rollout step stores as done (enum sac_done_mode); host state, no launch
+//   engine_set_action_source  where its sampled actions come from (enum sac_action_source); host state, no launch
 //   train_step           SAC.training_step            (sac/agent.py:302-327)
 //   train_graph          a loop of training_step      (sac/agent.py:361-364), hipGraph-replayed
 //   policy_act           SAC.select_action            (sac/agent.py:149-156; models.py:79-92)
@@ -69,6 +70,7 @@ struct EngineApi {
   decltype(&sac_replay_emit_nstep) replay_emit_nstep = nullptr;
   decltype(&sac_replay_emit_nstep_codes) replay_emit_nstep_codes = nullptr;
   decltype(&sac_engine_set_done_mode) engine_set_done_mode = nullptr;
+  decltype(&sac_engine_set_action_source) engine_set_action_source = nullptr;
   decltype(&sac_engine_train) engine_train = nullptr;
   decltype(&sac_engine_train_graph) engine_train_graph = nullptr;
   decltype(&sac_policy_act) policy_act = nullptr;
@@ -104,6 +106,7 @@ void bind_engine_library(c10::string_view path_) {
   resolve(h, "sac_replay_emit_nstep", a.replay_emit_nstep);
   resolve(h, "sac_replay_emit_nstep_codes", a.replay_emit_nstep_codes);
   resolve(h, "sac_engine_set_done_mode", a.engine_set_done_mode);
+  resolve(h, "sac_engine_set_action_source", a.engine_set_action_source);
   resolve(h, "sac_engine_train", a.engine_train);
   resolve(h, "sac_engine_train_graph", a.engine_train_graph);
   resolve(h, "sac_policy_act", a.policy_act);
@@ -285,6 +288,12 @@ void engine_set_done_mode(int64_t engine, int64_t mode) {
   TORCH_CHECK(engine != 0, "null engine handle");
   TORCH_CHECK_VALUE(mode >= 0 && mode <= 2, "done mode must be 0 (any end), 1 (terminated) or 2 (end code)");
   check_rc(api().engine_set_done_mode(reinterpret_cast<sac_engine*>(engine), static_cast<int32_t>(mode)));
+}
+
+void engine_set_action_source(int64_t engine, int64_t source) {
+  TORCH_CHECK(engine != 0, "null engine handle");
+  TORCH_CHECK_VALUE(source >= 0 && source <= 1, "action source must be 0 (policy) or 1 (uniform)");
+  check_rc(api().engine_set_action_source(reinterpret_cast<sac_engine*>(engine), static_cast<int32_t>(source)));
 }
 
 void train_step(int64_t engine, at::TensorList state, const at::Tensor& storage, const at::Tensor& rstate,
@@ -647,6 +656,7 @@ TORCH_LIBRARY(sac_hip, m) {
         "Tensor stage_state, int[] stage_layout, int n, int num_envs, int newest, float[] gpow, int size, int pos) "
         "-> ()");
   m.def("engine_set_done_mode(int engine, int mode) -> ()", &engine_set_done_mode);
+  m.def("engine_set_action_source(int engine, int source) -> ()", &engine_set_action_source);
   m.def("train_step(int engine, Tensor(a!)[] state, Tensor storage, Tensor replay_state, int[] layout, "
         "int n_steps, Tensor? indices=None, Tensor? eps=None) -> ()");
   m.def("train_graph(int engine, Tensor(a!)[] state, Tensor storage, Tensor replay_state, int[] layout, "

@@ -18,6 +18,8 @@ DEV_LAYERS = 6  # Linear layers per network the library takes (SAC_DEV_LAYERS): 
 PREC_FP32, PREC_BF16 = 0, 1
 # enum sac_done_mode: what the fused rollout step stores as done (train.bootstrap_truncated)
 DONE_ANY_END, DONE_TERMINATED, DONE_END_CODE = 0, 1, 2
+# enum sac_action_source: where a sampled rollout step's actions come from (train.random_steps)
+ACTIONS_POLICY, ACTIONS_UNIFORM = 0, 1
 
 _LIB_NAME = "libsac_engine.so"
 _OPS_NAME = "libsac_torch_ops.so"
@@ -134,6 +136,9 @@ SIGNATURES = {
                                                    ctypes.POINTER(ctypes.c_double), ctypes.c_int64, ctypes.c_int64,
                                                    ctypes.c_void_p]),
     "sac_engine_set_done_mode": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32]),
+    "sac_engine_set_action_source": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32]),
+    "sac_uniform_actions_host": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int32, ctypes.c_int32,
+                                                ctypes.c_float, ctypes.POINTER(ctypes.c_float)]),
     "sac_replay_gather": (ctypes.c_int, [ctypes.POINTER(ReplayDesc), ctypes.c_void_p, ctypes.c_int32]
                           + [ctypes.c_void_p] * 6),
     "sac_replay_sample_indices": (ctypes.c_int, [ctypes.POINTER(ReplayDesc), ctypes.c_int32, ctypes.c_uint64,
@@ -201,7 +206,7 @@ def ops():
     """``torch.ops.sac_hip``: the PyTorch custom ops over the C ABI
     (csrc/sac_torch_ops.cpp: replay_push, replay_gather, replay_sample,
     replay_sample_gather, replay_emit_nstep, replay_emit_nstep_codes,
-    engine_set_done_mode, train_step, train_graph, policy_act,
+    engine_set_done_mode, engine_set_action_source, train_step, train_graph, policy_act,
     q_values, q_values_replay, envs_reset, envs_step, rollout_step,
     rollout_step_dev, q_values_replay_dev, loop_graph).  The op library
     dlopens the engine library ctypes loaded (bind_engine_library: the same file,

@@ -38,6 +38,15 @@ Extra (optional) config keys, all under ``train``:
                a window the limit closes after k < n steps stores ``1 - gamma^k / gamma^n``
                (<= 0), which the gradient step's ``gamma^n (1 - done)`` turns into gamma^k.
 
+    random_steps: K >= 0 (default 0: nothing changes).  The first K env steps of a
+               ``run_vectorized_training_loop`` or ``run_device_training_loop`` run act
+               uniformly at random over the policy's range [-action_scale, action_scale)
+               instead of sampling the untrained policy: vector step v of
+               N envs is uniform iff v * N < K (``uniform_vector_step``).  On the device the
+               step is a launch with no policy forward; the vectorised loop takes the same
+               draws from the host (``SacEngine.uniform_actions``).  ``run_training_loop``
+               keeps the reference's ``warmup_replay_buffer``.
+
 After ``load_agent`` with auto-tuning, alpha stays frozen as in the reference
 (it rebinds ``log_alpha`` but not its optimizer, agent.py:550-554); the
 optional ``train.alpha_after_load: tune`` keeps tuning it instead.
@@ -133,6 +142,28 @@ def due_updates_staged(old_steps: int, new_steps: int, emitted: int, len_before:
     if warming_steps > capacity or len_before < warming_steps or new_steps <= old_steps:
         return 0
     return due_updates(old_steps, new_steps, update_frequency, gradient_steps)
+
+
+def check_random_steps(k, key: str = "train.random_steps") -> int:
+    """``k`` as an int >= 0, or ValueError naming ``key``."""
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or int(k) < 0:
+        raise ValueError(f"{key} must be an integer >= 0, got {k!r}")
+    return int(k)
+
+
+def uniform_vector_step(v: int, num_envs: int, random_steps: int) -> bool:
+    """Whether vector step ``v`` (0-based in the run) of ``num_envs`` envs acts
+    uniformly at random under ``train.random_steps``: iff its first env step,
+    ``v * num_envs``, is one of the first ``random_steps``.  So the uniform
+    steps are the first ceil(random_steps / num_envs) of a run."""
+    return v * num_envs < random_steps
+
+
+def graph_block_policy_only(first: int, num_envs: int, random_steps: int) -> bool:
+    """Whether the block of vector steps that starts at ``first`` may run from
+    the loop graph as far as ``train.random_steps`` goes: none of its steps is
+    uniform.  The uniform steps are a prefix of the run, so that is its first."""
+    return not uniform_vector_step(first, num_envs, random_steps)
 
 
 #: times ``run_device_training_loop(graph_steps=K)`` captures its loop graph again because the block's
@@ -344,6 +375,7 @@ class EpisodeStats:
 class SAC:
     n_step = 1  # train.n_step; __init__ reads it
     bootstrap_truncated = False  # train.bootstrap_truncated; __init__ reads it
+    random_steps = 0  # train.random_steps; __init__ reads it
 
     def __init__(self, env, config: dict):
         self.env = env
@@ -356,6 +388,8 @@ class SAC:
         if not isinstance(self.bootstrap_truncated, (bool, np.bool_)):
             raise ValueError(f"train.bootstrap_truncated must be a bool, got {self.bootstrap_truncated!r}")
         self.bootstrap_truncated = bool(self.bootstrap_truncated)
+        # uniform-random warm-up actions of the vectorised and device loops
+        self.random_steps = check_random_steps(config["train"].get("random_steps", 0))
         self.device = resolve_device(config["train"])
         self.replay_buffer = ReplayBuffer(config["buffer"]["capacity"], device=self.device)
         self.obs_size = env.observation_space.shape[0]
@@ -794,7 +828,12 @@ class SAC:
         ``train.n_step`` = n > 1: the N rows of a vector step go to a staging
         table (``sac.nstep.NStepStage``) and, from the n-th vector step on, one
         launch stores the N n-step rows of the window that just closed; the
-        gradient steps are gated by ``due_updates_staged``."""
+        gradient steps are gated by ``due_updates_staged``.
+
+        ``train.random_steps`` = K > 0: vector step v with v * N < K
+        (``uniform_vector_step``) takes ``SacEngine.uniform_actions(N, v + 1)``
+        instead of the policy's actions -- the draws the device loop takes with
+        the same engine seed, bit for bit; nothing after the actions changes."""
         env = vec_env if vec_env is not None else self.env
         if not hasattr(env, "num_envs"):
             raise TypeError("run_vectorized_training_loop needs a vectorised env (sac.vector_env.SyncVectorEnv)")
@@ -814,8 +853,11 @@ class SAC:
         loss_log = self._loss_log(active_logger)
         q_log = self._q_log(active_logger)
         pbar = _tqdm(range((int(total_env_steps) + N - 1) // N), disable=tqdm_disable)
-        for _ in pbar:
-            actions = self.select_actions(obs)
+        for v in pbar:
+            if uniform_vector_step(v, N, self.random_steps):
+                actions = self._engine().uniform_actions(N, v + 1)
+            else:
+                actions = self.select_actions(obs)
             next_obs, rewards, terminated, truncated, info = env.step(actions)
             dones = np.logical_or(terminated, truncated)
             len_before = len(self.replay_buffer)
@@ -921,7 +963,16 @@ class SAC:
         -- the same fused launch into a staging table plus one launch that
         stores the n-step rows -- gated by ``due_updates_staged``.
         ``graph_steps`` > 0 and ``device_q_values=True`` are refused (the loop
-        graph needs a second cursor for the staging table)."""
+        graph needs a second cursor for the staging table).
+
+        ``train.random_steps`` = K > 0: the engine's action source is
+        ``E.ACTIONS_UNIFORM`` for the vector steps v with v * N < K
+        (``uniform_vector_step``) and ``E.ACTIONS_POLICY`` afterwards, set at
+        the boundary only and back to the policy when the loop leaves, however
+        it leaves.  Gating, the n-step stage, the done mode, the Q-value log
+        and the drains are as without it.  With ``graph_steps`` a block goes
+        through the graph only if none of its steps is uniform
+        (``graph_block_policy_only``); earlier blocks run stepwise."""
         from .device_envs import DeviceQValueLog, EpisodeDrain
 
         if graph_steps:
@@ -972,12 +1023,19 @@ class SAC:
         vec_steps = (int(total_env_steps) + N - 1) // N
         rb, cap, warming = self.replay_buffer, self.replay_buffer.capacity, tr["warming_steps"]
 
+        def source(v: int) -> None:
+            """The engine's action source for vector step ``v``: a call into the engine at the boundary only."""
+            want = E.ACTIONS_UNIFORM if uniform_vector_step(v, N, self.random_steps) else E.ACTIONS_POLICY
+            if eng.action_source != want:
+                eng.set_action_source(want)
+
         def step(due: int) -> None:
             """One vector step issued from the host, with ``due`` gradient steps after it."""
             nonlocal total_steps, grad_steps
             if q_log is not None:
                 rb.flush()  # rows pushed from the host go in first: they move the write slot
             first_slot = rb._pos  # the step's N rows go to ring slots first_slot + i
+            source(total_steps // N)
             eng.rollout_step(env, rb)
             total_steps += N
             grad_steps += self._run_due(due, loss_log, total_steps)
@@ -989,42 +1047,49 @@ class SAC:
             if callback is not None:
                 callback(stats.counters(total_steps, grad_steps))
 
-        if K:
-            cursor, policy, seeded, done = eng.loop_cursor(), GraphBlockPolicy(), False, 0
-            batch = tr["batch_size"]
-            while done < vec_steps:
-                counts = plan_graph_block(total_steps, len(rb), cap, warming, update_every, n_grad, N, K)
-                if vec_steps - done >= K and graph_block_ready(counts, len(rb), cap, warming, batch, N) \
-                        and policy.admit(counts):
-                    if not seeded:  # the last block moved the host mirrors only
-                        eng.seed_cursor(cursor, env, rb)
-                        seeded = True
-                    eng.loop_graph(env, rb, cursor, counts, 1, None if q_log is None else q_log.ring)
-                    if q_log is not None:
-                        q_log.after_graph(K, total_steps + 1)
-                    total_steps += K * N
-                    grad_steps += sum(counts)
-                    if loss_log is not None and sum(counts):
-                        loss_log.after_updates(total_steps)
-                    done += K
-                else:
-                    seeded = False
-                    for due in counts[:vec_steps - done]:
-                        step(due)
-                        done += 1
-                report()
-        elif stage is not None:  # train.n_step > 1: the rows of a vector step are stored n - 1 steps late
-            for _ in range(vec_steps):
-                len_before = len(rb)
-                emitted = eng.rollout_step_nstep(env, stage)
-                total_steps += N
-                grad_steps += self._run_due(due_updates_staged(total_steps - N, total_steps, emitted, len_before, cap,
-                                                               warming, update_every, n_grad), loss_log, total_steps)
-                report()
-        else:
-            for _ in range(vec_steps):
-                step(due_updates_gated(total_steps, total_steps + N, len(rb), cap, warming, update_every, n_grad))
-                report()
+        try:
+            if K:
+                cursor, policy, seeded, done = eng.loop_cursor(), GraphBlockPolicy(), False, 0
+                batch = tr["batch_size"]
+                while done < vec_steps:
+                    counts = plan_graph_block(total_steps, len(rb), cap, warming, update_every, n_grad, N, K)
+                    if vec_steps - done >= K and graph_block_policy_only(done, N, self.random_steps) \
+                            and graph_block_ready(counts, len(rb), cap, warming, batch, N) and policy.admit(counts):
+                        if not seeded:  # the last block moved the host mirrors only
+                            eng.seed_cursor(cursor, env, rb)
+                            seeded = True
+                        source(done)
+                        eng.loop_graph(env, rb, cursor, counts, 1, None if q_log is None else q_log.ring)
+                        if q_log is not None:
+                            q_log.after_graph(K, total_steps + 1)
+                        total_steps += K * N
+                        grad_steps += sum(counts)
+                        if loss_log is not None and sum(counts):
+                            loss_log.after_updates(total_steps)
+                        done += K
+                    else:
+                        seeded = False
+                        for due in counts[:vec_steps - done]:
+                            step(due)
+                            done += 1
+                    report()
+            elif stage is not None:  # train.n_step > 1: the rows of a vector step are stored n - 1 steps late
+                for v in range(vec_steps):
+                    len_before = len(rb)
+                    source(v)
+                    emitted = eng.rollout_step_nstep(env, stage)
+                    total_steps += N
+                    grad_steps += self._run_due(due_updates_staged(total_steps - N, total_steps, emitted, len_before,
+                                                                   cap, warming, update_every, n_grad), loss_log,
+                                                total_steps)
+                    report()
+            else:
+                for _ in range(vec_steps):
+                    step(due_updates_gated(total_steps, total_steps + N, len(rb), cap, warming, update_every, n_grad))
+                    report()
+        finally:  # the source is the loop's, not the engine's: evaluation and later runs start from the policy
+            if eng.action_source != E.ACTIONS_POLICY:
+                eng.set_action_source(E.ACTIONS_POLICY)
         return self._finish_loop(active_logger, stats, (drain, loss_log, q_log), total_env_steps=total_steps,
                                  gradient_steps=grad_steps)
 

@@ -205,6 +205,32 @@ class SacEngine:
         E.check(self.lib.sac_engine_set_done_mode(self.handle, mode))
         self.done_mode = mode
 
+    action_source = E.ACTIONS_POLICY
+
+    def set_action_source(self, source: int) -> None:
+        """Where the sampled actions of ``rollout_step``, ``rollout_step_dev``
+        and ``loop_graph`` come from now on (enum sac_action_source):
+        ``E.ACTIONS_POLICY`` (default) or ``E.ACTIONS_UNIFORM``, uniform in
+        [-action_scale, action_scale) from a launch with no policy forward
+        (train.random_steps; ``uniform_actions`` is the same draw on the host).
+        ``deterministic=True`` stays the policy mean.  Host state of the
+        engine: no launch, no synchronisation."""
+        if isinstance(source, bool) or not isinstance(source, int) or not 0 <= source <= 1:
+            raise ValueError(f"set_action_source: source {source!r} must be 0 or 1")
+        E.check(self.lib.sac_engine_set_action_source(self.handle, source))
+        self.action_source = source
+
+    def uniform_actions(self, n: int, t: int) -> np.ndarray:
+        """The ``[n][act_dim]`` float32 actions a rollout step at RNG step ``t``
+        takes under ``E.ACTIONS_UNIFORM`` for env rows 0..n-1, computed on the
+        host from the engine's seed and action scale
+        (``sac_uniform_actions_host``): no launch, no device."""
+        out = np.empty((int(n), int(self.cfg.act_dim)), np.float32)
+        E.check(self.lib.sac_uniform_actions_host(int(self.cfg.seed), int(t), int(n), int(self.cfg.act_dim),
+                                                  float(self.cfg.action_scale),
+                                                  out.ctypes.data_as(ctypes.POINTER(ctypes.c_float))))
+        return out
+
     def sync_params(self) -> None:
         """Re-pack the MFMA compute copies after host-side parameter changes."""
         E.check(self.lib.sac_engine_sync_params(self.handle, self._stream()))

@@ -43,6 +43,11 @@ values are not logged (``logger.log_q_values`` must be off).
 ``--bootstrap-truncated`` sets ``train.bootstrap_truncated: true``: time-limit
 bootstrapping in either loop, with or without ``--graph-steps`` and ``--n-step``
 (a stored row's done is ``terminated`` alone).
+
+``--random-steps K`` sets ``train.random_steps``: the first K env steps of either
+loop act uniformly at random over the policy's range, with or without
+``--device-envs``, ``--graph-steps``, ``--n-step`` and ``--bootstrap-truncated``
+(DESIGN.md §3.13).
 """
 from __future__ import annotations
 
@@ -159,7 +164,12 @@ def parse_args(argv=None) -> argparse.Namespace:
     ap.add_argument("--bootstrap-truncated", action="store_true",
                     help="time-limit bootstrapping: sets train.bootstrap_truncated (rows the time limit ended "
                          "bootstrap from their next state)")
+    ap.add_argument("--random-steps", type=int, default=None,
+                    help="uniform-random warm-up actions: sets train.random_steps (env steps, >= 0; default: the "
+                         "config's, else 0)")
     a = ap.parse_args(argv)
+    if a.random_steps is not None and a.random_steps < 0:
+        raise SystemExit(f"--random-steps must be an integer >= 0, got {a.random_steps}")
     if a.device_envs and a.env not in PROBE_ENVS:
         raise SystemExit(f"--device-envs: {a.env!r} is not a probe env ({sorted(PROBE_ENVS)})")
     if a.graph_steps and not a.device_envs:
@@ -186,6 +196,8 @@ def main(argv=None) -> int:
         config["train"]["n_step"] = a.n_step
     if a.bootstrap_truncated:
         config["train"]["bootstrap_truncated"] = True
+    if a.random_steps is not None:
+        config["train"]["random_steps"] = a.random_steps
     rank, world, local = rank_env()
     if not torch.cuda.is_available():
         raise SystemExit("train_replicas: no HIP device visible; replica training runs the HIP engine, one "

@@ -5,10 +5,13 @@ of the device and the interval is device time; median of `--repeats`, min .. max
 Nets 2x[256,256] fp32, B = 256, buffer 1e6 rows.
 
     python tools/rollout_launch_time.py [--envs point_mass,pendulum,reacher,cartpole] [--num-envs 4096]
-                                        [--package DIR] [--label this] [--out FILE]
+                                        [--package DIR] [--label this] [--uniform] [--out FILE]
 --package DIR imports the `sac` package (and the libraries beside it) from DIR
 instead of this tree's soft-actor-critic_amd: another build of the project, for
-an A/B in one session.  Prints one line per (env, N) and appends them to --out.
+an A/B in one session.  --uniform adds, after each fused measurement, the same
+measurement with the engine's action source set to uniform (train.random_steps:
+one thread per environment row, no policy forward), labelled `<label>-u`.
+Prints one line per (env, N) and appends them to --out.
 """
 import argparse
 import os
@@ -45,6 +48,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--package", default=os.path.join(R, "soft-actor-critic_amd"))
     ap.add_argument("--label", default="this")
+    ap.add_argument("--uniform", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     sys.path[:0] = [R, os.path.abspath(args.package)]
@@ -65,25 +69,28 @@ def main():
             dv = DeviceVectorEnv.from_env(host_cls(), N, device="cuda")
             agent = SAC(dv, cfg(env))
             eng, rb = agent.engine, agent.replay_buffer
-            for _ in range(50):
-                eng.rollout_step(dv, rb)
-            torch.cuda.synchronize()
-            us = []
-            for _ in range(args.repeats):
-                for _ in range(8):
-                    big[1].copy_(big[0])
-                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                a.record()
-                for _ in range(args.launches):
+            for source, label in ((0, args.label), (1, args.label + "-u"))[:2 if args.uniform else 1]:
+                if source:
+                    eng.set_action_source(source)
+                for _ in range(50):
                     eng.rollout_step(dv, rb)
-                b.record()
                 torch.cuda.synchronize()
-                us.append(a.elapsed_time(b) * 1000.0 / args.launches)
-            eng.check()
+                us = []
+                for _ in range(args.repeats):
+                    for _ in range(8):
+                        big[1].copy_(big[0])
+                    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    a.record()
+                    for _ in range(args.launches):
+                        eng.rollout_step(dv, rb)
+                    b.record()
+                    torch.cuda.synchronize()
+                    us.append(a.elapsed_time(b) * 1000.0 / args.launches)
+                eng.check()
+                lines.append(f"{label:<7} {env:<11} N={N:>5}  {statistics.median(us):>8.3f}   "
+                             f"{min(us):.3f} .. {max(us):.3f}")
+                print(lines[-1], flush=True)
             eng.close()
-            lines.append(f"{args.label:<7} {env:<11} N={N:>5}  {statistics.median(us):>8.3f}   "
-                         f"{min(us):.3f} .. {max(us):.3f}")
-            print(lines[-1], flush=True)
     if args.out:
         with open(args.out, "a") as f:
             f.write("\n".join(lines) + "\n")
